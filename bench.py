@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the nunif hot path on MI355X.  Headline: waifu2x swin_unet 2x, tile 256, synthetic 1080p frames.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 ``--gpus N`` with N > 1 and no rendezvous in the environment RE-LAUNCHES this script as N ranks (one per GPU) through
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1``; launched by torchrun (the
@@ -13,7 +13,12 @@ collective (weak scaling: every rank renders K steps).  ``value`` = input megapi
 ``torch.cuda.synchronize()`` on both sides, max over ranks), the metric BASELINE.json names ("MPix" = source-frame
 pixels).  The default K gives a timed region of >= 3 s.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0 with the contract fields (``metric``,
+``value``, ``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step`` = wall milliseconds of one timed step) and figures derived
+from them.  ``--dump-outputs DIR`` then writes the frames of the last timed step (``dump_outputs``); inputs and weights are
+seeded, so two builds run with the same arguments can be compared output for output.
+
+``--full`` runs every other leg after the timed region and adds to the line (the ``--no-*`` switches drop single legs)
   roofline      — the dominant kernel (largest share of HIP-event time; classes are kernel symbols): algorithmic FLOPs or
                   bytes per launch / measured average launch duration, against the MI355X peak that bounds it
                   (arithmetic intensity vs the 2.5 PFLOP/s / 8 TB/s ridge); ``traffic`` = HBM bytes per launch from the
@@ -70,7 +75,15 @@ def parse_args():
     ap.add_argument("--no-4k", action="store_true", help="skip the 4K 4x (config 3) sub-record")
     ap.add_argument("--no-cunet", action="store_true", help="skip the cunet (config 1 geometry) sub-record")
     ap.add_argument("--no-config5", action="store_true", help="skip the 4K VDA-wrapper + mask-MLBW + video-inpaint (config 5) sub-record")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other leg (single stream, per-kernel roofline, host frames, 4K / cunet / "
+                         "iw3 / config 5 sub-records, CPU baseline, the N > 1 delivery legs); the --no-* switches select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frames the last timed step rendered to DIR/<name>.npy (float32; a fixed seeded sample of each)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def emit(result):
@@ -95,6 +108,24 @@ def relaunch_as_ranks(args):
 
 GATHER_TIMEOUT_S = 420          # watchdog of the N > 1 legs behind the headline (delivery, iw3, cunet; see main)
 CPU_WHOLE_FRAME_BUDGET_S = 40   # cpu_baseline times a whole 1080p frame on the host when the crop predicts at most this
+DUMP_FLOATS = 12 * 2 ** 20      # --dump-outputs: float32 elements over all files of all ranks (48 MiB)
+DUMP_SEED = 20240611
+
+
+def dump_outputs(path, outs, rank, world):
+    """Write the frames of the last timed step as ``path/out_rank<r>_stream<k>.npy`` (float32, flattened).  A frame larger than its
+    share of DUMP_FLOATS is written as a sample: the elements at DUMP_SEED's sorted random positions, the same on every run with the
+    same arguments, so two builds can be compared file for file."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_FLOATS // (world * len(outs))
+    for k, y in enumerate(outs):
+        flat = y.detach().reshape(-1)
+        if flat.numel() > share:
+            idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(DUMP_SEED))[:share].sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(path, f"out_rank{rank}_stream{k}.npy"), flat.float().cpu().numpy())
 
 
 def synth_frame(seed, h, w):
@@ -857,18 +888,22 @@ def main():
         step(i)
     barrier()
     t0 = time.perf_counter()
-    for i in range(args.steps):
+    for i in range(args.steps - 1):
         step(i)
+    last = step(args.steps - 1)             # kept for --dump-outputs; the earlier steps' frames are dropped as they come
     barrier()
     elapsed = time.perf_counter() - t0
     if multi:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [last] if n_streams == 1 else [h[0] for h in last], rank, world)
+    del last
 
     # ---- the same K frames on ONE stream (reported next to `value`; the per-kernel roofline below is measured this way) ----
     single = None
-    if n_streams > 1 and rank == 0 and not dry:
+    if args.full and n_streams > 1 and rank == 0 and not dry:
         n1 = min(args.steps, 100)
         torch.cuda.synchronize(dev)
         t1 = time.perf_counter()
@@ -881,7 +916,7 @@ def main():
 
     # ---- per-kernel timing with HIP events on the launch stream (library hooks), outside the timed region ----------
     roofline, classes = None, []
-    if rank == 0 and not dry:
+    if args.full and rank == 0 and not dry:
         _hip.profile_read(reset=True)
         _hip.profile_enable(True)
         n_prof = max(1, min(5, args.steps))
@@ -920,15 +955,16 @@ def main():
             "output_mpix_per_s": round(value * 4, 2),
             "model_tflops": round(45 * 98e9 * args.steps * n_streams * world / elapsed / 1e12, 2),
             "model_mfma_frac": round(45 * 98e9 * args.steps * n_streams * world / elapsed / 1e12 / (MFMA_PEAK_TFLOPS * world), 4),
-            "roofline": roofline, "kernel_classes": classes,
         }
+        if args.full:
+            result["roofline"], result["kernel_classes"] = roofline, classes
         if multi_gpu is not None:
             result["multi_gpu"] = multi_gpu
             if multi_gpu["ranks_seen"] != world or multi_gpu["distinct_pci_bus_ids"] != world:
                 result.setdefault("errors", []).append("ranks / devices do not add up to --gpus")
         if single is not None:
             result["single_stream"] = single        # one frame at a time on one stream, same build, same run
-        if not args.no_host_frames and not multi:
+        if args.full and not args.no_host_frames and not multi:
             # host uint8 frame -> pinned ring -> H2D -> to_tensor -> render -> quantise -> D2H -> host uint8 frame
             from nunif_amd.frame_ring import FrameRing
             host = [(f.clamp(0, 1) * 255).round().to(torch.uint8).permute(1, 2, 0).contiguous().cpu().numpy() for f in frames]
@@ -964,15 +1000,15 @@ def main():
                 result[key] = {"error": repr(e)}
                 result.setdefault("errors", []).append(f"sub-record {key} raised")
 
-        if not args.no_4k and not multi:
+        if args.full and not args.no_4k and not multi:
             sub_record("scale4x_4k", lambda: scale4x_record(dev))
-        if not args.no_cunet and not multi:
+        if args.full and not args.no_cunet and not multi:
             sub_record("cunet", lambda: cunet_record(dev, with_cpu=not args.no_cpu_baseline))
-        if not args.no_iw3 and not multi:
+        if args.full and not args.no_iw3 and not multi:
             sub_record("iw3", lambda: iw3_record(dev, with_cpu=not args.no_cpu_baseline))
-        if not args.no_config5 and not multi:
+        if args.full and not args.no_config5 and not multi:
             sub_record("config5", lambda: config5_record(dev))
-        if not args.no_cpu_baseline and not multi:      # contract: CPU baseline on rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and not multi:      # contract: CPU baseline on rank 0 at N = 1 only
             base, crop, ref, ref_whole = cpu_baseline(sd, frames[0].cpu())
             got = tiled_render(crop.to(dev), model, tile_size=TILE, batch_size=args.batch_size).cpu()
             mse = torch.mean((got.double() - ref.double()) ** 2).item()
@@ -992,7 +1028,7 @@ def main():
                     "frame": [FRAME_H, FRAME_W], "tile_batch": args.batch_size, "concurrent_streams": n_streams,
                     "max_abs_diff": round(float((outs[0] - ref_whole).abs().max()), 6),
                     "against": "oracle tiled_render of the same whole frame on the host cores (the cpu_baseline pass, output kept)"}
-    if multi:
+    if args.full and multi:
         import threading
         done = threading.Event()
 

@@ -25,7 +25,7 @@ def _bench(args, extra_env=None, timeout=420):
 
 
 def test_two_ranks_through_the_launcher_print_one_line():
-    r, lines = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1"])
+    r, lines = _bench(["--full", "--gpus", "2", "--steps", "3", "--warmup", "1"])
     assert r.returncode == 0, r.stderr[-3000:]
     assert len(lines) == 1, r.stdout[-2000:]                  # rank 0 alone speaks
     rec = json.loads(lines[0])
@@ -43,7 +43,7 @@ def test_two_ranks_through_the_launcher_print_one_line():
 
 
 def test_leg_switches_and_world_size_mismatch():
-    r, lines = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-iw3", "--no-cunet", "--no-config5"])
+    r, lines = _bench(["--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-iw3", "--no-cunet", "--no-config5"])
     assert r.returncode == 0, r.stderr[-3000:]
     rec = json.loads(lines[0])
     assert rec["ok"] and "iw3" not in rec and "cunet" not in rec and "config5" not in rec and rec["gathered"]["frames_delivered"] > 0
@@ -55,9 +55,32 @@ def test_leg_switches_and_world_size_mismatch():
 def test_four_ranks_deliver_every_frame():
     """The driver's scaling run goes 1 / 2 / 4 / 8: the same line at four ranks (odd frame counts per rank, three peers sending to
     rank 0 per round)."""
-    r, lines = _bench(["--gpus", "4", "--steps", "2", "--warmup", "1", "--no-cunet", "--no-config5"])
+    r, lines = _bench(["--full", "--gpus", "4", "--steps", "2", "--warmup", "1", "--no-cunet", "--no-config5"])
     assert r.returncode == 0, r.stderr[-3000:]
     rec = json.loads(lines[0])
     assert rec["ok"] and rec["n_gpus"] == 4 and rec["multi_gpu"]["ranks_seen"] == 4 and rec["multi_gpu"]["distinct_pci_bus_ids"] == 4
     assert rec["gathered"]["frames_delivered"] == rec["gathered"]["frames"] == 16
     assert rec["iw3"]["world"] == 4 and rec["iw3"]["frames_delivered"] == rec["iw3"]["frames"] == 32
+
+
+def test_plain_run_is_the_headline_only_and_dumps_its_last_step(tmp_path):
+    """Without ``--full`` the line holds the timed loop alone; ``--dump-outputs`` writes the last timed step's frames, and the same
+    arguments give the same files."""
+    import numpy as np
+    recs, dumps = [], []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r, lines = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert len(lines) == 1, r.stdout[-2000:]
+        recs.append(json.loads(lines[0]))
+        dumps.append({p.name: np.load(p) for p in sorted(d.iterdir())})
+    rec = recs[0]
+    assert rec["ok"] and rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and rec["value"] > 0
+    assert rec["unit"] == "MPix/s" and rec["higher_is_better"] is True and rec["dtype"] == "f16" and rec["metric"]
+    assert not {"gathered", "iw3", "cunet", "config5", "roofline", "kernel_classes", "cpu_baseline"} & set(rec)
+    assert sorted(dumps[0]) == ["out_rank0_stream0.npy", "out_rank1_stream0.npy"]
+    for name, a in dumps[0].items():
+        assert a.dtype == np.float32 and a.size == 3 * 96 * 160       # the dry stand-in renders 48 x 80 frames at 2x
+        assert np.array_equal(a, dumps[1][name])
+    assert not np.array_equal(dumps[0]["out_rank0_stream0.npy"], dumps[0]["out_rank1_stream0.npy"])

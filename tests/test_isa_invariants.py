@@ -18,26 +18,25 @@ FILES = ["swin_qkv_attn_r.hip", "swin_block_tail.hip", "swin_block_tail_ws.hip",
          "cunet_head.hip"]
 
 
-def _asm(fname):
+def _asm(fname, outdir):
     src = os.path.join(build.CSRC, fname)
-    out = os.path.join("/tmp", f"nunif_isa_{fname}.s")
-    newest = max(os.path.getmtime(p) for p in [src] + build.headers())
-    if not (os.path.exists(out) and os.path.getmtime(out) >= newest):
-        flags = [x for x in build.FLAGS if x != "-fPIC"] + build.EXTRA_FLAGS.get(fname, [])
-        subprocess.run([build.hipcc()] + flags + ["-S", "--cuda-device-only", "-I", os.path.join(ROOT, "include"), "-o", out, src],
-                       check=True, capture_output=True)
+    out = os.path.join(outdir, f"{fname}.s")
+    flags = [x for x in build.FLAGS if x != "-fPIC"] + build.EXTRA_FLAGS.get(fname, [])
+    subprocess.run([build.hipcc()] + flags + ["-S", "--cuda-device-only", "-I", os.path.join(ROOT, "include"), "-o", out, src],
+                   check=True, capture_output=True)
     return open(out).read()
 
 
 @pytest.fixture(scope="module")
-def kernels():
+def kernels(tmp_path_factory):
     """{mangled kernel name: (body, sgprs, vgprs, spills)} over FILES"""
     try:
         build.hipcc()
     except RuntimeError:
         pytest.skip("hipcc not available")
+    outdir = str(tmp_path_factory.mktemp("isa"))        # this checkout's sources only: no assembly shared between runs
     with ThreadPoolExecutor(max_workers=min(6, os.cpu_count() or 1)) as ex:
-        texts = list(ex.map(_asm, FILES))
+        texts = list(ex.map(lambda f: _asm(f, outdir), FILES))
     found = {}
     for text in texts:
         meta = {m.group(1): (int(m.group(2)), int(m.group(3)), int(m.group(4))) for m in re.finditer(

@@ -2,7 +2,7 @@
 cd /root/repo
 OUT=gpurun_out; mkdir -p $OUT
 timeout 1500 python -m pytest tests -m gpu -x -q > $OUT/r06fin2_gpu_suite.log 2>&1; echo "suite rc=$? $(tail -1 $OUT/r06fin2_gpu_suite.log)"
-python bench.py > $OUT/r06fin2_bench_line.json 2> $OUT/r06fin2_bench.err
+python bench.py --full > $OUT/r06fin2_bench_line.json 2> $OUT/r06fin2_bench.err
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/r06fin2_smoke.log 2>&1; tail -1 $OUT/r06fin2_smoke.log
 python - <<'PY'
 import json

@@ -8,7 +8,7 @@ TAG=${1:-n1}
 OUT=$(pwd)/gpurun_out; mkdir -p "$OUT"
 COMMON="--steps 60 --warmup 5 --no-cpu-baseline --no-host-frames --no-4k"
 timeout 900 python bench.py $COMMON --no-iw3 --no-cunet --no-config5 > "$OUT/${TAG}_n1_plain.json" 2> "$OUT/${TAG}_n1_plain.err"
-NUNIF_BENCH_FORCE_DIST=1 timeout 1200 python bench.py --gpus 1 $COMMON > "$OUT/${TAG}_n1_dist.json" 2> "$OUT/${TAG}_n1_dist.err"
+NUNIF_BENCH_FORCE_DIST=1 timeout 1200 python bench.py --full --gpus 1 $COMMON > "$OUT/${TAG}_n1_dist.json" 2> "$OUT/${TAG}_n1_dist.err"
 python - "$OUT/${TAG}_n1_plain.json" "$OUT/${TAG}_n1_dist.json" <<'PY' | tee "$OUT/${TAG}_n1_check.txt"
 import json, sys
 def line(p):

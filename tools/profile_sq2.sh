@@ -5,7 +5,7 @@ set -u
 TAG=${1:-sq2}
 REPO=$(pwd); OUT=$REPO/gpurun_out; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $REPO/bench.py --batch-size 45 --no-cpu-baseline --no-host-frames --streams 1 --steps 2 --warmup 1"
+BENCH="python $REPO/bench.py --full --batch-size 45 --no-cpu-baseline --no-host-frames --streams 1 --steps 2 --warmup 1"
 : > "$OUT/${TAG}_sq2.txt"
 i=0
 for grp in "SQ_VALU_MFMA_COEXEC_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INST_LEVEL_VMEM SQ_INSTS_VMEM SQ_INST_LEVEL_LDS SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_BUSY_CU_CYCLES" \
