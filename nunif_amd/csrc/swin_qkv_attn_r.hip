@@ -306,7 +306,8 @@ qkv_attn_r_kernel(QkvAttnRArgs a) {
         const int wq = (wb * nwy + wy) * nwx + wx;                         // index of this window in the window-major att map
         char *ab = reinterpret_cast<char *>(a.att) + (WM ? (long)wq * (HEADS * 36 * HD * 2) : (long)wb * img_bytes);
         // window-major map: a wave-uniform byte offset (the launcher keeps the map below 4 GB) + a lane constant per tile
-        const unsigned wm_base = (unsigned)__builtin_amdgcn_readfirstlane(wq * (HEADS * 36 * HD * 2));
+        // (in unsigned arithmetic: past 2 GB of map the product no longer fits a signed int; the launcher keeps it below 4 GB)
+        const unsigned wm_base = (unsigned)__builtin_amdgcn_readfirstlane((unsigned)wq * (unsigned)(HEADS * 36 * HD * 2));
 
         // C = 96: the six heads unrolled (every LDS address an immediate); C = 192 does not fit that way (143 spilled registers).
         // DIET & 16 (head_dim 16): the windows that need no shift-region term — all but the last row / column of a shifted map — take
@@ -557,6 +558,8 @@ int launch_qkv_attn_r(const f16 *x, f16 *att, const f16 *wres, const float *bqkv
     a.n_windows = B * (H / 6) * (W / 6);
     a.rev = rev;            // snake order between consecutive kernels (swin_unet.cpp next_dir)
     NUNIF_REQUIRE(!window_major || C == 96, "qkv_attn: the window-major att map exists for C = 96 only");
+    NUNIF_REQUIRE(!window_major || (long)a.n_windows * (6 * 36 * 16 * 2) < (1L << 32),
+                  "qkv_attn: the window-major att map of %d windows does not fit 32-bit byte offsets", a.n_windows);
     const double tok = (double)B * H * W;
     // C = 96: 16 waves per workgroup (120 registers, no register prefetch: four waves per SIMD hide the x loads; 8 waves with
     // prefetch measured 10 % slower, 12 waves in between); C = 192: 8 waves

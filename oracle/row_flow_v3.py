@@ -32,6 +32,7 @@ def window_score_bias_input(window):
 def window_score_bias(sd, p, window):
     """[N,N] additive attention bias: to_bias MLP (Linear 2->h, GELU(erf), Linear h->1) on the relative offsets."""
     index, delta = window_score_bias_input(window)
+    delta = delta.to(sd[p + "to_bias.0.weight"].dtype)             # (a float64 state dict runs the oracle in float64)
     h = F.gelu(F.linear(delta, sd[p + "to_bias.0.weight"], sd[p + "to_bias.0.bias"]))
     b = F.linear(h, sd[p + "to_bias.2.weight"], sd[p + "to_bias.2.bias"])
     n = window[0] * window[1]

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import errloc as E
 from conftest import psnr, sd_checksum, synth_image
 from oracle import seam_blending as OS
 from oracle import swin_unet as O
@@ -106,6 +107,7 @@ def test_forward_matches_golden_and_oracle(hiplib, golden_swin, sf, tag):
     assert float(y.min()) >= 0.0 and float(y.max()) <= 1.0
     assert psnr(y, ref) >= PSNR_MIN, f"PSNR vs reference fixture {psnr(y, ref):.2f} dB"
     assert psnr(y, O.model_forward(sd, x, NAMES[sf])) >= PSNR_MIN
+    E.check_net(y, sd, x, NAMES[sf])              # window by window against the float64 oracle (tests/errloc.py)
 
 
 @pytest.mark.parametrize("sf,tag", [(1, "1x"), (2, "2x"), (4, "4x")])
@@ -199,6 +201,7 @@ def test_forward_112_batch3_and_half_input(hiplib, golden_swin):
     assert psnr(y[0], ref[0]) >= PSNR_MIN
     assert psnr(y[1], O.model_forward(sd, xb[1:2])[0]) >= PSNR_MIN
     assert psnr(y[2], O.model_forward(sd, xb[2:3])[0]) >= PSNR_MIN
+    E.check_net(y, sd, xb, NAMES[2])
     yh = m(x.to("cuda:0").half())
     assert yh.dtype == torch.float16 and psnr(yh.float().cpu(), ref) >= 48.0   # fp16 I/O quantisation on top
 
@@ -263,14 +266,17 @@ def test_full_size_1080p_properties(hiplib):
     z = O.model_forward(sd, t)[0]                       # [3,480,480] covers output [472:952)
     inner = out[:, 472 + 8:952 - 8, 472 + 8:952 - 8].cpu()   # exclude the blended ramps
     assert psnr(inner, z[:, 8:-8, 8:-8]) >= PSNR_MIN
+    E.check_net(inner, sd, t, NAMES[2], origin=8, crop=(8, 472, 8, 472), label="1080p tile (1,1)")
     # the last tile (4,8): mostly replicate padding on the right/bottom; its un-blended interior that lies inside
     # the frame is output rows [1888+8 : 2160), cols [3776+8 : 3840)
     t = xp[:, 4 * 236:4 * 236 + 256, 8 * 236:8 * 236 + 256][None]
     z = O.model_forward(sd, t)[0]
     assert psnr(out[:, 1896:2160, 3784:3840].cpu(), z[:, 8:272, 8:64]) >= PSNR_MIN
+    E.check_net(out[:, 1896:2160, 3784:3840].cpu(), sd, t, NAMES[2], origin=8, crop=(8, 272, 8, 64), label="1080p last tile")
     # first tile (0,0): top/left replicate padding of 8 px
     z = O.model_forward(sd, xp[:, 0:256, 0:256][None])[0]
     assert psnr(out[:, 0:472, 0:472].cpu(), z[:, 0:472, 0:472]) >= PSNR_MIN
+    E.check_net(out[:, 0:472, 0:472].cpu(), sd, xp[:, 0:256, 0:256][None], NAMES[2], crop=(0, 472, 0, 472), label="1080p tile (0,0)")
     # a whole different tile size renders through the same code path
     out208 = tiled_render(img, m, tile_size=208, batch_size=8)
     assert out208.shape == out.shape and float(out208.min()) >= 0 and float(out208.max()) <= 1
@@ -326,10 +332,14 @@ def test_full_size_4k_4x_properties(hiplib):
     z = O.model_forward(sd, t, NAMES[4])[0]                                      # [3,960,960] -> output [3*944 : +960)
     y0, x0 = 3 * 944, 5 * 944
     assert psnr(out[:, y0 + 16:y0 + 944, x0 + 16:x0 + 944].cpu(), z[:, 16:944, 16:944]) >= PSNR_MIN
+    E.check_net(out[:, y0 + 16:y0 + 944, x0 + 16:x0 + 944].cpu(), sd, t, NAMES[4], origin=16, crop=(16, 944, 16, 944),
+                label="4K tile (3,5)")
     t = xp[:, 9 * 236:9 * 236 + 256, 16 * 236:16 * 236 + 256][None]             # last tile (9,16)
     z = O.model_forward(sd, t, NAMES[4])[0]
     y0, x0 = 9 * 944, 16 * 944
     assert psnr(out[:, y0 + 16:8640, x0 + 16:15360].cpu(), z[:, 16:8640 - y0, 16:15360 - x0]) >= PSNR_MIN
+    E.check_net(out[:, y0 + 16:8640, x0 + 16:15360].cpu(), sd, t, NAMES[4], origin=16, crop=(16, 8640 - y0, 16, 15360 - x0),
+                label="4K last tile")
 
 
 def test_load_save_roundtrip_and_errors(hiplib, tmp_path):
@@ -369,6 +379,7 @@ def test_swin_unet_8x(hiplib):
     assert y.shape == ref.shape == (1, 3, 384, 384)
     assert psnr(y, ref) >= PSNR_MIN, psnr(y, ref)
     assert psnr(y, O.model_forward(sd, x, "waifu2x.swin_unet_8x")) >= PSNR_MIN
+    E.check_net(y, sd, x, "waifu2x.swin_unet_8x")
 
 
 def test_swin_unet_4xl(hiplib):
@@ -390,6 +401,7 @@ def test_swin_unet_4xl(hiplib):
     ref = torch.from_numpy(g["y"]).float()
     assert y.shape == ref.shape == (1, 3, 192, 192)
     assert psnr(y, ref) >= PSNR_MIN, psnr(y, ref)
+    E.check_net(y, sd, x, "waifu2x.swin_unet_4xl")
     # whole-frame tiled render through the same handle (2 x 2 tiles of 64) against the oracle's per-tile render
     m2 = M.SwinUNet2x(layer_norm=True).eval()
     sd2 = O.random_state_dict(205, 2, base_dim=96, layer_norm=True)
@@ -398,6 +410,7 @@ def test_swin_unet_4xl(hiplib):
     y2 = m2(x.to("cuda:0")).cpu()
     ref2 = torch.from_numpy(g["y2_ln"]).float()
     assert psnr(y2, ref2) >= PSNR_MIN, psnr(y2, ref2)
+    E.check_net(y2, sd2, x, NAMES[2], label="2x layer_norm")
     from nunif_amd.nunif.utils.render import tiled_render
     img = x[0, :, :50, :60].contiguous()
     out = tiled_render(img.to("cuda:0"), m, tile_size=64, batch_size=4).cpu()

@@ -8,6 +8,7 @@ checked against the reference constructor in the CPU suite).  Tolerance: float P
 import pytest
 import torch
 
+import errloc as E
 from conftest import psnr, synth_image
 from oracle import swin_unet_v2 as OV
 
@@ -42,6 +43,7 @@ def test_forward_matches_oracle(hiplib, sf, capsys):
     assert psnr(y, raw_ref.clamp(0, 1)) >= 50.0
     assert err.max().item() < 2e-2 and err.pow(2).mean().sqrt().item() < 3e-3
     assert torch.equal(y, raw.clamp(0, 1))
+    E.check_net(y, sd, x, NAMES[sf])              # window by window against the float64 oracle (tests/errloc.py)
 
 
 def test_larger_tile_and_batch_of_one(hiplib):
@@ -52,6 +54,7 @@ def test_larger_tile_and_batch_of_one(hiplib):
     y = m(x.to("cuda:0")).cpu()
     assert y.shape == (1, 3, 188, 188)
     assert psnr(y, y_ref) >= 50.0
+    E.check_net(y, sd, x, NAMES[2])
 
 
 def test_tiled_render_and_downscaled(hiplib):
