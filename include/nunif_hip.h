@@ -369,6 +369,33 @@ int nunif_hip_stereo_to_frame(const float *left, const float *right, void *frame
 int nunif_hip_stereo_compose(const float *left, const float *right, float *out, int32_t H, int32_t W,
                              int32_t layout, void *stream);
 
+/* Film grain (waifu2x --grain) and the rotated frame entry of the waifu2x video loop.
+ * The random stream is Philox-4x32-10 keyed by `seed`, with counter (x >> 2, plane * H + y, `counter`, component): a value
+ * depends on (seed, counter, element coordinates) only — not on launch shape, tile order or stream.  Values differ from torch's
+ * for any seed; the distribution is the reference's.  `counter` must be below 2^63.
+ * rgb_noise replaces nunif/utils/rgb_noise.py rgb_noise_like :5-18 on planar fp32 [planes,H,W] (planes = 3 or B*3).
+ *   component 0: the function's result for `level` (1: n1 ~ N(0,1); 2: 0.5*n1 + 0.5*up(n2), n2 ~ N(0,1) on [H/2,W/2], `up` =
+ *   torch's nearest resize); 1: n1 alone; 2: up(n2) alone; 3: the n2 grid itself, out = [planes,H/2,W/2].
+ * apply_rgb_noise replaces rgb_noise.py apply_rgb_noise :21-39 on n fp32 values (any shape; out may alias rgb).
+ * grain_blend replaces waifu2x/ui_utils.py :169-174: buf = noise when `first` (first frame / shape change), else
+ *   buf = buf*(1-speed) + noise*speed.
+ * grain_video_step fuses ui_utils.py :167-177 for one frame: draw rgb_noise_like(level), update noise_buffer [3,H,W] as
+ *   grain_blend does, apply_rgb_noise, then video.py from_tensor :236-245 ((x*max).round()) into the HWC frame (uint8 for
+ *   bits=8, uint16 for bits=16; device or pinned host memory).  Same bytes as rgb_noise -> grain_blend -> apply_rgb_noise ->
+ *   stereo_to_frame(layout 3) with the same seed and counter.
+ * frame_to_tensor_rot replaces video.py to_tensor :218-223 followed by torch.rot90(x, turns, (-2,-1)) of ui_utils.py
+ *   :159-162 (turns 1 = --rotate-left, 3 = --rotate-right): frame HWC [H,W,3] -> chw [3,W,H]. */
+int nunif_hip_rgb_noise(float *out, int32_t planes, int32_t H, int32_t W, int32_t level, int32_t component, uint64_t seed,
+                        uint64_t counter, void *stream);
+int nunif_hip_apply_rgb_noise(const float *rgb, const float *noise, float *out, int64_t n, double strength, double gamma,
+                              int32_t light_decay, double light_decay_strength, void *stream);
+int nunif_hip_grain_blend(float *buf, const float *noise, int64_t n, double speed, int32_t first, void *stream);
+int nunif_hip_grain_video_step(const float *rgb, float *noise_buffer, void *frame, int32_t H, int32_t W, int32_t bits,
+                               int32_t level, uint64_t seed, uint64_t counter, double speed, int32_t first, double strength,
+                               double gamma, int32_t light_decay, double light_decay_strength, void *stream);
+int nunif_hip_frame_to_tensor_rot(const void *frame, float *chw, int32_t H, int32_t W, int32_t bits, int32_t turns,
+                                  void *stream);
+
 /* Pointwise depth -> disparity mappers of iw3/mapper.py :7-118.  kind: 0 identity, 1 pow2, 2 softplus01_legacy(c=p0),
  * 3 softplus01(bias=p0, scale=p1), 4 inv_softplus01(bias=p0, scale=p1), 5 distance_to_disparity(c=p0),
  * 6 shift_relative_depth(min_distance=p0, max_distance=p1). */

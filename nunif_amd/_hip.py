@@ -10,8 +10,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # NUNIF_HIP_LIB: another build of the same ABI (same-box A/B runs of two kernel versions, tools/ab_lib.sh); never a fallback
 LIB_PATH = os.environ.get("NUNIF_HIP_LIB") or os.path.join(_HERE, "libnunif_hip.so")
 
-c_void_p, c_int32, c_int64, c_float, c_char_p, c_double = (
-    ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_char_p, ctypes.c_double)
+c_void_p, c_int32, c_int64, c_float, c_char_p, c_double, c_uint64 = (
+    ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_char_p, ctypes.c_double, ctypes.c_uint64)
 
 
 class NunifHipError(RuntimeError):
@@ -121,6 +121,12 @@ SIGNATURES = {
     "nunif_hip_frame_to_tensor": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "nunif_hip_stereo_to_frame": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "nunif_hip_stereo_compose": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "nunif_hip_rgb_noise": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_uint64, c_uint64, c_void_p]),
+    "nunif_hip_apply_rgb_noise": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_int32, c_double, c_void_p]),
+    "nunif_hip_grain_blend": (c_int32, [c_void_p, c_void_p, c_int64, c_double, c_int32, c_void_p]),
+    "nunif_hip_grain_video_step": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_uint64, c_uint64,
+                                             c_double, c_int32, c_double, c_double, c_int32, c_double, c_void_p]),
+    "nunif_hip_frame_to_tensor_rot": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "nunif_hip_map_depth": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_double, c_double, c_void_p]),
     "nunif_hip_swin_unet_debug_taps": (c_int32, [c_void_p, c_int32]),
     "nunif_hip_swin_unet_get_tap": (c_int32, [c_void_p, c_int32, c_char_p, c_int32, c_void_p, c_int64,

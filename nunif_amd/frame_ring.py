@@ -21,7 +21,7 @@ from .iw3 import _ops
 
 class FrameRing:
     def __init__(self, process_fn, in_shape, out_shape, device="cuda:0", depth=3, bits=8, zero_copy=True, out_mode="copy",
-                 edge_streams=True):
+                 edge_streams=True, enter_fn=None, leave_fn=None, in_bits=None):
         """``process_fn(chw_float_tensor) -> chw_float_tensor in [0,1]`` runs on the ring's stream.
         in_shape / out_shape: (H, W, 3) of the uint8 (or uint16 when bits=16) HWC frames.
 
@@ -31,6 +31,15 @@ class FrameRing:
         stream or on their own, blocked the submitting thread for a whole frame time (5-7 ms inside ``copy_``) and
         the pipeline ran at 19-20 ms per 1080p 2x frame against 9.5 ms of GPU work."""
         assert bits in (8, 16) and out_mode in ("copy", "view")
+        # in_bits: the bit depth of the frames going IN when it is not the output's (a 10-bit source written to an 8-bit pixel
+        # format, or the reverse): the entry kernel divides by the source's own maximum, as VU.to_tensor does
+        self.in_bits = in_bits = bits if in_bits is None else in_bits
+        assert in_bits in (8, 16)
+        # the two edge conversions; a caller may fold more into them (waifu2x video: a quarter turn into the entry, the film
+        # grain into the leave).  enter_fn(hwc, device=...) -> chw float; leave_fn(chw float, bits, out=hwc or None) -> hwc.
+        # Each runs on ONE stream of the ring for every frame, in submission order, so it may keep state across frames.
+        self.enter_fn = enter_fn or _ops.frame_to_tensor
+        self.leave_fn = leave_fn or _ops.to_frame
         # out_mode: what a finished frame is handed back as.  "copy" = a fresh numpy array (safe to keep; costs one
         # single-threaded 25 MB host memcpy + a page-faulting allocation per 1080p 2x frame, which — not PCIe — was the
         # 21 ms / frame of round 1: tools/pcie_probe.py moves the same bytes over PCIe in 0.6 ms with no stalls at all);
@@ -45,12 +54,13 @@ class FrameRing:
             raise RuntimeError("FrameRing needs a ROCm device; there is no CPU path")
         self.process_fn, self.bits, self.depth, self.zero_copy = process_fn, bits, depth, zero_copy
         t_dtype = torch.uint8 if bits == 8 else torch.int16          # int16 carries the uint16 bit pattern
+        i_dtype = torch.uint8 if in_bits == 8 else torch.int16
         self.slots = []
         for _ in range(depth):
             self.slots.append({
-                "h_in": torch.empty(in_shape, dtype=t_dtype).pin_memory(),
+                "h_in": torch.empty(in_shape, dtype=i_dtype).pin_memory(),
                 "h_out": torch.empty(out_shape, dtype=t_dtype).pin_memory(),
-                "d_in": None if zero_copy else torch.empty(in_shape, dtype=t_dtype, device=self.device),
+                "d_in": None if zero_copy else torch.empty(in_shape, dtype=i_dtype, device=self.device),
                 "done": torch.cuda.Event(),
                 "busy": False,
             })
@@ -76,12 +86,12 @@ class FrameRing:
             # host memcpy into the pinned buffer — with numpy, NOT ``Tensor.copy_``: torch's copy into a pinned tensor took
             # 0.14 ms at the median but 70-90 ms every 3rd-4th frame (tools/ring_trace.py: 13 of round 1's 21 ms per frame;
             # the "platform stall" of DESIGN.md round 1 was this call), np.copyto is a flat 0.13 ms
-            np.copyto(slot["h_in"].numpy(), frame.view(np.int16) if self.bits == 16 else frame)
+            np.copyto(slot["h_in"].numpy(), frame.view(np.int16) if self.in_bits == 16 else frame)
         if self.zero_copy and self.edge_streams:
             # three streams: the PCIe-bound edge kernels of neighbouring frames (0.12 ms in, 0.45 ms out for 1080p -> 2x) run
             # beside the render of the frame in the middle instead of in front of / behind it on one stream
             with torch.cuda.stream(self.in_stream):
-                x = _ops.frame_to_tensor(slot["h_in"], device=self.device)
+                x = self.enter_fn(slot["h_in"], device=self.device)
                 ev_in = torch.cuda.Event()
                 ev_in.record(self.in_stream)
             with torch.cuda.stream(self.stream):
@@ -93,20 +103,20 @@ class FrameRing:
             with torch.cuda.stream(self.out_stream):
                 self.out_stream.wait_event(ev_c)
                 y.record_stream(self.out_stream)
-                _ops.to_frame(y, self.bits, out=slot["h_out"])
+                self.leave_fn(y, self.bits, out=slot["h_out"])
                 slot["done"].record(self.out_stream)
             slot["busy"] = True
             self._pending.append(slot)
             return out
         with torch.cuda.stream(self.stream):
             if self.zero_copy:
-                x = _ops.frame_to_tensor(slot["h_in"], device=self.device)
+                x = self.enter_fn(slot["h_in"], device=self.device)
                 y = self.process_fn(x)
-                _ops.to_frame(y, self.bits, out=slot["h_out"])
+                self.leave_fn(y, self.bits, out=slot["h_out"])
             else:
                 slot["d_in"].copy_(slot["h_in"], non_blocking=True)
-                y = self.process_fn(_ops.frame_to_tensor(slot["d_in"]))
-                slot["h_out"].copy_(_ops.to_frame(y, self.bits), non_blocking=True)
+                y = self.process_fn(self.enter_fn(slot["d_in"]))
+                slot["h_out"].copy_(self.leave_fn(y, self.bits), non_blocking=True)
             slot["done"].record(self.stream)
         slot["busy"] = True
         self._pending.append(slot)
@@ -132,7 +142,7 @@ class FrameRing:
         if slot["busy"]:
             self._held = self._collect()
         arr = self.slots[self._next]["h_in"].numpy()
-        return arr.view(np.uint16) if self.bits == 16 else arr
+        return arr.view(np.uint16) if self.in_bits == 16 else arr
 
     def drain(self):
         outs = []

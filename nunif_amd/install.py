@@ -59,6 +59,11 @@ PATCHES = [
     ("iw3.utils", "postprocess_image"),
     ("iw3.utils", "preprocess_image"),
     ("iw3.equirectangular", "equirectangular_projection"),
+    # film grain (nunif/utils/rgb_noise.py:5-39; waifu2x/ui_utils.py process_image :57-61 binds both by name) and the waifu2x
+    # video loop (waifu2x/ui_utils.py:104-206: the frame callback runs on Waifu2xVideoStream, the rest is the reference's code)
+    ("nunif.utils.rgb_noise", "rgb_noise_like"),
+    ("nunif.utils.rgb_noise", "apply_rgb_noise"),
+    ("waifu2x.ui_utils", "process_video"),
 ]
 
 # reference packages whose modules may hold ``from ... import`` copies of a patched name
@@ -151,6 +156,17 @@ def install(registry=True, strict=True):
             importlib.import_module("nunif.models.register")._models.update(reg_saved)
         raise
     return report
+
+
+def original(ref_name, attr):
+    """The reference's own object behind a patched name while installed (``None`` otherwise): for engine functions that
+    delegate everything but their hot path to the reference's code."""
+    if _state is None:
+        return None
+    for mod, key, orig in _state["bindings"]:
+        if mod.__name__ == ref_name and key == attr:
+            return orig
+    return None
 
 
 def uninstall():

@@ -159,10 +159,19 @@ def backward_warp(c, depth, divergence, convergence, synthetic_view):
     return left, right
 
 
-def frame_to_tensor(frame_hwc, device=None):
+def _frame_to_tensor_call(src, out, h, w, bits, turns, dev):
+    if turns == 0:
+        _hip.check(_hip.lib().nunif_hip_frame_to_tensor(_p(src), _p(out), h, w, bits, _hip.current_stream_ptr(dev)))
+    else:
+        _hip.check(_hip.lib().nunif_hip_frame_to_tensor_rot(_p(src), _p(out), h, w, bits, turns, _hip.current_stream_ptr(dev)))
+
+
+def frame_to_tensor(frame_hwc, device=None, turns=0):
     """uint8 / int16-held-uint16 HWC [H,W,3] -> CHW float on the device (VU.to_tensor, video.py:218-223).
     The frame is either a device tensor or a PINNED host tensor (zero-copy: the kernel reads it over PCIe; pass
-    ``device``)."""
+    ``device``).  ``turns`` = 1 / 3 folds ``torch.rot90(x, turns, (-2, -1))`` into the gather (waifu2x --rotate-left /
+    --rotate-right, ui_utils.py:159-162): the result is [3,W,H]."""
+    assert turns in (0, 1, 3)
     if frame_hwc.device.type != "cuda":
         if not (frame_hwc.is_pinned() and device is not None):
             raise RuntimeError("frame_to_tensor: tensor must live on a ROCm device or in pinned host memory "
@@ -171,9 +180,9 @@ def frame_to_tensor(frame_hwc, device=None):
         assert frame_hwc.dim() == 3 and frame_hwc.shape[2] == 3 and frame_hwc.is_contiguous()
         bits = 8 if frame_hwc.dtype == torch.uint8 else 16
         h, w, _ = frame_hwc.shape
-        out = torch.empty((3, h, w), dtype=torch.float32, device=dev)
+        out = torch.empty((3, h, w) if turns == 0 else (3, w, h), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _hip.check(_hip.lib().nunif_hip_frame_to_tensor(_p(frame_hwc), _p(out), h, w, bits, _hip.current_stream_ptr(dev)))
+            _frame_to_tensor_call(frame_hwc, out, h, w, bits, turns, dev)
         return out
     assert frame_hwc.dim() == 3 and frame_hwc.shape[2] == 3
     if frame_hwc.dtype == torch.uint8:
@@ -183,9 +192,9 @@ def frame_to_tensor(frame_hwc, device=None):
     else:
         raise ValueError(f"unsupported frame dtype {frame_hwc.dtype}")
     h, w, _ = src.shape
-    out = torch.empty((3, h, w), dtype=torch.float32, device=src.device)
+    out = torch.empty((3, h, w) if turns == 0 else (3, w, h), dtype=torch.float32, device=src.device)
     with torch.cuda.device(src.device):
-        _hip.check(_hip.lib().nunif_hip_frame_to_tensor(_p(src), _p(out), h, w, bits, _hip.current_stream_ptr(src.device)))
+        _frame_to_tensor_call(src, out, h, w, bits, turns, src.device)
     return out
 
 

@@ -1,0 +1,147 @@
+"""The waifu2x video loop on the HIP engine: what ``waifu2x/ui_utils.py`` ``process_video``'s ``frame_callback`` (:154-177)
+does per frame, without its blocking copies and pointwise ATen chain.
+
+    numpy HWC frame --FrameRing (pinned, zero-copy)--> frame_to_tensor [+ quarter turn] --> ctx.convert -->
+    [film grain: noise, noise-buffer blend, apply] + quantise, ONE launch --> pinned HWC frame --> numpy
+
+``Waifu2xVideoStream`` is a ``frame -> frame | None`` callback as ``VU.process_video`` expects: the ring holds ``depth`` frames
+in flight, so the first calls return ``None`` and ``callback(None)`` at the end of the stream returns the frames still inside,
+in order (``nunif/utils/video.py:567-574`` ``get_new_frames`` accepts ``None``, one frame or a list).  It works on numpy frames;
+``av.VideoFrame`` objects are converted at the outermost edge only (``av_callback``), as ``iw3/frame_pipeline.py`` does.
+"""
+import numpy as np
+import torch
+
+from ..frame_ring import FrameRing
+from ..iw3 import _ops
+from ..iw3.frame_pipeline import pix_fmt_requires_16bit
+from ..nunif.utils import rgb_noise
+
+def _frame_pixels(frame):
+    if isinstance(frame, np.ndarray):
+        return frame
+    if hasattr(frame, "data") and not callable(frame.data):                 # frame_pipeline.HostFrame
+        return frame.data
+    if hasattr(frame, "format") and hasattr(frame.format, "components"):    # PyAV: nunif/utils/video.py:226-233
+        return frame.to_ndarray(format="rgb48le" if frame.format.components[0].bits > 8 else "rgb24")
+    return frame.to_ndarray()
+
+
+class Waifu2xVideoStream:
+    def __init__(self, ctx, args, device=None, depth=3, seed=None, use_16bit=None):
+        """``ctx``: a loaded ``Waifu2x`` context; ``args``: the reference's argparse namespace (``method``, ``noise_level``,
+        ``tile_size``, ``batch_size``, ``tta``, ``disable_amp``, ``rotate_left`` / ``rotate_right``, ``grain``,
+        ``grain_strength``, ``grain_speed``, ``pix_fmt``).  ``seed``: the grain seed; by default torch's
+        ``torch.initial_seed()`` at construction, so ``torch.manual_seed`` makes a run repeatable.  ``use_16bit``: the output
+        depth when the caller has already asked ``VU.pix_fmt_requires_16bit(args.pix_fmt)``; by default the engine's own copy of
+        that rule.  The depth of the frames going in is each frame's own (uint8 or uint16), as in ``VU.to_tensor``."""
+        self.ctx, self.args = ctx, args
+        self.device = torch.device(device if device is not None else ctx.device)
+        if self.device.type != "cuda":
+            raise RuntimeError("Waifu2xVideoStream needs a ROCm device; there is no CPU path")
+        self.depth = depth
+        if use_16bit is None:
+            use_16bit = pix_fmt_requires_16bit(getattr(args, "pix_fmt", None))
+        self.bits = 16 if use_16bit else 8
+        self.turns = 1 if getattr(args, "rotate_left", False) else 3 if getattr(args, "rotate_right", False) else 0
+        self.grain = bool(getattr(args, "grain", False))
+        self.grain_strength = float(getattr(args, "grain_strength", 0.2))
+        self.grain_speed = float(getattr(args, "grain_speed", 0.8))
+        self.seed = (torch.initial_seed() if seed is None else int(seed)) & ((1 << 64) - 1)
+        self.frame_counter = 0             # frames that have passed the leave step: the generator's counter
+        self.noise_buffer = None           # [3, Ho, Wo] fp32, lives on the ring's leave stream
+        self.frames_in = self.frames_out = 0
+        self._ring = None
+        self._in_shape = self._in_bits = None
+
+    # ---- geometry -------------------------------------------------------------------------------------------------------
+    def scale(self):
+        method = self.args.method
+        return 4 if method in ("scale4x", "noise_scale4x") else 1 if method == "noise" else 2
+
+    def output_shape(self, in_shape):
+        """(H, W, 3) of the frame that comes out for an (H, W, 3) frame going in."""
+        h, w = in_shape[:2]
+        if self.turns:
+            h, w = w, h
+        s = self.scale()
+        return (h * s, w * s, 3)
+
+    # ---- the three steps the ring runs ----------------------------------------------------------------------------------
+    def _enter(self, hwc, device=None):
+        return _ops.frame_to_tensor(hwc, device=device, turns=self.turns)
+
+    def _convert(self, rgb):
+        a = self.args
+        out, _ = self.ctx.convert(rgb, None, a.method, a.noise_level, a.tile_size, a.batch_size, a.tta,
+                                  enable_amp=not a.disable_amp, output_device=rgb.device)
+        return out
+
+    def _leave(self, y, bits, out=None):
+        if not self.grain:
+            return _ops.to_frame(y, bits, out=out)
+        y = y.to(torch.float32).contiguous()
+        if out is None:
+            out = torch.empty((y.shape[1], y.shape[2], 3), dtype=torch.uint8 if bits == 8 else torch.int16, device=y.device)
+        first = self.noise_buffer is None or self.noise_buffer.shape != y.shape          # ui_utils.py:169-171
+        if first:
+            self.noise_buffer = torch.empty_like(y)
+        rgb_noise.grain_video_step(y, self.noise_buffer, out, bits=bits, level=2, seed=self.seed, counter=self.frame_counter,
+                                   speed=self.grain_speed, first=first, strength=self.grain_strength)
+        self.frame_counter += 1
+        return out
+
+    # ---- the callback ---------------------------------------------------------------------------------------------------
+    def _open(self, in_shape, in_bits):
+        self._in_shape, self._in_bits = tuple(in_shape), in_bits
+        self._ring = FrameRing(self._convert, self._in_shape, self.output_shape(in_shape), device=self.device,
+                               depth=self.depth, bits=self.bits, in_bits=in_bits, enter_fn=self._enter, leave_fn=self._leave)
+
+    def drain(self):
+        outs = self._ring.drain() if self._ring is not None else []
+        self.frames_out += len(outs)
+        return outs
+
+    @torch.inference_mode()
+    def __call__(self, frame):
+        """One numpy HWC frame (uint8 or uint16, whatever the output depth is) in; ``None``, one frame or a list of frames out,
+        always in submission order.  ``None`` in: the end of the stream — returns what the ring still holds."""
+        if frame is None:
+            return self.drain() or None
+        frame = _frame_pixels(frame)
+        if frame.dtype not in (np.uint8, np.uint16):
+            raise ValueError(f"unsupported frame dtype {frame.dtype}")
+        in_bits = 16 if frame.dtype == np.uint16 else 8      # a 10-bit source keeps its depth whatever the output pixel format is
+        flushed = []
+        if self._ring is None or tuple(frame.shape) != self._in_shape or in_bits != self._in_bits:
+            flushed = self.drain()                      # a new frame size or depth: everything in flight leaves first
+            self._open(frame.shape, in_bits)
+        self.frames_in += 1
+        out = self._ring.submit(np.ascontiguousarray(frame))
+        if out is not None:
+            self.frames_out += 1
+            flushed.append(out)
+        if not flushed:
+            return None
+        return flushed[0] if len(flushed) == 1 else flushed
+
+    def av_callback(self, to_frame):
+        """The same callback for a PyAV loop: ``to_frame`` is the reference's ``VU.to_frame`` (numpy HWC -> ``av.VideoFrame``)."""
+        def callback(frame):
+            out = self(frame)
+            if out is None:
+                return None
+            if isinstance(out, list):
+                return [to_frame(o) for o in out]
+            return to_frame(out)
+        return callback
+
+    def test_callback(self, to_frame):
+        """``VU.process_video``'s size probe (``video.py:1006-1012``): a blank frame of the output size, without touching the
+        ring, the noise buffer or the frame counter."""
+        def callback(frame):
+            if frame is None:
+                return None
+            shape = self.output_shape(_frame_pixels(frame).shape)
+            return to_frame(np.zeros(shape, dtype=np.uint16 if self.bits == 16 else np.uint8))
+        return callback
