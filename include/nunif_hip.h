@@ -401,6 +401,27 @@ int nunif_hip_frame_to_tensor_rot(const void *frame, float *chw, int32_t H, int3
  * 6 shift_relative_depth(min_distance=p0, max_distance=p1). */
 int nunif_hip_map_depth(const float *x, float *y, int64_t n, int32_t kind, double p0, double p1, void *stream);
 
+/* TransNetV2 shot-boundary network (nunif/utils/transnetv2.py TransNetV2 :7-87 as `TransNetV2()` builds it: F=16, L=3, S=2,
+ * D=1024, frame similarity :220-259 and colour histograms :262-316 on, many-hot head on, no mean pooling), eval mode, fp32
+ * operands and accumulation (the reference runs it without autocast, nunif/utils/shot_boundary_detection.py:42).
+ * create() takes the weights already packed on the host (nunif_amd/nunif/utils/transnetv2.py pack_weights), BatchNorm3d folded:
+ *   b{0..2}.l{0,1}.ws  [ceil16(9*Cin)][8F']  the four branches' (1,3,3) kernels, row = (kh*3+kw)*Cin + c, column = branch*2F' + o
+ *   b{..}.l{..}.wt     [4][6F'][max(F',32)]  the (3,1,1) kernels x BN scale, row = tap*2F' + c, zero-padded columns
+ *   b{..}.l{..}.bias   [4F']                 BN shift
+ *   proj.wt [448][128], proj.b; sim.wt / hist.wt [101][128], sim.b / hist.b; fc1.wt [4864][1024], fc1.b; cls1.w / cls2.w [1024],
+ *   cls1.b / cls2.b [1]                      (Linear weights transposed to [in][out])
+ * `filters` is F of the constructor; only 16 is built (NUNIF_HIP_EUNSUPPORTED otherwise).
+ * forward: frames [B,T,3,27,48] f32 device, the values as the caller hands them in (the histogram branch takes int(v) >> 5 of
+ * them, as the reference does); one_hot, many_hot, sigmoid_out: [B,T] f32 device, logits of cls_layer1 / cls_layer2 and
+ * sigmoid(one_hot) (:45 of shot_boundary_detection.py); many_hot and sigmoid_out may be NULL.  Any T >= 1, B*T <= 4096.
+ * Scratch is owned by the handle: calls on one handle must be ordered (one stream at a time). */
+typedef struct nunif_transnetv2 nunif_transnetv2;
+int nunif_hip_transnetv2_create(const nunif_tensor_desc *tensors, int32_t n_tensors, int32_t filters,
+                                nunif_transnetv2 **handle);
+void nunif_hip_transnetv2_destroy(nunif_transnetv2 *handle);
+int nunif_hip_transnetv2_forward(nunif_transnetv2 *handle, const float *frames, int32_t B, int32_t T, float *one_hot,
+                                 float *many_hot, float *sigmoid_out, void *stream);
+
 /* Test hooks (tests/ only): snapshot every stage's NHWC fp16 output during the next forward calls, then read
  * them back one by one (returns 1 past the last tap).  Names match oracle.swin_unet.unet_forward(taps=...). */
 int nunif_hip_swin_unet_debug_taps(nunif_swin_unet *handle, int32_t enable);

@@ -128,7 +128,10 @@ SIGNATURES = {
                                              c_double, c_int32, c_double, c_double, c_int32, c_double, c_void_p]),
     "nunif_hip_frame_to_tensor_rot": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "nunif_hip_map_depth": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_double, c_double, c_void_p]),
-    "nunif_hip_swin_unet_debug_taps": (c_int32, [c_void_p, c_int32]),
+    "nunif_hip_transnetv2_create": (c_int32, [ctypes.POINTER(TensorDesc), c_int32, c_int32, ctypes.POINTER(c_void_p)]),
+    "nunif_hip_transnetv2_destroy": (None, [c_void_p]),
+    "nunif_hip_transnetv2_forward": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nunif_hip_swin_unet_debug_taps":(c_int32, [c_void_p, c_int32]),
     "nunif_hip_swin_unet_get_tap": (c_int32, [c_void_p, c_int32, c_char_p, c_int32, c_void_p, c_int64,
                                               ctypes.POINTER(c_int64)]),
     "nunif_hip_minmax": (c_int32, [c_void_p, c_void_p, c_int32, c_int64, c_void_p]),

@@ -64,6 +64,11 @@ PATCHES = [
     ("nunif.utils.rgb_noise", "rgb_noise_like"),
     ("nunif.utils.rgb_noise", "apply_rgb_noise"),
     ("waifu2x.ui_utils", "process_video"),
+    # shot boundary network (nunif/utils/transnetv2.py:7-93).  Patched in its defining module; the reference's
+    # nunif.utils.shot_boundary_detection (:2 `from .transnetv2 import TransNetV2`) and nunif/cli/split_video.py pick the engine's
+    # class up as consumers when they are loaded.  shot_boundary_detection itself is not a PATCHES entry: it imports PyAV, and
+    # install(strict=True) must not depend on that.
+    ("nunif.utils.transnetv2", "TransNetV2"),
 ]
 
 # reference packages whose modules may hold ``from ... import`` copies of a patched name

@@ -605,6 +605,42 @@ def video_depth_anything_state_dict(seed, grid=37, encoder="vits"):
     return sd
 
 
+def transnetv2_state_dict(seed, head_gain=0.5, head_bias=-5.5):
+    """Seeded TransNetV2 weights in the reference's key layout (``nunif/utils/transnetv2.py``).  The reference's default init
+    gives logits within +-0.03: useless for a threshold test.  Convolutions get He gain (activations stay O(1) through the
+    three blocks), BatchNorm gets non-trivial statistics (scale 0.6-1.4, shift, mean, variance 0.5-1.5) so that a wrong fold
+    shows, every bias is non-zero, and the two heads read the CENTRED fc1 features with ``head_gain``: fc1's ReLU output has a
+    large common mode over frames that would push every logit to one side; the heads' weights are made zero-sum against the
+    per-unit mean activation expected from He scaling, so that what is left is the frame-to-frame variation and the logits of a
+    clip with cuts fall on both sides of zero.  ``head_bias`` removes what remains of the common mode: with unit gain the
+    logits of the synthetic clips of tests/transnetv2_ref.py have a median near 11 and span -5 .. 24, so gain 0.5 and bias
+    -5.5 centre them (about -8 .. +6, a third to a half of the frames on each side)."""
+    from .nunif.utils.transnetv2 import state_dict_shapes
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for key, shape in state_dict_shapes().items():
+        if key.endswith("num_batches_tracked"):
+            sd[key] = torch.tensor(100, dtype=torch.long)
+        elif key.endswith("bn.weight"):
+            sd[key] = 0.6 + 0.8 * torch.rand(shape, generator=g)
+        elif key.endswith("bn.running_var"):
+            sd[key] = 0.5 + torch.rand(shape, generator=g)
+        elif key.endswith(("bn.bias", "bn.running_mean")):
+            sd[key] = 0.2 * torch.randn(shape, generator=g)
+        elif key.endswith(".bias"):
+            sd[key] = 0.05 * torch.randn(shape, generator=g)
+        else:
+            fan = 1
+            for s in shape[1:]:
+                fan *= s
+            sd[key] = torch.randn(shape, generator=g) * math.sqrt(2.0 / fan)
+    for head in ("cls_layer1", "cls_layer2"):
+        w = sd[head + ".weight"]
+        sd[head + ".weight"] = (w - w.mean()) * head_gain
+        sd[head + ".bias"] = sd[head + ".bias"] + head_bias
+    return sd
+
+
 def synth_depth(seed, b, h, w, kind="edges"):
     """Synthetic normalised depth maps: the step pattern of the reference's ``_bench`` (forward_warp.py:309-316)
     blurred, plus a ramp / smooth noise so that floor/ceil collisions, holes and layered holes all occur."""
