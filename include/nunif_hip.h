@@ -427,6 +427,14 @@ int nunif_hip_transnetv2_forward(nunif_transnetv2 *handle, const float *frames, 
 int nunif_hip_swin_unet_debug_taps(nunif_swin_unet *handle, int32_t enable);
 int nunif_hip_swin_unet_get_tap(nunif_swin_unet *handle, int32_t index, char *name, int32_t name_cap,
                                 void *host_dst, int64_t cap_bytes, int64_t *nbytes);
+/* The same for the cunet engine (CUNet / UpCUNet / vgg_7 / upconv_7): the map each launch wrote (NHWC fp16; "z1" planar fp32;
+ * "*.scale" the SE vectors [B][C] fp32), copied device-side right after the launch.  Taps never change which kernels run: the
+ * output with taps on equals the output with taps off.  Names match oracle.cunet.model_forward / conv_stack_forward(taps=...);
+ * a map that no launch writes in the current configuration (the 32-channel map inside the fused stem) has no tap.  Every forward
+ * with taps on starts from an empty store: the taps read back are those of the last forward (of a render: its last minibatch). */
+int nunif_hip_cunet_debug_taps(nunif_cunet *handle, int32_t enable);
+int nunif_hip_cunet_get_tap(nunif_cunet *handle, int32_t index, char *name, int32_t name_cap,
+                            void *host_dst, int64_t cap_bytes, int64_t *nbytes);
 
 /* Timing hooks for bench.py: per-kernel-class HIP-event accumulation on the launch stream. */
 int nunif_hip_profile_enable(int32_t on);

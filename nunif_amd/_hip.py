@@ -134,6 +134,9 @@ SIGNATURES = {
     "nunif_hip_swin_unet_debug_taps":(c_int32, [c_void_p, c_int32]),
     "nunif_hip_swin_unet_get_tap": (c_int32, [c_void_p, c_int32, c_char_p, c_int32, c_void_p, c_int64,
                                               ctypes.POINTER(c_int64)]),
+    "nunif_hip_cunet_debug_taps": (c_int32, [c_void_p, c_int32]),
+    "nunif_hip_cunet_get_tap": (c_int32, [c_void_p, c_int32, c_char_p, c_int32, c_void_p, c_int64,
+                                          ctypes.POINTER(c_int64)]),
     "nunif_hip_minmax": (c_int32, [c_void_p, c_void_p, c_int32, c_int64, c_void_p]),
     "nunif_hip_ema_scaler_push": (c_int32, [c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_double, c_void_p]),
     "nunif_hip_ema_scaler_ring_minmax": (c_int32, [c_void_p, c_int32, c_void_p]),

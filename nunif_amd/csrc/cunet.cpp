@@ -64,6 +64,12 @@ struct nunif_cunet {
     C3W u2c1a; ConvW u2c1b, u2down1, u2c2a, u2c2b, u2down2, u2c3a, u2c3b, u2c4a, u2c4b, u2c5, u2bottom;
     SEW u2se2, u2se3, u2se4; UpW u2up3, u2up4;
     Buf t[12], z1, sums, scale, tile_out;
+    // debug taps (tests only): when on, the map each launch wrote is copied device-side at once (the 12 buffers are reused down the
+    // net); the launches themselves are the ones that run with taps off
+    struct Tap { std::string name; void *dev; size_t bytes; };
+    bool taps_on = false;
+    std::vector<Tap> taps;
+    void clear_taps() { for (auto &t : taps) (void)hipFree(t.dev); taps.clear(); }
 };
 
 namespace {
@@ -249,6 +255,18 @@ int make_se(nunif_cunet *h, const TMap &m, const std::string &key, int C, SEW *s
     return NUNIF_HIP_OK;
 }
 
+int tap_copy(nunif_cunet *h, const char *name, const void *src, size_t bytes, hipStream_t s) {
+    void *p = nullptr;
+    NUNIF_HIP_CHECK(hipMalloc(&p, bytes));
+    h->taps.push_back({name, p, bytes});
+    NUNIF_HIP_CHECK(hipMemcpyAsync(p, src, bytes, hipMemcpyDeviceToDevice, s));
+    return NUNIF_HIP_OK;
+}
+
+// one branch per launch when taps are off
+#define CUNET_TAP(name, src, bytes) \
+    do { if (h->taps_on) { int trc_ = tap_copy(h, name, src, bytes, s); if (trc_) return trc_; } } while (0)
+
 int run_conv(const ConvW &c, const f16 *a, const f16 *a2, int H2, int crop2, int B, int Hi, f16 *out, float *out32,
              const float *add32, int addH, int add_crop, int clamp01, int act, hipStream_t s) {
     ConvArgs g;
@@ -305,9 +323,25 @@ int run_down(const ConvW &c, const f16 *a, int B, int Hi, f16 *out, hipStream_t 
 int run_up(const UpW &u, const f16 *a, int B, int Hi, f16 *out, hipStream_t s, const f16 *skip = nullptr, int skip_side = 0,
            int crop = 0, const float *in_scale = nullptr) {
     if (u.K == 64 && u.cq == 64 && skip) {
-        // 64 -> 4 x 64 with a cropped skip: the resident-weight prefetching kernel (cunet_up.hip), every launch of that shape
-        CunetUpArgs cu = {a, u.w, u.bias, skip, out, in_scale, B, Hi, skip_side, crop, 0.1f};
-        if (cunet_up_supported(cu)) return launch_cunet_up(cu, s);
+        // 64 -> 4 x 64 with a cropped skip: the resident-weight prefetching kernel (cunet_up.hip), every launch of that shape.  Its
+        // limits on the batch (the SE scale table of at most 128 images in LDS, 32-bit byte offsets into the skip and output maps)
+        // are met by running it over groups of images: which kernel runs must not depend on the tile minibatch
+        const long skip_img = (long)skip_side * skip_side * 64 * 2, out_img = 4L * Hi * Hi * 64 * 2;
+        const long fit = std::min<long>(((1L << 32) - 1) / std::max(skip_img, out_img), in_scale ? 128 : B);
+        const int nb = (int)std::max<long>(1, std::min<long>(B, fit));
+        CunetUpArgs cu = {a, u.w, u.bias, skip, out, in_scale, nb, Hi, skip_side, crop, 0.1f};
+        if (cunet_up_supported(cu)) {
+            for (int b0 = 0; b0 < B; b0 += nb) {
+                cu.B = std::min(nb, B - b0);
+                cu.a = a + (size_t)b0 * Hi * Hi * 64;
+                cu.res = skip + (size_t)b0 * skip_side * skip_side * 64;
+                cu.out = out + (size_t)b0 * 4 * Hi * Hi * 64;
+                cu.in_scale = in_scale ? in_scale + (size_t)b0 * 64 : nullptr;
+                int rc = launch_cunet_up(cu, s);
+                if (rc) return rc;
+            }
+            return NUNIF_HIP_OK;
+        }
     }
     GemmArgs g;
     memset(&g, 0, sizeof(g));
@@ -367,11 +401,13 @@ int forward_stack(nunif_cunet *h, const float *x, const float *frame, const nuni
     c3.B = B; c3.T = T; c3.w = h->st_first.w; c3.bias = h->st_first.b; c3.C = h->st_first.C; c3.out = cur; c3.slope = 0.1f;
     if ((rc = launch_c3_conv(c3, s))) return rc;
     int side = T - 2;
+    CUNET_TAP("net.0", cur, (size_t)B * side * side * h->st_first.C * sizeof(f16));      // (upconv_7: 16 channels padded to 32)
     const int n_mid = h->kind == 2 ? h->st_n - 1 : h->st_n;          // vgg_7: the last conv is the image head
     for (int i = 0; i < n_mid; ++i) {
         if ((rc = run_conv(h->st_conv[i], cur, nullptr, 0, 0, B, side, nxt, nullptr, nullptr, 0, 0, 0, 2, s))) return rc;
         std::swap(cur, nxt);
         side -= 2;
+        CUNET_TAP(("net." + std::to_string(2 * (i + 1))).c_str(), cur, (size_t)B * side * side * h->st_conv[i].N * sizeof(f16));
     }
     if (h->kind == 2)
         return run_conv(h->st_conv[h->st_n - 1], cur, nullptr, 0, 0, B, side, nullptr, z, nullptr, 0, 0, 1, 0, s);
@@ -381,6 +417,7 @@ int forward_stack(nunif_cunet *h, const float *x, const float *frame, const nuni
 // x: tile mode [B,3,T,T] or (frame != NULL) frame + grid; z: [B,3,T-56,T-56] (CUNet) / [B,3,2T-72,2T-72] (UpCUNet)
 int forward_impl(nunif_cunet *h, const float *x, const float *frame, const nunif_tile_grid *grid, int tile_begin,
                  float *z, int B, int T, hipStream_t s) {
+    if (h->taps_on) h->clear_taps();                // the taps are those of the LAST forward (of a render: of its last minibatch)
     if (h->kind >= 2) return forward_stack(h, x, frame, grid, tile_begin, z, B, T, s);
     NUNIF_REQUIRE(T % 4 == 0 && T >= 64, "tile_size %d is not valid for cunet (multiple of 4, >= 64)", T);
     const size_t b = B;
@@ -425,21 +462,31 @@ int forward_impl(nunif_cunet *h, const float *x, const float *frame, const nunif
         if ((rc = run_stem(c3, h->u1c1a, h->u1c1b, tX1, s))) return rc;                                                // x1
     } else {
         if ((rc = launch_c3_conv(c3, s))) return rc;
+        CUNET_TAP("unet1.conv1.0", tA, sz(a1, 32));
         if ((rc = run_conv(h->u1c1b, tA, nullptr, 0, 0, B, a1, tX1, nullptr, nullptr, 0, 0, 0, 2, s))) return rc;   // x1
     }
+    CUNET_TAP("unet1.x1", tX1, sz(x1, 64));
     if ((rc = run_down(h->u1down, tX1, B, x1, tD, s))) return rc;
+    CUNET_TAP("unet1.down", tD, sz(d1, 64));
     if ((rc = run_conv(h->u1c2a, tD, nullptr, 0, 0, B, d1, tE, nullptr, nullptr, 0, 0, 0, 2, s))) return rc;
+    CUNET_TAP("unet1.conv2.0", tE, sz(e1, 128));
     if ((rc = run_conv(h->u1c2b, tE, nullptr, 0, 0, B, e1, tF, nullptr, nullptr, 0, 0, 0, 2, s))) return rc;
+    CUNET_TAP("unet1.conv2", tF, sz(f1, 64));
     const bool sef = se_fuse_enabled();
     if ((rc = launch_se(tF, sums, scale, h->u1se2.w1, h->u1se2.b1, h->u1se2.w2, h->u1se2.b2, B, (long)f1 * f1, 64, s, sef))) return rc;
+    CUNET_TAP("unet1.se2.scale", scale, b * 64 * sizeof(float));
+    if (!sef) CUNET_TAP("unet1.x2", tF, sz(f1, 64));
     // conv3(crop(x1, 4) + x2): the add happens in the up-GEMM's epilogue
     if ((rc = run_up(h->u1up, tF, B, f1, tG, s, tX1, x1, 4, sef ? scale : nullptr))) return rc;
+    CUNET_TAP("unet1.up_add", tG, sz(g1, 64));
     if ((rc = run_conv(h->u1c3, tG, nullptr, 0, 0, B, g1, tH, nullptr, nullptr, 0, 0, 0, 2, s))) return rc;
+    CUNET_TAP("unet1.x3", tH, sz(h1, 64));
     // conv_bottom -> z1 (clamped unless no_clip, cunet.py:185-186)
     if (h->up) {
         if ((rc = run_deconv4(h->u1bottom_up, tH, B, h1, z1, h->no_clip ? 1 : 0, s))) return rc;
     } else if ((rc = run_conv(h->u1bottom, tH, nullptr, 0, 0, B, h1, nullptr, z1, nullptr, 0, 0, h->no_clip ? 0 : 1, 0, s)))
         return rc;
+    CUNET_TAP("z1", z1, b * 3 * T2 * T2 * sizeof(float));
 
     // ---------------- unet2 (cunet.py:99-121) ----------------
     memset(&c3, 0, sizeof(c3));
@@ -448,24 +495,43 @@ int forward_impl(nunif_cunet *h, const float *x, const float *frame, const nunif
         if ((rc = run_stem(c3, h->u2c1a, h->u2c1b, tY1, s))) return rc;                                                // x1
     } else {
         if ((rc = launch_c3_conv(c3, s))) return rc;
+        CUNET_TAP("unet2.conv1.0", tA, sz(a2, 32));
         if ((rc = run_conv(h->u2c1b, tA, nullptr, 0, 0, B, a2, tY1, nullptr, nullptr, 0, 0, 0, 2, s))) return rc;   // x1
     }
+    CUNET_TAP("unet2.x1", tY1, sz(y1, 64));
     if ((rc = run_down(h->u2down1, tY1, B, y1, tD, s))) return rc;
+    CUNET_TAP("unet2.down1", tD, sz(d2, 64));
     if ((rc = run_conv(h->u2c2a, tD, nullptr, 0, 0, B, d2, tE, nullptr, nullptr, 0, 0, 0, 2, s))) return rc;
+    CUNET_TAP("unet2.conv2.0", tE, sz(e2, 64));
     if ((rc = run_conv(h->u2c2b, tE, nullptr, 0, 0, B, e2, tX2, nullptr, nullptr, 0, 0, 0, 2, s))) return rc;       // x2
+    CUNET_TAP("unet2.conv2", tX2, sz(y2, 128));
     if ((rc = launch_se(tX2, sums, scale, h->u2se2.w1, h->u2se2.b1, h->u2se2.w2, h->u2se2.b2, B, (long)y2 * y2, 128, s))) return rc;
+    CUNET_TAP("unet2.se2.scale", scale, b * 128 * sizeof(float));
+    CUNET_TAP("unet2.x2", tX2, sz(y2, 128));
     if ((rc = run_down(h->u2down2, tX2, B, y2, tD, s))) return rc;
+    CUNET_TAP("unet2.down2", tD, sz(d3, 128));
     if ((rc = run_conv(h->u2c3a, tD, nullptr, 0, 0, B, d3, tE, nullptr, nullptr, 0, 0, 0, 2, s))) return rc;
+    CUNET_TAP("unet2.conv3.0", tE, sz(e3, 256));
     if ((rc = run_conv(h->u2c3b, tE, nullptr, 0, 0, B, e3, tF, nullptr, nullptr, 0, 0, 0, 2, s))) return rc;
+    CUNET_TAP("unet2.conv3", tF, sz(f3, 128));
     if ((rc = launch_se(tF, sums, scale, h->u2se3.w1, h->u2se3.b1, h->u2se3.w2, h->u2se3.b2, B, (long)f3 * f3, 128, s, sef))) return rc;
+    CUNET_TAP("unet2.se3.scale", scale, b * 128 * sizeof(float));
+    if (!sef) CUNET_TAP("unet2.x3", tF, sz(f3, 128));
     // conv4(crop(x2, 4) + x3)
     if ((rc = run_up(h->u2up3, tF, B, f3, tG, s, tX2, y2, 4, sef ? scale : nullptr))) return rc;
+    CUNET_TAP("unet2.up3_add", tG, sz(g3, 128));
     if ((rc = run_conv(h->u2c4a, tG, nullptr, 0, 0, B, g3, tE, nullptr, nullptr, 0, 0, 0, 2, s))) return rc;
+    CUNET_TAP("unet2.conv4.0", tE, sz(e4, 64));
     if ((rc = run_conv(h->u2c4b, tE, nullptr, 0, 0, B, e4, tF, nullptr, nullptr, 0, 0, 0, 2, s))) return rc;
+    CUNET_TAP("unet2.conv4", tF, sz(f4, 64));
     if ((rc = launch_se(tF, sums, scale, h->u2se4.w1, h->u2se4.b1, h->u2se4.w2, h->u2se4.b2, B, (long)f4 * f4, 64, s, sef))) return rc;
+    CUNET_TAP("unet2.se4.scale", scale, b * 64 * sizeof(float));
+    if (!sef) CUNET_TAP("unet2.x4", tF, sz(f4, 64));
     // conv5(crop(x1, 16) + x4)
     if ((rc = run_up(h->u2up4, tF, B, f4, tG, s, tY1, y1, 16, sef ? scale : nullptr))) return rc;
+    CUNET_TAP("unet2.up4_add", tG, sz(g4, 64));
     if ((rc = run_conv(h->u2c5, tG, nullptr, 0, 0, B, g4, tH, nullptr, nullptr, 0, 0, 0, 2, s))) return rc;
+    CUNET_TAP("unet2.x5", tH, sz(h5, 64));
     // z = clamp(crop(z1, 20) + conv_bottom(x5), 0, 1)
     if ((rc = run_conv(h->u2bottom, tH, nullptr, 0, 0, B, h5, nullptr, z, z1, T2, 20, 1, 0, s))) return rc;
     return NUNIF_HIP_OK;
@@ -544,8 +610,31 @@ extern "C" int nunif_hip_cunet_create(const nunif_tensor_desc *tensors, int32_t 
     return NUNIF_HIP_OK;
 }
 
+extern "C" int nunif_hip_cunet_debug_taps(nunif_cunet *h, int32_t enable) {
+    NUNIF_REQUIRE(h, "debug_taps: NULL handle");
+    h->clear_taps();
+    h->taps_on = enable != 0;
+    return NUNIF_HIP_OK;
+}
+
+extern "C" int nunif_hip_cunet_get_tap(nunif_cunet *h, int32_t index, char *name, int32_t name_cap, void *host_dst,
+                                       int64_t cap_bytes, int64_t *nbytes) {
+    NUNIF_REQUIRE(h && nbytes, "get_tap: NULL argument");
+    if (index < 0 || index >= (int)h->taps.size()) return 1;   // end of list
+    const auto &t = h->taps[index];
+    if (name && name_cap > 0) { strncpy(name, t.name.c_str(), name_cap - 1); name[name_cap - 1] = 0; }
+    *nbytes = (int64_t)t.bytes;
+    if (host_dst) {
+        NUNIF_REQUIRE(cap_bytes >= (int64_t)t.bytes, "get_tap: buffer too small");
+        NUNIF_HIP_CHECK(hipDeviceSynchronize());
+        NUNIF_HIP_CHECK(hipMemcpy(host_dst, t.dev, t.bytes, hipMemcpyDeviceToHost));
+    }
+    return NUNIF_HIP_OK;
+}
+
 extern "C" void nunif_hip_cunet_destroy(nunif_cunet *h) {
     if (!h) return;
+    h->clear_taps();
     for (void *p : h->owned) (void)hipFree(p);
     for (auto &b : h->t) b.release();
     h->z1.release(); h->sums.release(); h->scale.release(); h->tile_out.release();

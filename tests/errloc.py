@@ -1,4 +1,4 @@
-"""Localised error bounds for the swin nets: worst-REGION error against a float64 oracle (helper module, not a conftest).
+"""Localised error bounds for the swin and cunet nets: worst-REGION error against a float64 oracle (helper module, not a conftest).
 
 PSNR is a whole-image average: one 6 x 6 window of a 256 tile off by 0.1 (70x the fp16 noise floor) still reads 51 dB.  The
 kernels go wrong per window (lanes, masks, tables and index arithmetic are per window / per head / per edge row), so this module
@@ -11,12 +11,17 @@ and ``check_localised`` asserts, per image, (a) max|err| <= A * max|noise| and (
 (both the aligned and the half-cell-shifted partition, i.e. the windows of the plain and the shifted blocks)
 region_max(err) <= B * region_max(noise) + tau.  tau is a floor for regions where the clamp flattens the output to exact 0 / 1
 (there the emulation's error is 0).  Regions in the first / last row / column of an image are reported as bands of their own.
+
+The CUNet family (``waifu2x.cunet`` / ``upcunet`` / ``vgg_7`` / ``upconv_7``, oracle/cunet.py) goes wrong per 8 x 32 output patch of a
+conv workgroup, per 16 x 16 head tile, per 16-channel MFMA n-tile and per image (SE pooling, the scale table): its regions are the
+cells 8 / 16 / 32 / 64 of the level-1 map in output pixels (twice that for the 2x nets), with the same constants.
 """
 import math
 
 import torch
 import torch.nn.functional as F
 
+from oracle import cunet as OC
 from oracle import swin_unet as O
 from oracle import swin_unet_v2 as OV
 from oracle.fp16_emulation import fp16_autocast_emulation, half_weights
@@ -27,6 +32,10 @@ SCALE = {"waifu2x.swin_unet_1x": 1, "waifu2x.swin_unet_2x": 2, "waifu2x.swin_une
 # swin_unet_v2: window sizes of its levels (oracle/swin_unet_v2.py: wac1 8 / 6, wac2 8 at half resolution, wac3 8); the output
 # starts one level-1 token in (x[:, :, s:-s, s:-s] after the pixel shuffle)
 V2_WINDOWS = ((6, 1), (8, 1), (16, 2))          # (window in level-1 tokens, level)
+# the cunet engine's nets: name -> output pixels per level-1 pixel (a level-1 patch covers 2x pixels after the 4 x 4 stride-2 deconv)
+CUNET_SCALE = {"waifu2x.cunet": 1, "waifu2x.upcunet": 2, "waifu2x.vgg_7": 1, "waifu2x.upconv_7": 2}
+CUNET_OFFSET = {"waifu2x.cunet": 28, "waifu2x.upcunet": 36, "waifu2x.vgg_7": 7, "waifu2x.upconv_7": 14}
+CUNET_CELLS = (8, 16, 32, 64)                   # kTH = 8, the 16 x 16 head tile, kTW = 32, and two patches side by side
 
 # Thresholds: about twice the worst ratios measured on an MI355X over every case of tests/test_gpu_swin_errloc.py (its docstring)
 A_OUT, B_OUT, TAU_OUT = 2.5, 3.75, 5e-4          # clamped [0,1] outputs (worst 1.16 / 1.82); tau = one fp16 ulp in [0.5, 1)
@@ -34,28 +43,36 @@ A_TAP, B_TAP = 3.5, 5.5                          # NHWC debug taps per 6 x 6 win
 TAP_TAU_REL = 2e-3                               # tap tau = 2e-3 x the tap's rms
 
 
-def _forward(sd, x, name, taps=None):
+def _forward(sd, x, name, taps=None, no_clip=False):
+    if name in ("waifu2x.cunet", "waifu2x.upcunet"):
+        return OC.model_forward(sd, x, no_clip=no_clip, taps=taps)
+    if name in ("waifu2x.vgg_7", "waifu2x.upconv_7"):
+        return OC.conv_stack_forward(sd, x, taps=taps)
+    assert not no_clip, "no_clip is a cunet option"
     if name in V2_SCALE:
         assert taps is None, "swin_unet_v2 has no taps"
         return OV.model_forward(sd, x, V2_SCALE[name])
     return torch.clamp(O.unet_forward(sd, x, O.GEOMETRY.get(name, (0, 0, 0, SCALE[name]))[3], taps=taps), 0.0, 1.0)
 
 
-def oracle64(sd, x, name, taps=None):
+def oracle64(sd, x, name, taps=None, no_clip=False):
     """The oracle forward with the state dict and the input cast to float64 (float64 output, clamped like the wrapper)."""
     sd64 = {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
-    return _forward(sd64, x.double(), name, taps)
+    return _forward(sd64, x.double(), name, taps, no_clip)
 
 
-def emulated(sd, x, name, taps=None):
+def emulated(sd, x, name, taps=None, no_clip=False):
     """The reference's own GPU arithmetic: fp16 parameters, every op result rounded to fp16 (oracle/fp16_emulation.py)."""
     with fp16_autocast_emulation():
-        return _forward(half_weights(sd), x.float(), name, taps)
+        return _forward(half_weights(sd), x.float(), name, taps, no_clip)
 
 
 def cells_for(name, origin=0):
     """[(cell, offset)] of the windows of every level mapped to output pixels: the aligned partition of each level.
     ``origin``: the tile-output pixel the compared map starts at (a crop of the tile output)."""
+    if name in CUNET_SCALE:
+        s = CUNET_SCALE[name]
+        return [(c * s, (-origin) % (c * s)) for c in CUNET_CELLS]
     if name in V2_SCALE:
         s = V2_SCALE[name]
         return [(ws * s, (-s - origin) % (ws * s)) for ws, _ in V2_WINDOWS]
@@ -127,7 +144,8 @@ def localised_stats(y, y64, yemu, cells, B=1.0, tau=0.0, group=None):
                 out["bands"]["interior"] = max(out["bands"].get("interior", 0.0), float(ratio[:, :, 1:-1, 1:-1].max()))
             out["worst"] = max(out["worst"], float(flat.max()))
     out["regions"].sort(key=lambda d: -d["ratio"])
-    out["_err"], out["_group"] = err, group
+    out["_err"], out["_group"], out["_B"], out["_tau"] = err, group, B, tau
+    out["_gmax"], out["_nmax"], out["_finite"] = float(err.abs().max()), float(noise.abs().max()), bool(torch.isfinite(y).all())
     return out
 
 
@@ -140,20 +158,26 @@ def format_regions(st, n=5):
     return "\n".join(lines)
 
 
-def check_localised(y, y64, yemu, cells, A, B, tau, group=None, label=""):
-    """Assert the global bound (a) and the per-region bound (b); the message names the 5 worst regions and the band of each (c).
-    y / y64 / yemu: [B, C, H, W] (NHWC maps: pass them permuted).  Returns the stats (``localised_stats``)."""
-    assert y.shape == y64.shape == yemu.shape, (label, y.shape, y64.shape, yemu.shape)
-    assert bool(torch.isfinite(y).all()), f"{label}: non-finite values"
-    st = localised_stats(y, y64, yemu, cells, B, tau, group)
-    gmax = float((y.double() - y64.double()).abs().max())
-    nmax = float((yemu.double() - y64.double()).abs().max())
+def assert_localised(st, A, B, tau, label=""):
+    """The asserts of ``check_localised`` on stats that ``localised_stats`` computed with the same ``B`` and ``tau`` (for a caller
+    that prints the figures before it asserts)."""
+    assert (st["_B"], st["_tau"]) == (B, tau), f"{label}: stats computed with B {st['_B']}, tau {st['_tau']}, asserted with {B}, {tau}"
+    assert st["_finite"], f"{label}: non-finite values"
+    gmax, nmax = st["_gmax"], st["_nmax"]
     bands = " ".join(f"{k} {v:.2f}" for k, v in sorted(st["bands"].items()))
     msg = (f"{label}: max|err| {gmax:.3e} (noise {nmax:.3e}, A {A}), worst region ratio {st['worst']:.2f} (B {B}, tau {tau}); "
            f"bands: {bands}\n" + format_regions(st))
     assert gmax <= A * nmax, msg
     assert st["worst"] <= B, msg
     return st
+
+
+def check_localised(y, y64, yemu, cells, A, B, tau, group=None, label=""):
+    """Assert the global bound (a) and the per-region bound (b); the message names the 5 worst regions and the band of each (c).
+    y / y64 / yemu: [B, C, H, W] (NHWC maps: pass them permuted).  Returns the stats (``localised_stats``)."""
+    assert y.shape == y64.shape == yemu.shape, (label, y.shape, y64.shape, yemu.shape)
+    assert bool(torch.isfinite(y).all()), f"{label}: non-finite values"
+    return assert_localised(localised_stats(y, y64, yemu, cells, B, tau, group), A, B, tau, label)
 
 
 def summary(st):
@@ -176,12 +200,28 @@ def psnr_db(a, b):
     return 10.0 * math.log10(1.0 / (mse + 1.0e-6))
 
 
-def check_net(y, sd, x, name, origin=0, crop=None, label=""):
+def check_render_tile(out, sd, img, name, tile, ti, tj, no_clip=False, label=""):
+    """``check_net`` of tile (ti, tj) of a whole-frame render ``out`` [3, H s, W s] of ``img`` [3, H, W] by one of the cunet engine's
+    nets (no blending: a tile's output lands in the frame as it is, cut at the frame's edge).  The tile's input is cut from the
+    replicate-padded frame as the renderer cuts it (oracle/seam_blending.py create_config)."""
+    from oracle import seam_blending as OS
+    s, off = CUNET_SCALE[name], CUNET_OFFSET[name]
+    cfg = OS.create_config(img.shape[1], img.shape[2], s, off, tile, 0)
+    xp = F.pad(img[None], cfg["pad"], mode="replicate")[0]
+    i0, j0 = ti * cfg["input_tile_step"], tj * cfg["input_tile_step"]
+    o0, o1, to = ti * cfg["output_tile_step"], tj * cfg["output_tile_step"], tile * s - 2 * off
+    sub = out[:, o0:o0 + to, o1:o1 + to].cpu()
+    assert sub.numel() > 0, (ti, tj, out.shape)
+    return check_net(sub, sd, xp[:, i0:i0 + tile, j0:j0 + tile][None], name, crop=(0, sub.shape[1], 0, sub.shape[2]),
+                     label=label or f"{name} render tile ({ti},{tj})", no_clip=no_clip)
+
+
+def check_net(y, sd, x, name, origin=0, crop=None, label="", no_clip=False):
     """``check_localised`` of an engine output against the float64 oracle and the emulation of the same forward.  ``crop``: the
     (row0, row1, col0, col1) window of the tile output that ``y`` holds; ``origin`` = row0 = col0 of it."""
     with torch.inference_mode():
         set_threads()
-        y64, ye = oracle64(sd, x, name), emulated(sd, x, name)
+        y64, ye = oracle64(sd, x, name, no_clip=no_clip), emulated(sd, x, name, no_clip=no_clip)
     if crop is not None:
         r0, r1, c0, c1 = crop
         y64, ye = y64[..., r0:r1, c0:c1], ye[..., r0:r1, c0:c1]

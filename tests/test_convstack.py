@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import errloc as E
 from conftest import GOLDEN, psnr, sd_checksum
 from oracle import cunet as OC
 
@@ -33,17 +34,21 @@ def test_hip_conv_stack(hiplib, g, tag, seed, scale, offset):
     from nunif_amd.waifu2x.models import vgg_7  # noqa: F401
     m = create_model("waifu2x." + tag).eval()
     assert (m.i2i_scale, m.i2i_offset) == (scale, offset)
-    m.load_state_dict(OC.conv_stack_state_dict(seed, tag), strict=True)
+    sd = OC.conv_stack_state_dict(seed, tag)
+    m.load_state_dict(sd, strict=True)
     m = m.to("cuda:0")
     with torch.no_grad():
         z = m(g["x"].to("cuda:0"))
         assert z.shape == g[tag + "_z"].shape
         p = psnr(z.cpu(), g[tag + "_z"])
         assert p >= 50.0, (tag, p)
+        E.check_net(z.cpu(), sd, g["x"], "waifu2x." + tag)          # patch by patch against the float64 oracle (tests/errloc.py)
         y = tiled_render(g["frame"].to("cuda:0"), m, tile_size=64, batch_size=4)
         assert y.shape == g[tag + "_render"].shape
         p = psnr(y.cpu(), g[tag + "_render"])
         assert p >= 50.0, (tag, "render", p)
+        E.check_render_tile(y, sd, g["frame"], "waifu2x." + tag, 64, 0, 1)
+        E.check_render_tile(y, sd, g["frame"], "waifu2x." + tag, 64, 1, 2)       # the last tile, cut by the frame
     with pytest.raises(RuntimeError):
         m.load_state_dict({"net.0.weight": torch.zeros(1)}, strict=True)
     with pytest.raises(RuntimeError):

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import errloc as E
 from conftest import GOLDEN, psnr, sd_checksum, synth_image
 from oracle import cunet as OC
 from oracle import seam_blending as OS
@@ -58,14 +59,19 @@ def test_hip_forward_and_render(hiplib, g):
     y = m(g["x"].to("cuda:0")).cpu()
     assert y.shape == g["y"].shape and float(y.min()) >= 0 and float(y.max()) <= 1
     assert psnr(y, g["y"]) >= 50.0, psnr(y, g["y"])            # vs the reference's own output
+    E.check_net(y, sd, g["x"], "waifu2x.cunet")                # patch by patch against the float64 oracle (tests/errloc.py)
     y1 = m(g["x"][1:2].to("cuda:0")).cpu()
     assert torch.equal(y1, y[1:2]), "result depends on the minibatch (SE pooling must stay per tile)"
     out = tiled_render(g["img"], m, tile_size=96, batch_size=4)
     assert psnr(out.cpu(), g["render_t96_b4"]) >= 50.0
+    E.check_render_tile(out, sd, g["img"], "waifu2x.cunet", 96, 1, 1)
+    E.check_render_tile(out, sd, g["img"], "waifu2x.cunet", 96, 3, 4)      # the last tile: 30 x 10 pixels of it are inside the frame
     assert torch.equal(out, tiled_render(g["img"], m, tile_size=96, batch_size=9))
     m2 = CUNet(no_clip=True).eval()
     m2.load_state_dict(sd)
-    assert psnr(m2.to("cuda:0")(g["x"][:1].to("cuda:0")).cpu(), g["y_no_clip"]) >= 50.0
+    y2 = m2.to("cuda:0")(g["x"][:1].to("cuda:0")).cpu()
+    assert psnr(y2, g["y_no_clip"]) >= 50.0
+    E.check_net(y2, sd, g["x"][:1], "waifu2x.cunet", no_clip=True)
 
 
 @pytest.mark.gpu
@@ -80,16 +86,22 @@ def test_hip_upcunet_forward_and_render(hiplib, g):
     y = m(g["x"].to("cuda:0")).cpu()
     assert y.shape == g["up_y"].shape and float(y.min()) >= 0 and float(y.max()) <= 1
     assert psnr(y, g["up_y"]) >= 50.0, psnr(y, g["up_y"])      # vs the reference's own output
+    E.check_net(y, sd, g["x"], "waifu2x.upcunet", no_clip=True)
     mc = UpCUNet().eval()
     mc.load_state_dict(sd)
-    assert psnr(mc.to("cuda:0")(g["x"][:1].to("cuda:0")).cpu(), g["up_y_clip"]) >= 50.0
+    yc = mc.to("cuda:0")(g["x"][:1].to("cuda:0")).cpu()
+    assert psnr(yc, g["up_y_clip"]) >= 50.0
+    E.check_net(yc, sd, g["x"][:1], "waifu2x.upcunet")
     out = tiled_render(g["up_img"], m, tile_size=64, batch_size=5)
     assert out.shape == (3, 200, 260) and psnr(out.cpu(), g["up_render_t64_b5"]) >= 50.0
+    E.check_render_tile(out, sd, g["up_img"], "waifu2x.upcunet", 64, 1, 2, no_clip=True)
+    E.check_render_tile(out, sd, g["up_img"], "waifu2x.upcunet", 64, 3, 4, no_clip=True)      # the last tile, cut by the frame
     assert torch.equal(out, tiled_render(g["up_img"], m, tile_size=64, batch_size=12))
     # a 256 tile (the default): 2*256 - 72 = 440, interior vs the oracle
     x = synth_image(62, 3, 256, 256)[None]
     z = m(x.to("cuda:0")).cpu()
     assert z.shape == (1, 3, 440, 440) and psnr(z, OC.model_forward(sd, x, no_clip=True)) >= 50.0
+    E.check_net(z, sd, x, "waifu2x.upcunet", no_clip=True)
 
 
 @pytest.mark.gpu
@@ -109,6 +121,8 @@ def test_hip_config1_512_tile256(hiplib):
     xp = torch.nn.functional.pad(img[None], cfg["pad"], mode="replicate")[0]
     z = OC.model_forward(sd, xp[:, 200:456, 200:456][None])[0]        # tile (1,1) -> output [200:400)
     assert psnr(out[:, 200:400, 200:400].cpu(), z) >= 50.0
+    E.check_render_tile(out, sd, img, "waifu2x.cunet", 256, 1, 1)
+    E.check_render_tile(out, sd, img, "waifu2x.cunet", 256, 2, 2)      # the last tile: 112 x 112 pixels of it are inside the frame
     with pytest.raises(Exception):
         m(torch.rand(1, 3, 62, 62).to("cuda:0"))                     # not a multiple of 4
 
@@ -134,6 +148,8 @@ def test_hip_cunet_1080p_whole_frame_minibatch_equals_small_minibatches(hiplib):
     xp = torch.nn.functional.pad(img[None], cfg["pad"], mode="replicate")[0]
     z = OC.model_forward(sd, xp[:, 400:656, 800:1056][None])[0]        # tile (2,4) -> output [400:600) x [800:1000)
     assert psnr(out[:, 400:600, 800:1000].cpu(), z) >= 50.0
+    E.check_render_tile(out, sd, img, "waifu2x.cunet", 256, 2, 4)
+    E.check_render_tile(out, sd, img, "waifu2x.cunet", 256, 5, 9)      # the last tile of the 66-tile minibatch (80 x 120 inside the frame)
 
 
 @pytest.mark.gpu

@@ -145,6 +145,9 @@ def test_cunet_through_the_context(tmp_path, hiplib):
         rgb, _ = ctx.convert(x, None, "noise", 1, tile_size=96, batch_size=4)
     ref = OS.tiled_render(x, lambda mb: OC.model_forward(sd, mb), 1, 28, 0, 96, 4)
     assert rgb.shape == (3, 128, 128) and psnr(rgb, ref) >= 50.0
+    import errloc as E
+    for ti, tj in ((0, 0), (1, 2), (3, 3)):                     # 4 x 4 tiles of 40 x 40; the last one is cut to 8 x 8 by the frame
+        E.check_render_tile(rgb, sd, x, "waifu2x.cunet", 96, ti, tj)
 
 
 @pytest.mark.gpu
