@@ -164,6 +164,8 @@ typedef struct {
     int32_t fill;             /* 1 = method "forward_fill" (shift_fill inpaint), 0 = "forward" (clamp) */
     int32_t synthetic_view;   /* 0 both, 1 left, 2 right */
     int32_t width_base;       /* base_size = W if 1 else max(H,W) */
+    const float *convergence_dev;   /* optional [B] f32 device: a convergence per frame (iw3/utils.py:303-307, the output of the
+                                       convergence estimator) read by the kernel; NULL = the scalar `convergence` above */
 } nunif_forward_warp_params;
 
 /* Replaces iw3/forward_warp.py apply_divergence_forward_warp :246-256 -> depth_order_bilinear_forward_warp
@@ -296,7 +298,8 @@ int nunif_hip_delta_weight_warp(const float *c, const float *delta, const float 
  * resolution and bilinearly resized, as the reference does). */
 int nunif_hip_backward_warp(const float *c, const float *depth, float *left, float *right, int32_t B, int32_t C,
                             int32_t H, int32_t W, int32_t dh, int32_t dw, double divergence, double convergence,
-                            int32_t synthetic_view, void *stream);
+                            int32_t synthetic_view, void *stream, const float *convergence_dev);
+/* (convergence_dev: optional [B] f32 device, a convergence per frame as in nunif_forward_warp_params; NULL = the scalar) */
 
 /* F.interpolate(..., antialias=True) for planar fp32 maps: bilinear (bicubic=0) or bicubic a=-0.5 (bicubic=1),
  * with ATen's coordinate rules (align_corners changes only the scale when antialias is on — SURVEY.md App. C).
@@ -334,7 +337,9 @@ int nunif_hip_range_normalize(const float *x, float *y, const float *lohi, int64
 /* iw3/backward_warp.py make_input_tensor :33-64 with c = None for a whole batch: out [B,3,H,W] = depth | divergence plane |
  * convergence plane, with the screen-border taper of `border_pix` columns (0: none). */
 int nunif_hip_make_input_planes(const float *depth, float *out, int32_t B, int32_t H, int32_t W, double divergence_value,
-                                double convergence_value, int32_t border_pix, void *stream);
+                                double convergence_value, int32_t border_pix, void *stream, const float *convergence_dev);
+/* (convergence_dev: optional [B] f32 device, a convergence per frame; convergence_value then is -divergence_pix and the plane of
+ *  frame b holds fp32(convergence_value * convergence_dev[b] / 32), make_divergence_feature_value :24-29 with that frame's value) */
 
 /* torch.stack of n <= 16 equally sized device buffers into dst (one launch; the per-frame tensors of a batch). */
 int nunif_hip_stack(const void *const *srcs, int32_t n, int64_t bytes_each, void *dst, void *stream);
@@ -421,6 +426,36 @@ int nunif_hip_transnetv2_create(const nunif_tensor_desc *tensors, int32_t n_tens
 void nunif_hip_transnetv2_destroy(nunif_transnetv2 *handle);
 int nunif_hip_transnetv2_forward(nunif_transnetv2 *handle, const float *frames, int32_t B, int32_t T, float *one_hot,
                                  float *many_hot, float *sigmoid_out, void *stream);
+
+/* SOD v1 saliency estimator of iw3's auto convergence (--convergence-mode sod_v1): iw3/models/sod_v1.py SODV1 :9-56 =
+ * U2NETP(in_ch=6) of nunif/utils/u2netp.py :321-430 (RSU7 :44-116, RSU6 :119-182, RSU5 :185-238, RSU4 :241-284, RSU4F :287-318,
+ * REBNCONV :11-35 with BatchNorm folded as fuse() :20-26 does), eval mode, fp32 operands and accumulation, net size 192.
+ * create() takes the weights packed on the host (nunif_amd/iw3/models/sod_v1.py pack_weights), all fp32:
+ *   <stage>.<rebnconv>.w [Cout/8][Cin][9][8]  BN-folded 3x3 kernel, (co / 8, ci, kh*3+kw, co % 8);  <stage>.<rebnconv>.b [Cout]
+ *   side.w [6][64][9], side.b [6]             side1 .. side6;   outconv.w [6], outconv.b [1]
+ * net_size must be 192 (MaxPool2d(ceil_mode=True) is built for even maps only; NUNIF_HIP_EUNSUPPORTED otherwise).
+ * forward replaces SODV1.infer :49-56: rgb [B,3,H,W] and depth [B,1,h,w] f32 device, any H, W, h, w -> saliency [B,1,192,192]
+ *   (sigmoid, u2netp.py:430) and depth_scaled [B,1,192,192] (the bilinear resize of depth, :52).  workspace: caller-owned device
+ *   floats, nunif_hip_sod_v1_workspace_floats(B) of them, so that calls on different streams never share scratch.
+ * entry is forward's first launch alone (:51-54 + to_feature :31-35 + the cat :41): x6 [B,6,192,192].
+ * debug_taps (tests only) copies one of the maps hx1 .. hx6, hx1d (u2netp.py:368-404) of the forward that last ran on `workspace`
+ *   into out ([B,64,S,S] f32 device, shape4 receives the shape).
+ * depth_position replaces ConvergenceEstimator.depth_position_from_ratio (iw3/convergence_estimator.py:33-59): saliency and depth
+ *   [B][n] f32 -> out [B] f32, all on the device.  ema replaces the loop of __call__ :69-82: state = {ema, has_value} on the
+ *   device, bit i of reset_mask = reset_pts[i] (B <= 64). */
+typedef struct nunif_sod_v1 nunif_sod_v1;
+int nunif_hip_sod_v1_create(const nunif_tensor_desc *tensors, int32_t n_tensors, int32_t net_size, nunif_sod_v1 **handle);
+void nunif_hip_sod_v1_destroy(nunif_sod_v1 *handle);
+int64_t nunif_hip_sod_v1_workspace_floats(int32_t B);
+int nunif_hip_sod_v1_forward(nunif_sod_v1 *handle, const float *rgb, int32_t H, int32_t W, const float *depth, int32_t h,
+                             int32_t w, int32_t B, float *workspace, float *saliency, float *depth_scaled, void *stream);
+int nunif_hip_sod_v1_entry(const float *rgb, int32_t H, int32_t W, const float *depth, int32_t h, int32_t w, int32_t B,
+                           float *x6, float *depth_scaled, void *stream);
+int nunif_hip_sod_v1_debug_taps(nunif_sod_v1 *handle, const float *workspace, int32_t B, const char *name, float *out,
+                                int64_t capacity, int64_t *shape4, void *stream);
+int nunif_hip_sod_v1_depth_position(const float *saliency, const float *depth, int32_t B, int64_t n, double pos, float *out,
+                                    void *stream);
+int nunif_hip_sod_v1_ema(const float *z, float *out, int32_t B, float *state, double decay, uint64_t reset_mask, void *stream);
 
 /* Test hooks (tests/ only): snapshot every stage's NHWC fp16 output during the next forward calls, then read
  * them back one by one (returns 1 past the last tap).  Names match oracle.swin_unet.unet_forward(taps=...). */

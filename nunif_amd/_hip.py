@@ -41,7 +41,7 @@ class TensorDesc(ctypes.Structure):
 
 class ForwardWarpParams(ctypes.Structure):
     _fields_ = [("B", c_int32), ("H", c_int32), ("W", c_int32), ("divergence", c_double), ("convergence", c_double),
-                ("fill", c_int32), ("synthetic_view", c_int32), ("width_base", c_int32)]
+                ("fill", c_int32), ("synthetic_view", c_int32), ("width_base", c_int32), ("convergence_dev", c_void_p)]
 
 
 class ProfRecord(ctypes.Structure):
@@ -74,7 +74,7 @@ SIGNATURES = {
     "nunif_hip_forward_warp": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                          ctypes.POINTER(ForwardWarpParams), c_void_p]),
     "nunif_hip_backward_warp": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int32] * 6 +
-                                [c_double, c_double, c_int32, c_void_p]),
+                                [c_double, c_double, c_int32, c_void_p, c_void_p]),
     "nunif_hip_row_flow_create": (c_int32, [ctypes.POINTER(TensorDesc), c_int32, ctypes.POINTER(c_void_p)]),
     "nunif_hip_row_flow_destroy": (None, [c_void_p]),
     "nunif_hip_row_flow_delta": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
@@ -131,6 +131,17 @@ SIGNATURES = {
     "nunif_hip_transnetv2_create": (c_int32, [ctypes.POINTER(TensorDesc), c_int32, c_int32, ctypes.POINTER(c_void_p)]),
     "nunif_hip_transnetv2_destroy": (None, [c_void_p]),
     "nunif_hip_transnetv2_forward": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nunif_hip_sod_v1_create": (c_int32, [ctypes.POINTER(TensorDesc), c_int32, c_int32, ctypes.POINTER(c_void_p)]),
+    "nunif_hip_sod_v1_destroy": (None, [c_void_p]),
+    "nunif_hip_sod_v1_workspace_floats": (c_int64, [c_int32]),
+    "nunif_hip_sod_v1_forward": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p,
+                                           c_void_p, c_void_p, c_void_p]),
+    "nunif_hip_sod_v1_entry": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                         c_void_p]),
+    "nunif_hip_sod_v1_debug_taps": (c_int32, [c_void_p, c_void_p, c_int32, c_char_p, c_void_p, c_int64, ctypes.POINTER(c_int64),
+                                              c_void_p]),
+    "nunif_hip_sod_v1_depth_position": (c_int32, [c_void_p, c_void_p, c_int32, c_int64, c_double, c_void_p, c_void_p]),
+    "nunif_hip_sod_v1_ema": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_double, c_uint64, c_void_p]),
     "nunif_hip_swin_unet_debug_taps":(c_int32, [c_void_p, c_int32]),
     "nunif_hip_swin_unet_get_tap": (c_int32, [c_void_p, c_int32, c_char_p, c_int32, c_void_p, c_int64,
                                               ctypes.POINTER(c_int64)]),
@@ -141,7 +152,7 @@ SIGNATURES = {
     "nunif_hip_ema_scaler_push": (c_int32, [c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_double, c_void_p]),
     "nunif_hip_ema_scaler_ring_minmax": (c_int32, [c_void_p, c_int32, c_void_p]),
     "nunif_hip_range_normalize": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
-    "nunif_hip_make_input_planes": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_double, c_double, c_int32, c_void_p]),
+    "nunif_hip_make_input_planes": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_double, c_double, c_int32, c_void_p, c_void_p]),
     "nunif_hip_stack": (c_int32, [ctypes.POINTER(c_void_p), c_int32, c_int64, c_void_p, c_void_p]),
     "nunif_hip_profile_enable": (c_int32, [c_int32]),
     "nunif_hip_profile_read": (c_int32, [ctypes.POINTER(ProfRecord), c_int32, c_int32]),

@@ -445,13 +445,15 @@ __device__ __forceinline__ float linspace_at(float start, float end, int i, int 
     return i < n / 2 ? start + step * (float)i : end - step * (float)(n - 1 - i);
 }
 __global__ void __launch_bounds__(256) make_input_planes_kernel(const float *__restrict__ depth, float *__restrict__ out,
-                                                                int B, int H, int W, float dv, float cv, int border) {
+                                                                int B, int H, int W, float dv, float cv, int border,
+                                                                const float *__restrict__ conv, double cvd) {
     const long hw = (long)H * W;
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long)B * hw) return;
     const long b = i / hw, p = i - b * hw;
     const int x = (int)(p % W);
     float d = dv, c = cv;
+    if (conv) c = (float)((cvd * (double)conv[b]) / 32.0);      // per-frame convergence: make_divergence_feature_value with conv[b]
     if (border > 0) {
         // left strip first, then the right strip on the result (a narrow map's strips may overlap), like the reference's
         // two in-place slice multiplications
@@ -693,11 +695,11 @@ extern "C" int nunif_hip_range_normalize(const float *x, float *y, const float *
 
 extern "C" int nunif_hip_make_input_planes(const float *depth, float *out, int32_t B, int32_t H, int32_t W,
                                            double divergence_value, double convergence_value, int32_t border_pix,
-                                           void *stream) {
+                                           void *stream, const float *convergence_dev) {
     NUNIF_REQUIRE(depth && out && B > 0 && H > 0 && W > 0 && border_pix >= 0, "make_input_planes: bad argument");
     const long n = (long)B * H * W;
     make_input_planes_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(
-        depth, out, B, H, W, (float)divergence_value, (float)convergence_value, border_pix);
+        depth, out, B, H, W, (float)divergence_value, (float)convergence_value, border_pix, convergence_dev, convergence_value);
     NUNIF_LAUNCH_CHECK();
     return NUNIF_HIP_OK;
 }

@@ -31,6 +31,8 @@ struct FwdWarpArgs {
     int B, H, W, pad, fill;
     float shift_size;      // fp32(divergence*0.01*base*0.5)
     float shift_conv;      // fp32(shift_size*convergence) computed in double on the host
+    const float *conv;     // optional [B] per-frame convergence on the device (CT kernels): shift_conv = fp32(shift_d * conv[b])
+    double shift_d;
 };
 
 __device__ __forceinline__ unsigned int order_key(float v) {
@@ -69,8 +71,10 @@ constexpr int kWarpThreads = 1024;
 // (<= 64 VGPRs and <= 80 SGPRs keep two rows = 8 waves per SIMD resident.  The compiler reports "Occupancy: 8" up to 96 SGPRs, the
 //  hardware does not deliver it: the same code at 86 SGPRs measured 103-109 us against 70, profiles/r05ag_fw_pairs.txt; round 4 saw
 //  the same at 102)
-template <bool DIET, int PI>
-__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80))) forward_warp_kernel(FwdWarpArgs a) {
+// CT: the convergence is a per-frame device value (--convergence-mode sod_v1, iw3/utils.py:303-307); the same double product and
+// rounding as the host's, so frame b equals the scalar call with float(conv[b]) bit for bit.  The scalar kernels are unchanged.
+template <bool DIET, int PI, bool CT>
+__device__ __forceinline__ void forward_warp_body(const FwdWarpArgs &a) {
     constexpr int kPairIters = PI;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int W = a.W, pad = a.pad, Wp = W + 2 * pad;
@@ -83,6 +87,8 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80))) for
     float *cws = idx2;                                                       // [Wp] ceil weight of source column xs (DIET)
     const int row = blockIdx.x;                  // b*H + y
     const int b = row / a.H, y = row - b * a.H;
+    float shift_conv = a.shift_conv;
+    if constexpr (CT) shift_conv = (float)(a.shift_d * (double)a.conv[b]);
     const float *drow = a.depth + (long)row * W;
     const float *crow = a.c + ((long)b * 3 * a.H + y) * W;
     const long cplane = (long)a.H * W;
@@ -98,7 +104,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80))) for
         for (int xs = tid; xs < Wp; xs += kWarpThreads) {
             const float d = dl[min(max(xs - pad, 0), W - 1)];
             int fl, ce; float fw, cw;
-            bilinear_target(d, sgn, a.shift_size, a.shift_conv, xs, Wp, fl, ce, fw, cw);
+            bilinear_target(d, sgn, a.shift_size, shift_conv, xs, Wp, fl, ce, fw, cw);
             const unsigned long long key = ((unsigned long long)order_key(d) << 32) | (unsigned int)(xs + 1);
             atomicMax(&kf[fl], key);
             atomicMax(&kc[ce], key);
@@ -117,7 +123,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80))) for
                     fwt = 1.0f - cws[sf];                               // bilinear_target: fw = 1.0f - cw
                 } else {
                     int fl, ce; float fw, cw;
-                    bilinear_target(dl[sx], sgn, a.shift_size, a.shift_conv, sf, Wp, fl, ce, fw, cw);
+                    bilinear_target(dl[sx], sgn, a.shift_size, shift_conv, sf, Wp, fl, ce, fw, cw);
                     fwt = fw;
                 }
                 fv[0] = crow[sx]; fv[1] = crow[cplane + sx]; fv[2] = crow[2 * cplane + sx]; fv[3] = (float)sf;
@@ -128,7 +134,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80))) for
                     cwt = cws[sc];
                 } else {
                     int fl, ce; float fw, cw;
-                    bilinear_target(dl[sx], sgn, a.shift_size, a.shift_conv, sc, Wp, fl, ce, fw, cw);
+                    bilinear_target(dl[sx], sgn, a.shift_size, shift_conv, sc, Wp, fl, ce, fw, cw);
                     cwt = cw;
                 }
                 cv[0] = crow[sx]; cv[1] = crow[cplane + sx]; cv[2] = crow[2 * cplane + sx]; cv[3] = (float)sc;
@@ -288,6 +294,16 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80))) for
     }
 }
 
+template <bool DIET, int PI>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80))) forward_warp_kernel(FwdWarpArgs a) {
+    forward_warp_body<DIET, PI, false>(a);
+}
+// the same rows with a convergence per frame read on the device
+template <int PI>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(80))) forward_warp_per_frame_kernel(FwdWarpArgs a) {
+    forward_warp_body<true, PI, true>(a);
+}
+
 // ---- backward warp: grid_sample(bilinear, border, align_corners=True) of a horizontally displaced identity grid -----
 struct BwdWarpArgs {
     const float *c;        // [B,C,H,W]
@@ -296,6 +312,8 @@ struct BwdWarpArgs {
     int B, C, H, W, h, w;
     float shift_size;      // fp32(divergence*0.01)
     float shift_conv;      // fp32(shift_size*convergence)
+    const float *conv;     // optional [B] per-frame convergence on the device: shift_conv = fp32(shift_d * conv[b])
+    double shift_d;
     float delta_scale;     // fp32(max(h,w)/w)
 };
 
@@ -316,12 +334,13 @@ __global__ void __launch_bounds__(256) backward_warp_kernel(BwdWarpArgs a) {
     const int b = (int)(t / a.H);
     const bool same = (a.h == a.H && a.w == a.W);
     const float *dmap = a.depth + (long)b * a.h * a.w;
+    const float shift_conv = a.conv ? (float)(a.shift_d * (double)a.conv[b]) : a.shift_conv;
     for (int eye = 0; eye < 2; ++eye) {
         if (!a.out[eye]) continue;
         const float sgn = eye == 0 ? -1.0f : 1.0f;      // left = backward_warp(c, grid, -delta)
         // grid value at a (y, x) node of the depth-resolution grid: linspace + delta*delta_scale (backward_warp.py:68)
         auto gx_at = [&](int yy, int xx) -> float {
-            const float sh = dmap[(long)yy * a.w + xx] * a.shift_size - a.shift_conv;
+            const float sh = dmap[(long)yy * a.w + xx] * a.shift_size - shift_conv;
             return linspace_pm1(xx, a.w) + (sgn * sh) * a.delta_scale;
         };
         float gx, gy;
@@ -385,6 +404,8 @@ extern "C" int nunif_hip_forward_warp(const float *c, const float *depth, float 
     a.B = p->B; a.H = p->H; a.W = p->W; a.pad = pad; a.fill = p->fill;
     a.shift_size = (float)shift_size;
     a.shift_conv = (float)(shift_size * p->convergence);
+    a.conv = p->convergence_dev;
+    a.shift_d = shift_size;
     const long Wp = (long)p->W + 2 * pad;
     const size_t smem = (size_t)Wp * 16 + (size_t)p->W * 5 * sizeof(float) + (size_t)Wp * sizeof(float);
     NUNIF_REQUIRE(smem <= 160 * 1024, "forward_warp: row of %d (+2*%d pad) does not fit LDS", p->W, pad);
@@ -397,6 +418,10 @@ extern "C" int nunif_hip_forward_warp(const float *c, const float *depth, float 
                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         NUNIF_HIP_CHECK(hipFuncSetAttribute((const void *)forward_warp_kernel<false, 1>,
                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        NUNIF_HIP_CHECK(hipFuncSetAttribute((const void *)forward_warp_per_frame_kernel<1>,
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        NUNIF_HIP_CHECK(hipFuncSetAttribute((const void *)forward_warp_per_frame_kernel<2>,
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set = true;
     }
     const double px = (double)p->B * p->H * p->W;
@@ -404,7 +429,9 @@ extern "C" int nunif_hip_forward_warp(const float *c, const float *depth, float 
     ProfScope ps("forward_warp", s, 0.0, px * (16.0 + 12.0 * eyes));
     // NUNIF_FW_DIET=0: round 4's instruction stream (A/B runs; the results are the same bits)
     static const bool diet = !(getenv("NUNIF_FW_DIET") && atoi(getenv("NUNIF_FW_DIET")) == 0);
-    if (diet && p->W <= 2 * kWarpThreads) forward_warp_kernel<true, 1><<<p->B * p->H, kWarpThreads, smem, s>>>(a);
+    if (a.conv && p->W <= 2 * kWarpThreads) forward_warp_per_frame_kernel<1><<<p->B * p->H, kWarpThreads, smem, s>>>(a);
+    else if (a.conv) forward_warp_per_frame_kernel<2><<<p->B * p->H, kWarpThreads, smem, s>>>(a);
+    else if (diet && p->W <= 2 * kWarpThreads) forward_warp_kernel<true, 1><<<p->B * p->H, kWarpThreads, smem, s>>>(a);
     else if (diet) forward_warp_kernel<true, 2><<<p->B * p->H, kWarpThreads, smem, s>>>(a);
     else forward_warp_kernel<false, 1><<<p->B * p->H, kWarpThreads, smem, s>>>(a);
     NUNIF_LAUNCH_CHECK();
@@ -413,7 +440,8 @@ extern "C" int nunif_hip_forward_warp(const float *c, const float *depth, float 
 
 extern "C" int nunif_hip_backward_warp(const float *c, const float *depth, float *left, float *right, int32_t B,
                                        int32_t C, int32_t H, int32_t W, int32_t dh, int32_t dw, double divergence,
-                                       double convergence, int32_t synthetic_view, void *stream) {
+                                       double convergence, int32_t synthetic_view, void *stream,
+                                       const float *convergence_dev) {
     NUNIF_REQUIRE(c && depth && B > 0 && C > 0 && H > 0 && W > 0 && dh > 0 && dw > 0, "backward_warp: bad argument");
     NUNIF_REQUIRE(synthetic_view >= 0 && synthetic_view <= 2, "backward_warp: synthetic_view must be 0/1/2");
     double div = divergence;
@@ -427,6 +455,8 @@ extern "C" int nunif_hip_backward_warp(const float *c, const float *depth, float
     a.B = B; a.C = C; a.H = H; a.W = W; a.h = dh; a.w = dw;
     a.shift_size = (float)shift_size;
     a.shift_conv = (float)(shift_size * convergence);
+    a.conv = convergence_dev;
+    a.shift_d = shift_size;
     a.delta_scale = (float)((double)(dh > dw ? dh : dw) / (double)dw);
     hipStream_t s = (hipStream_t)stream;
     const long total = (long)B * H * W;

@@ -69,6 +69,9 @@ PATCHES = [
     # class up as consumers when they are loaded.  shot_boundary_detection itself is not a PATCHES entry: it imports PyAV, and
     # install(strict=True) must not depend on that.
     ("nunif.utils.transnetv2", "TransNetV2"),
+    # --convergence-mode sod_v1 (iw3/convergence_estimator.py:11-84); iw3/utils.py:44 binds the class by name and picks the engine's
+    # up as a consumer.  The net it loads (iw3.sod_v1 / iw3.dsod_v1) comes through the model registry below.
+    ("iw3.convergence_estimator", "ConvergenceEstimator"),
 ]
 
 # reference packages whose modules may hold ``from ... import`` copies of a patched name

@@ -89,15 +89,30 @@ def range_normalize(x, lohi, max_mode=False):
     return y
 
 
-def make_input_planes(depth, divergence_value, convergence_value, border_pix=0):
-    """[B,1,H,W] depth -> [B,3,H,W] = depth | divergence plane | convergence plane (+ screen-border taper)."""
+def _convergence_dev(convergence, b, device):
+    """A per-frame convergence tensor ([B,1,1,1], [B] or one element) as B contiguous fp32 values on ``device``; None for a
+    scalar.  No host read: the kernels take the pointer."""
+    if not torch.is_tensor(convergence):
+        return None
+    t = convergence.detach().to(device=device, dtype=torch.float32).reshape(-1)
+    if t.numel() == 1 and b != 1:
+        t = t.expand(b)
+    if t.numel() != b:
+        raise ValueError(f"convergence tensor has {t.numel()} values for a batch of {b}")
+    return t.contiguous()
+
+
+def make_input_planes(depth, divergence_value, convergence_value, border_pix=0, convergence_dev=None):
+    """[B,1,H,W] depth -> [B,3,H,W] = depth | divergence plane | convergence plane (+ screen-border taper).  With
+    ``convergence_dev`` ([B] per-frame values on the device) ``convergence_value`` is ``-divergence_pix``."""
     depth = _cuda_f32(depth, "make_input_planes")
     b, _, h, w = depth.shape
+    convergence_dev = _convergence_dev(convergence_dev, b, depth.device)
     out = torch.empty((b, 3, h, w), dtype=torch.float32, device=depth.device)
     with torch.cuda.device(depth.device):
         _hip.check(_hip.lib().nunif_hip_make_input_planes(_p(depth), _p(out), b, h, w, float(divergence_value),
                                                           float(convergence_value), int(border_pix),
-                                                          _hip.current_stream_ptr(depth.device)))
+                                                          _hip.current_stream_ptr(depth.device), _p(convergence_dev)))
     return out
 
 
@@ -136,8 +151,9 @@ def forward_warp(c, depth, divergence, convergence, fill, synthetic_view, return
     right = torch.empty_like(c) if view != 1 else None
     lm = torch.empty((b, 1, h, w), dtype=torch.float32, device=c.device) if (return_mask and view != 2) else None
     rm = torch.empty((b, 1, h, w), dtype=torch.float32, device=c.device) if (return_mask and view != 1) else None
-    p = _hip.ForwardWarpParams(b, h, w, float(divergence), float(convergence), 1 if fill else 0, view,
-                               1 if width_base else 0)
+    conv_dev = _convergence_dev(convergence, b, c.device)
+    p = _hip.ForwardWarpParams(b, h, w, float(divergence), 0.0 if conv_dev is not None else float(convergence),
+                               1 if fill else 0, view, 1 if width_base else 0, _p(conv_dev))
     with torch.cuda.device(c.device):
         _hip.check(_hip.lib().nunif_hip_forward_warp(_p(c), _p(depth), _p(left), _p(right), _p(lm), _p(rm),
                                                      ctypes.byref(p), _hip.current_stream_ptr(c.device)))
@@ -152,10 +168,11 @@ def backward_warp(c, depth, divergence, convergence, synthetic_view):
     view = VIEW[synthetic_view]
     left = torch.empty_like(c) if view != 2 else None
     right = torch.empty_like(c) if view != 1 else None
+    conv_dev = _convergence_dev(convergence, b, c.device)
     with torch.cuda.device(c.device):
         _hip.check(_hip.lib().nunif_hip_backward_warp(_p(c), _p(depth), _p(left), _p(right), b, ch, h, w, dh, dw,
-                                                      float(divergence), float(convergence), view,
-                                                      _hip.current_stream_ptr(c.device)))
+                                                      float(divergence), 0.0 if conv_dev is not None else float(convergence),
+                                                      view, _hip.current_stream_ptr(c.device), _p(conv_dev)))
     return left, right
 
 

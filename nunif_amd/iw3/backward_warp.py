@@ -92,6 +92,13 @@ def make_input_batch(depth, divergence, convergence, image_width, preserve_scree
         if preserve_screen_border:
             border_pix = max(round(divergence * 0.75 * 0.01 * image_width * (depth.shape[-1] / image_width)), 0)
         return _ops.make_input_planes(depth, dv, cv, border_pix)
+    if depth.is_cuda and torch.is_tensor(convergence):
+        # a convergence per frame (the convergence estimator's output): the same launch reads conv[b] on the device
+        dv, _ = make_divergence_feature_value(divergence, 0.0, image_width)
+        border_pix = 0
+        if preserve_screen_border:
+            border_pix = max(round(divergence * 0.75 * 0.01 * image_width * (depth.shape[-1] / image_width)), 0)
+        return _ops.make_input_planes(depth, dv, -(divergence * 0.5 * 0.01 * image_width), border_pix, convergence_dev=convergence)
     conv = convergence.flatten() if torch.is_tensor(convergence) else (
         list(convergence) if isinstance(convergence, (list, tuple)) else [convergence] * B)
     return torch.stack([make_input_tensor(None, depth[i], divergence=divergence, convergence=conv[i], image_width=image_width,
@@ -211,8 +218,11 @@ def apply_divergence_nn_symmetric(model, c, depth, divergence, convergence, synt
         convergence = convergence.flatten()
     else:
         convergence = [convergence] * B
-    x = torch.stack([make_input_tensor(None, depth[i], divergence=divergence, convergence=convergence[i], image_width=W)
-                     for i in range(B)])
+    if torch.is_tensor(convergence) and depth.is_cuda:
+        x = make_input_batch(depth, divergence, convergence, W)          # per-frame values: conv[b] is read on the device
+    else:
+        x = torch.stack([make_input_tensor(None, depth[i], divergence=divergence, convergence=convergence[i], image_width=W)
+                         for i in range(B)])
     delta = model.infer_delta(x, flip=False)
     delta_scale = 1.0 / (W // 2 - 1)
     left_eye = _ops.delta_warp(c, delta, delta_scale, flip=False).to(c.dtype) if synthetic_view != "right" else c

@@ -41,13 +41,15 @@ def apply_divergence(depth, im, args, side_model, reset_pts=None):
     if not batch:
         depth, im = depth.unsqueeze(0), im.unsqueeze(0)
     state = getattr(args, "state", None)
-    if isinstance(state, dict) and state.get("convergence_model") is not None:
-        # iw3/utils.py:303-307: --convergence auto feeds a per-frame convergence TENSOR (ConvergenceEstimator on a U2NETP
-        # saliency net) through the mapper into every warp; the warp kernels here take a scalar.  Refuse instead of
-        # silently using args.convergence (same policy as --autocrop).
-        raise NotImplementedError("--convergence auto (args.state['convergence_model']) is not supported by the HIP engine")
-    depth = get_mapper(args.mapper)(depth)
-    convergence = args.convergence
+    convergence_model = state.get("convergence_model") if isinstance(state, dict) else None
+    mapper_fn = get_mapper(args.mapper)
+    if convergence_model is not None:
+        # iw3/utils.py:303-307 (--convergence-mode sod_v1): one convergence per frame, [B,1,1,1] on the device, through the same
+        # mapper as the depth; every method below reads convergence[b] on the device (no host read in the batch loop)
+        convergence = mapper_fn(convergence_model(im, depth, reset_pts=reset_pts))
+    else:
+        convergence = args.convergence
+    depth = mapper_fn(depth)
     if args.method == "NULL":
         left, right = im.clone(), im.clone()
     elif args.method in {"grid_sample", "backward"}:

@@ -661,3 +661,34 @@ def synth_depth(seed, b, h, w, kind="edges"):
         if kind == "smooth_edges":
             d = F.avg_pool2d(F.pad(d, (2, 2, 2, 2), mode="replicate"), 5, stride=1)
     return torch.clamp(d, 0, 1)
+
+
+def sod_v1_state_dict(seed, out_gain=0.04, out_bias=0.0):
+    """Seeded ``iw3.sod_v1`` weights in the reference's key layout (``iw3/models/sod_v1.py`` over ``nunif/utils/u2netp.py``).
+    Convolutions get He gain so that activations stay O(1) through the ~20 convolutions in series, BatchNorm gets non-trivial
+    statistics (scale 0.6-1.4, shift, mean, variance 0.5-1.5) so that a wrong fold shows, every bias is non-zero.  The six side
+    logits of such a net are strongly correlated and sit on one side of zero; ``outconv`` takes them with alternating signs
+    times ``out_gain`` (with unit gain the logits of the test scenes have a standard deviation near 120) so that the final logits spread over both sides of 0 and few pixels
+    sit near saliency 0.5 (tests/test_sod_v1_cpu.py checks that on the recorded output); ``out_bias`` shifts them (a strongly
+    negative one gives the empty mask)."""
+    from .iw3.models.sod_v1 import state_dict_shapes
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for key, shape in state_dict_shapes().items():
+        if key.endswith("num_batches_tracked"):
+            sd[key] = torch.tensor(100, dtype=torch.long)
+        elif key.endswith("bn_s1.weight"):
+            sd[key] = 0.6 + 0.8 * torch.rand(shape, generator=g)
+        elif key.endswith("running_var"):
+            sd[key] = 0.5 + torch.rand(shape, generator=g)
+        elif key.endswith(("bn_s1.bias", "running_mean")):
+            sd[key] = 0.2 * torch.randn(shape, generator=g)
+        elif key.endswith(".bias"):
+            sd[key] = 0.05 * torch.randn(shape, generator=g)
+        else:
+            fan = shape[1] * shape[2] * shape[3]
+            sd[key] = torch.randn(shape, generator=g) * math.sqrt(2.0 / fan)
+    sign = torch.tensor([1.0, -1.0, 1.0, -1.0, 1.0, -1.0])
+    sd["u2netp.outconv.weight"] = (out_gain * sign * (0.75 + 0.5 * torch.rand(6, generator=g))).reshape(1, 6, 1, 1)
+    sd["u2netp.outconv.bias"] = torch.tensor([float(out_bias)])
+    return sd
