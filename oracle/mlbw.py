@@ -58,11 +58,12 @@ def delta_forward(sd, x, num_layers):
     x = RF.pixel_shuffle_w(x, 8)
     x = F.conv2d(F.pad(x + x1, (4, 4, 0, 0), mode="replicate"), sd["lv1_out.1.weight"], sd["lv1_out.1.bias"])
     x = x[:, :, ph1:x.shape[2] - ph2, pw1:x.shape[3] - pw2]
+    f32 = (lambda t: t) if x.dtype == torch.float64 else (lambda t: t.float())     # (a float64 run stays in float64)
     if x.shape[1] == 2 * num_layers + 1:                              # hole_mask=True (mlbw.py:104-106)
         delta, weight = x[:, :2 * num_layers].chunk(2, dim=1)
-        return delta, F.softmax(weight.float(), dim=1), x[:, 2 * num_layers:].float()
+        return delta, F.softmax(f32(weight), dim=1), f32(x[:, 2 * num_layers:])
     delta, weight = x.chunk(2, dim=1)
-    return delta, F.softmax(weight.float(), dim=1)
+    return delta, F.softmax(f32(weight), dim=1)
 
 
 # ---- hole mask ---------------------------------------------------------------------------------------------------------

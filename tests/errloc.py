@@ -1,4 +1,4 @@
-"""Localised error bounds for the swin and cunet nets: worst-REGION error against a float64 oracle (helper module, not a conftest).
+"""Localised error bounds for the swin and cunet nets and the iw3 side nets: worst-REGION error against a float64 oracle (helper module, not a conftest).
 
 PSNR is a whole-image average: one 6 x 6 window of a 256 tile off by 0.1 (70x the fp16 noise floor) still reads 51 dB.  The
 kernels go wrong per window (lanes, masks, tables and index arithmetic are per window / per head / per edge row), so this module
@@ -15,6 +15,10 @@ region_max(err) <= B * region_max(noise) + tau.  tau is a floor for regions wher
 The CUNet family (``waifu2x.cunet`` / ``upcunet`` / ``vgg_7`` / ``upconv_7``, oracle/cunet.py) goes wrong per 8 x 32 output patch of a
 conv workgroup, per 16 x 16 head tile, per 16-channel MFMA n-tile and per image (SE pooling, the scale table): its regions are the
 cells 8 / 16 / 32 / 64 of the level-1 map in output pixels (twice that for the 2x nets), with the same constants.
+
+The iw3 side nets (``sbs.row_flow_v3``, ``sbs.mlbw_*``, csrc/rowflow.hip) run one window of 4 x 4 or 3 x 3 tokens per wave and a token
+is 1 row x 8 depth pixels: their regions are rectangular cells (cell_h, cell_w) with offsets (off_y, off_x), and since flows,
+softmax weights and logits are not clamped the floor is relative, tau = TAP_TAU_REL x the map's rms (``tests/sidenet_cases.py``).
 """
 import math
 
@@ -22,6 +26,8 @@ import torch
 import torch.nn.functional as F
 
 from oracle import cunet as OC
+from oracle import mlbw as OM
+from oracle import row_flow_v3 as ORF
 from oracle import swin_unet as O
 from oracle import swin_unet_v2 as OV
 from oracle.fp16_emulation import fp16_autocast_emulation, half_weights
@@ -37,13 +43,44 @@ CUNET_SCALE = {"waifu2x.cunet": 1, "waifu2x.upcunet": 2, "waifu2x.vgg_7": 1, "wa
 CUNET_OFFSET = {"waifu2x.cunet": 28, "waifu2x.upcunet": 36, "waifu2x.vgg_7": 7, "waifu2x.upconv_7": 14}
 CUNET_CELLS = (8, 16, 32, 64)                   # kTH = 8, the 16 x 16 head tile, kTW = 32, and two patches side by side
 
+# the iw3 side nets (csrc/rowflow.hip): one window per wave, a token = 1 row x 8 depth pixels, so a window of WS x WS tokens is a
+# cell of (WS, 8 WS) output pixels.  name -> (layers, small, hole mask) for the MLBW family
+ROW_FLOW = "sbs.row_flow_v3"
+ROW_FLOW_CELLS = ((4, 32), (3, 24), (12, 96))   # the 4 x 4 and the 3 x 3 window, and the pad unit (12 rows x 96 columns)
+MLBW = {"sbs.mlbw_l2": (2, False, False), "sbs.mlbw_l4": (4, False, False), "sbs.mlbw_l2s": (2, True, False),
+        "sbs.mask_mlbw_l2": (2, False, True)}
+MLBW_CELL = (4, 32)
+
 # Thresholds: about twice the worst ratios measured on an MI355X over every case of tests/test_gpu_swin_errloc.py (its docstring)
 A_OUT, B_OUT, TAU_OUT = 2.5, 3.75, 5e-4          # clamped [0,1] outputs (worst 1.16 / 1.82); tau = one fp16 ulp in [0.5, 1)
 A_TAP, B_TAP = 3.5, 5.5                          # NHWC debug taps per 6 x 6 window and head (worst 1.69 / 2.78)
 TAP_TAU_REL = 2e-3                               # tap tau = 2e-3 x the tap's rms
+# the side nets (unclamped flows, softmax weights, mask logits; tau = TAP_TAU_REL x the map's rms): about twice the worst ratios
+# measured on an MI355X over every case of tests/test_gpu_sidenet_errloc.py (its docstring): 1.03 global, 1.80 per region
+A_SIDE, B_SIDE = 2.1, 3.6
+# fp32 kernels (delta_warp): e_hip <= K_WARP e_ref + floor over the whole map and per (8, 8) cell, e_ref = the oracle's own fp32 error.
+# The floor is WARP_FLOOR_ULPS ulp of the normalised sampling coordinate (``warp_floor``); K_WARP stays at the project's 2.2 (the
+# measured worst k is below half of it, and a k below 1 would ask the engine to beat the fp32 reference)
+K_WARP, WARP_FLOOR_ULPS = 2.2, 1.0
+
+
+def warp_floor(c):
+    """The error of a bilinear sample of ``c`` [B,C,H,W] whose normalised coordinates (gx + 1, gy + 1 in [1, 2) over the right / lower
+    half, align_corners) are off by WARP_FLOOR_ULPS fp32 ulp each: 2^-23 (W - 1) / 2 pixels times the steepest horizontal step, plus
+    the same vertically.  Two correct fp32 evaluations differ by this much wherever one of them happens to land on an exact pixel (a
+    zero flow: the oracle's fp32 error is 5.5e-8 in cells where the kernel's is 1.4e-6 = 0.6 ulp at W = 131), so a fixed 1e-6 is not
+    a floor for images wider than about 60 pixels."""
+    h, w = c.shape[2:]
+    sx = float((c[..., :, 1:] - c[..., :, :-1]).abs().max()) if w > 1 else 0.0
+    sy = float((c[..., 1:, :] - c[..., :-1, :]).abs().max()) if h > 1 else 0.0
+    return WARP_FLOOR_ULPS * 2.0 ** -23 * (0.5 * (w - 1) * sx + 0.5 * (h - 1) * sy)
 
 
 def _forward(sd, x, name, taps=None, no_clip=False):
+    if name == ROW_FLOW or name in MLBW:
+        assert taps is None and not no_clip, "the side nets have no taps / no_clip"
+        # x: the [B,3,h,w] feature planes (depth | divergence | convergence); unclamped flows, softmax weights, mask logits
+        return ORF.delta_forward(sd, x) if name == ROW_FLOW else OM.delta_forward(sd, x, MLBW[name][0])
     if name in ("waifu2x.cunet", "waifu2x.upcunet"):
         return OC.model_forward(sd, x, no_clip=no_clip, taps=taps)
     if name in ("waifu2x.vgg_7", "waifu2x.upconv_7"):
@@ -67,9 +104,23 @@ def emulated(sd, x, name, taps=None, no_clip=False):
         return _forward(half_weights(sd), x.float(), name, taps, no_clip)
 
 
-def cells_for(name, origin=0):
+def mlbw_pad(h, w):
+    """(ph1, pw1): the top / left part of MLBW's centred replicate pad to multiples of 4 x 32 (oracle/mlbw.py delta_forward)."""
+    return (4 - h % 4) // 2, (32 - w % 32) // 2
+
+
+def cells_for(name, origin=0, shape=None):
     """[(cell, offset)] of the windows of every level mapped to output pixels: the aligned partition of each level.
-    ``origin``: the tile-output pixel the compared map starts at (a crop of the tile output)."""
+    ``origin``: the tile-output pixel the compared map starts at (a crop of the tile output).
+    The side nets have rectangular cells: entries ((cell_h, cell_w), (off_y, off_x)[, (shift_y, shift_x)]); the shift is the second
+    partition ``localised_stats`` looks at (default: half a cell both ways).  row_flow_v3 pads bottom / right only (origin 0); MLBW pads
+    centred, so its windows start at (-ph1, -pw1) of the ``shape`` = (h, w) output, and its shifted blocks sit 2 tokens further
+    (sy / sx of nunif_hip_mlbw_create: (2, 2) tokens = (2, 16) pixels for the full nets, (0, 2) = (0, 16) for the small ones)."""
+    if name == ROW_FLOW:
+        return [(c, (0, 0)) for c in ROW_FLOW_CELLS]
+    if name in MLBW:
+        ph1, pw1 = mlbw_pad(*shape)
+        return [(MLBW_CELL, ((-ph1) % MLBW_CELL[0], (-pw1) % MLBW_CELL[1]), (0, 16) if MLBW[name][1] else (2, 16))]
     if name in CUNET_SCALE:
         s = CUNET_SCALE[name]
         return [(c * s, (-origin) % (c * s)) for c in CUNET_CELLS]
@@ -80,29 +131,36 @@ def cells_for(name, origin=0):
     return [(6 * s * 2 ** k, (-origin) % (6 * s * 2 ** k)) for k in range(3)]
 
 
+def _pair(v):
+    """An int cell / offset means the same on both axes; a (y, x) pair is taken as it is."""
+    return (v, v) if isinstance(v, int) else (int(v[0]), int(v[1]))
+
+
 def region_max(err, cell, offset=0, group=None):
     """max |err| over channels (or over each group of ``group`` channels) inside each ``cell x cell`` block, per image.
     err: [B, C, H, W].  Block boundaries sit at ``offset + k * cell``; the partial blocks at the borders are regions too.
+    ``cell`` / ``offset``: an int, or (cell_h, cell_w) / (off_y, off_x) for rectangular blocks.
     Returns [B, G, nby, nbx] (G = 1 without ``group``)."""
     e = err.abs()
     b, c, h, w = e.shape
     g = c if group is None else group
     e = e.reshape(b, c // g, g, h, w).amax(2)
-    lead = offset % cell
-    top = (cell - lead) % cell
-    bottom = (-(h + top)) % cell
-    right = (-(w + top)) % cell
-    e = F.pad(e, (top, right, top, bottom))                 # |err| >= 0: zero padding never wins a max
-    return F.max_pool2d(e, cell, cell)
+    (ch, cw), (oy, ox) = _pair(cell), _pair(offset)
+    top, left = (ch - oy % ch) % ch, (cw - ox % cw) % cw
+    bottom = (-(h + top)) % ch
+    right = (-(w + left)) % cw
+    e = F.pad(e, (left, right, top, bottom))                # |err| >= 0: zero padding never wins a max
+    return F.max_pool2d(e, (ch, cw), (ch, cw))
 
 
 def _argmax_channel(err, bi, gi, group, cell, offset, ry, rx):
     e = err[bi].abs()
     if group is not None:
         e = e[gi * group:(gi + 1) * group]
-    top = (cell - offset % cell) % cell
-    y0, x0 = max(0, ry * cell - top), max(0, rx * cell - top)
-    y1, x1 = ry * cell - top + cell, rx * cell - top + cell
+    (ch, cw), (oy, ox) = _pair(cell), _pair(offset)
+    top, left = (ch - oy % ch) % ch, (cw - ox % cw) % cw
+    y0, x0 = max(0, ry * ch - top), max(0, rx * cw - left)
+    y1, x1 = ry * ch - top + ch, rx * cw - left + cw
     blk = e[:, y0:y1, x0:x1]
     ch = int(blk.reshape(blk.shape[0], -1).amax(1).argmax())
     return ch + (gi * group if group is not None else 0), (y0, x0)
@@ -119,8 +177,14 @@ def localised_stats(y, y64, yemu, cells, B=1.0, tau=0.0, group=None):
     err = y.double() - y64.double()
     noise = yemu.double() - y64.double()
     out = {"global": float(err.abs().max() / noise.abs().max().clamp_min(1e-30)), "worst": 0.0, "bands": {}, "regions": []}
-    for cell, base in cells:
-        for off in sorted({base % cell, (base + cell // 2) % cell}):
+    for cell, base, *shift in cells:
+        if isinstance(cell, int):
+            offsets = sorted({base % cell, (base + cell // 2) % cell})
+        else:                                               # rectangular: (cell_h, cell_w), (off_y, off_x)[, (shift_y, shift_x)]
+            (ch, cw), (by, bx) = _pair(cell), _pair(base)
+            sy, sx = _pair(shift[0]) if shift else (ch // 2, cw // 2)
+            offsets = sorted({(by % ch, bx % cw), ((by + sy) % ch, (bx + sx) % cw)})
+        for off in offsets:
             r = region_max(err, cell, off, group)
             re = region_max(noise, cell, off, group)
             ratio = r / (re + tau / B)

@@ -5,6 +5,8 @@ import numpy as np
 import pytest
 import torch
 
+import errloc as E
+import sidenet_cases as S
 from conftest import GOLDEN, psnr, sd_checksum
 from oracle import mlbw as OM
 from oracle import row_flow_v3 as ORF
@@ -51,6 +53,11 @@ def test_hip_mlbw(hiplib, g, tag, L, small, nb):
     ed, ew = (d.cpu() - g[tag + "_delta"]).abs(), (w.cpu() - g[tag + "_weight"]).abs()
     assert ed.max().item() < 5e-2 and ed.mean().item() < 4e-3, (ed.max().item(), ed.mean().item())
     assert ew.max().item() < 3e-2 and ew.mean().item() < 2e-3, (ew.max().item(), ew.mean().item())
+    # the same outputs window by window against the float64 oracle (tests/errloc.py, test_gpu_sidenet_errloc.py)
+    xo = ORF.make_input(g["depth"][:1], 2.0, 0.5, 104)
+    for name, y, y64, ye in zip(("delta", "weight"), (d, w), E.oracle64(sd, xo, "sbs.mlbw_" + tag), E.emulated(sd, xo, "sbs.mlbw_" + tag)):
+        E.check_localised(y.cpu(), y64, ye, E.cells_for("sbs.mlbw_" + tag, shape=(58, 104)), E.A_SIDE, E.B_SIDE, S.tau_for(y64),
+                          label=f"mlbw_{tag} fixture {name}")
     left, right = apply_divergence_nn_LR(m, c[:nb], depth[:nb], 2.0, 0.5, steps=1, synthetic_view="both")
     pl, pr = psnr(left.cpu(), g[tag + "_left"]), psnr(right.cpu(), g[tag + "_right"])
     assert pl >= 50.0 and pr >= 50.0, (pl, pr)

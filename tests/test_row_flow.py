@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+import errloc as E
+import sidenet_cases as S
 from conftest import GOLDEN, psnr, sd_checksum, synth_image
 from oracle import row_flow_v3 as ORF
 from oracle.forward_warp import synth_depth
@@ -56,6 +58,10 @@ def test_hip_delta_and_warp(hiplib, g):
     err = (d2[:, :1].cpu() - g["delta"]).abs()
     # delta is in depth pixels; fp16 activations: a few 1e-3 px
     assert err.max().item() < 2e-2 and err.mean().item() < 2e-3, (err.max().item(), err.mean().item())
+    # the same output window by window against the float64 oracle (tests/errloc.py, test_gpu_sidenet_errloc.py)
+    xo = ORF.make_input(g["depth"], 2.0, 0.5, 104)
+    y64, ye = E.oracle64(sd, xo, m.name), E.emulated(sd, xo, m.name)
+    E.check_localised(d2[:, :1].cpu(), y64, ye, E.cells_for(m.name), E.A_SIDE, E.B_SIDE, S.tau_for(y64), label="row_flow fixture delta")
     left, right = apply_divergence_nn_LR(m, c, depth, 2.0, 0.5, steps=None, synthetic_view="both")
     assert psnr(left.cpu(), g["left"]) >= 50.0 and psnr(right.cpu(), g["right"]) >= 50.0, \
         (psnr(left.cpu(), g["left"]), psnr(right.cpu(), g["right"]))
