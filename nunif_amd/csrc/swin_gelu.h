@@ -12,17 +12,10 @@
 namespace nunif {
 
 __device__ __forceinline__ f16x8 gelu8(const f32x4 &a, const f32x4 &b) {
-#ifdef NUNIF_GELU_DEG8
-    constexpr int ND = 8;
-    constexpr float kc[ND + 1] = {8.063430101e-11f, -7.003475758e-09f, 2.716159007e-07f, -6.295003997e-06f,
-                                  9.890811950e-05f, -1.133922332e-03f, 9.877477530e-03f, -6.641059600e-02f,
-                                  3.989227099e-01f};
-#else
     constexpr int ND = 6;
     constexpr float kc[ND + 1] = {2.2779071073841806e-08f, -1.5984835499693872e-06f, 4.795320637640543e-05f,
                                   -0.0008139933925122023f, 0.008772282861173153f, -0.06457287818193436f,
                                   0.39788317680358887f};
-#endif
     float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
     float u[8], q[8];
 #pragma unroll
@@ -83,15 +76,10 @@ __device__ __forceinline__ f16x8 gelu8h(const f32x4 &a, const f32x4 &b) {
 // inputs per hot-regime case (tools/hot_regime_stats.py, profiles/r05a_hot_*.json): mean distance to the emulated fp16 reference
 // with the packed / the fp32 form  2x -0.77 / -0.82 dB, 4x -0.86 / -0.56, 2x_chaos -2.81 / -2.76 — inside the +-0.3..0.4 dB standard
 // error, no difference — but 1x -1.81 / -0.55: that net pays 1.3 dB for the packed form, so it does not get it.
-// -DNUNIF_GELU_F32 forces the fp32 form everywhere (A/B builds).
 template <bool G32 = false>
 __device__ __forceinline__ f16x8 gelu8t(const f32x4 &a, const f32x4 &b) {
-#ifdef NUNIF_GELU_F32
-    return gelu8(a, b);
-#else
     if constexpr (G32) return gelu8(a, b);
     else return gelu8h(a, b);
-#endif
 }
 
 }  // namespace nunif

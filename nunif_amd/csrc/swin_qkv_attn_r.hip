@@ -17,7 +17,6 @@
 //   * the next window's x is requested at the end of a window's trip (four waves per SIMD hide the rest).
 #include <algorithm>
 #include <cstdlib>
-#include <type_traits>
 
 #include "swin_kernels.h"
 
@@ -25,34 +24,12 @@ namespace nunif {
 
 #define MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
 
-// LDS operands requested one step ahead (round 6): 1 = weight fragments, 2 = qkv biases, 4 = score bias rows
-#ifndef NUNIF_QKV_PF
-#define NUNIF_QKV_PF 1
-#endif
-#ifndef NUNIF_QKV_PF192
-#define NUNIF_QKV_PF192 0
-#endif
-// Round 6: compile-time switches of this kernel, each measured as a same-box A/B of build variants (tools/build_variant.py,
-// tools/ab_multi.sh; DESIGN.md 6.000000, profiles/r06*_attn_*).  NUNIF_QKV_DIET is a bit mask; the default is what measured fastest.
-//   ON   1  window-major stores as `SGPR base + 32-bit lane constant` (no 64-bit address arithmetic per tile)
-//   ON   2  `o * inv` and its fp16 convert as one v_fma_mixlo / mixhi_f16 per value (one rounding instead of two)
-//   ON   4  (the lone probability of key tile 2 built from an opaque zero: hipcc still emits v_cvt_f16_f32 + v_pack_b32_f16 — no effect)
-//   ON   8  C = 96: the six heads unrolled behind sched_barrier(0): every LDS address an immediate (13 address adds per head gone)
-//   ON  32  C = 96 window-major: the next window's x requested when the last head's q / k / v exist          338.5 -> 333.4 us
-//   off 16  K = 16 score MFMAs (v_mfma_f32_16x16x16_f16) on a path of their own for the windows without shift regions   344.9 vs 342.1
-//   off 64  that split with K = 32 MFMAs on both paths (no region registers on the common path)                  24 spilled registers
-//   off 128 two passes over a wave's windows (plain, then the last row / column): no scratch, 353.0 vs 341.7 (a tail of 0-3 windows)
-//   off NUNIF_QKV_BTAB_FRAG (swin_kernels.h): bias tables / qkv biases as lane-linear fragments: no bank conflicts, 353.3 vs 342.7
-//   off NUNIF_QKV_UNROLL192 1 / 2: C = 192 heads unrolled / + early x: 137.5 / 140.7 vs 138.6
-// With 1 + 2 + 8 + 32 the window-major C = 96 instance sits at exactly 128 registers and hipcc parks ~15 per-lane constants of the
-// last-row / last-column path in scratch (prologue + that path; +7.4 % FETCH_SIZE); tests/test_isa_invariants.py pins that no scratch
-// access sits inside the unrolled heads.
-#ifndef NUNIF_QKV_UNROLL192
-#define NUNIF_QKV_UNROLL192 0
-#endif
-#ifndef NUNIF_QKV_DIET
-#define NUNIF_QKV_DIET 47
-#endif
+// What is compiled today (the measured-off build variants of round 6 and their numbers: docs/history.md, "Removed build variants"):
+// window-major stores are `SGPR base + 32-bit lane constant`, `o * inv` and its fp16 convert are one v_fma_mixlo / mixhi_f16 per
+// value, the six heads of C = 96 are unrolled behind sched_barrier(0) (every LDS address an immediate) with the weight fragments
+// requested one step ahead, and the window-major C = 96 instance requests the next window's x once the last head's q / k / v exist.
+// That instance sits at exactly 128 registers and hipcc parks ~15 per-lane constants of the last-row / last-column path in scratch
+// (prologue + that path; +7.4 % FETCH_SIZE); tests/test_isa_invariants.py pins that no scratch access sits inside the unrolled heads.
 
 // the "real key" column 36 of the bias table carries 1000: padded keys end up 1000 (log2 units) below every real one
 constexpr float kRegionR = 100.0f;     // added where query and key share a shift region
@@ -75,21 +52,13 @@ __device__ __forceinline__ f16x8 cat8r(f16x4 lo, f16x4 hi) {
 // one instruction per value instead of v_mul_f32 + half a v_cvt_pk_f16_f32.  (Written as C so that hipcc counts the wait states
 // between the MFMA that produces `o` and this read: as inline asm it does not, and the first version read half-written accumulators.)
 __device__ __forceinline__ f16x4 mul4_to_f16(const f32x4 &o, float inv) {
-    if constexpr ((NUNIF_QKV_DIET & 2) != 0) {
-        return (f16x4){(f16)__builtin_fmaf(o[0], inv, 0.0f), (f16)__builtin_fmaf(o[1], inv, 0.0f), (f16)__builtin_fmaf(o[2], inv, 0.0f),
-                       (f16)__builtin_fmaf(o[3], inv, 0.0f)};
-    } else {
-        return (f16x4){(f16)(o[0] * inv), (f16)(o[1] * inv), (f16)(o[2] * inv), (f16)(o[3] * inv)};
-    }
+    return (f16x4){(f16)__builtin_fmaf(o[0], inv, 0.0f), (f16)__builtin_fmaf(o[1], inv, 0.0f), (f16)__builtin_fmaf(o[2], inv, 0.0f),
+                   (f16)__builtin_fmaf(o[3], inv, 0.0f)};
 }
-// {(f16) e, 0, 0, 0}: with a zero hipcc cannot see through (`zf`, an SGPR) the pair is ONE v_cvt_pk_f16_f32 instead of v_cvt_f16_f32 +
-// v_pack_b32_f16
+// {(f16) e, 0, 0, 0} with a zero hipcc cannot see through (`zf`, an SGPR).  Meant to make the pair ONE v_cvt_pk_f16_f32; hipcc still
+// emits v_cvt_f16_f32 + v_pack_b32_f16 (no effect measured), and the form is kept because it is what the pinned code is compiled from
 __device__ __forceinline__ f16x4 lone_to_f16x4(float e, float zf) {
-    if constexpr ((NUNIF_QKV_DIET & 4) != 0) {
-        return (f16x4){(f16)e, (f16)zf, (f16)0.f, (f16)0.f};
-    } else {
-        return (f16x4){(f16)e, (f16)0.f, (f16)0.f, (f16)0.f};
-    }
+    return (f16x4){(f16)e, (f16)zf, (f16)0.f, (f16)0.f};
 }
 
 constexpr int kBiasStride = 52;        // fp32 row stride of the CBIAS table: 16 lanes x 16 B land in 16 distinct bank quads
@@ -132,10 +101,7 @@ qkv_attn_r_kernel(QkvAttnRArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_r[];
     f16x8 *wl = reinterpret_cast<f16x8 *>(smem_r);                                   // [HPP*FPH][64]
     float *bt32 = reinterpret_cast<float *>(wl + HPP * FPH * 64);                    // [HPP][36][52]
-    // qkv biases: kQkvBiasFragMajor: the accumulators' initial values as FRAGMENTS [HPP][3 NTH][64 lanes] f32x4 (q / k tiles: four
-    // channels per lane group, v tiles — operands swapped — the column's channel in all four registers): one lane-linear read like
-    // every other LDS operand of this kernel, whose single address register is lane * 16; otherwise [3C] floats
-    float *bl = bt32 + HPP * kQkvBiasFloatsPerHead;
+    float *bl = bt32 + HPP * kQkvBiasFloatsPerHead;                                  // qkv biases, [3C]
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -147,21 +113,13 @@ qkv_attn_r_kernel(QkvAttnRArgs a) {
     float zf = 0.f;
     asm("" : "+s"(zf));                     // a zero the compiler cannot fold (lone_to_f16x4)
 
-    if constexpr (!kQkvBiasFragMajor) {
-        for (int i = tid; i < 3 * C; i += NTHR) bl[i] = a.bqkv[i];
-    }
+    for (int i = tid; i < 3 * C; i += NTHR) bl[i] = a.bqkv[i];
     const f16x8 ones8 = {(f16)1.f, (f16)1.f, (f16)1.f, (f16)1.f, (f16)1.f, (f16)1.f, (f16)1.f, (f16)1.f};
 
     // ---- per-lane constants of the launch: the window token of column r16 of tile mt, its pixel offset ----------------------
-    int tokc[3], iyc[3], ixc[3];
-    unsigned xoff[3];                       // byte offset of (token, channel 8 grp) from the window's first pixel, no wrap-around
+    int tokc[3];
 #pragma unroll
-    for (int mt = 0; mt < 3; ++mt) {
-        tokc[mt] = win_token(mt, r16);
-        iyc[mt] = tokc[mt] / 6;
-        ixc[mt] = tokc[mt] - 6 * iyc[mt];
-        xoff[mt] = (unsigned)(((iyc[mt] * a.W + ixc[mt]) * C + 8 * grp) * 2);
-    }
+    for (int mt = 0; mt < 3; ++mt) tokc[mt] = win_token(mt, r16);
     unsigned wm_off[3];                     // window-major store offset of (token, channels 4 grp ..) inside a head's 36 x HD block
 #pragma unroll
     for (int mt = 0; mt < 3; ++mt) wm_off[mt] = (unsigned)((tokc[mt] * HD + 4 * grp) * 2);
@@ -188,16 +146,6 @@ qkv_attn_r_kernel(QkvAttnRArgs a) {
     {
         const f16x8 *src = reinterpret_cast<const f16x8 *>(a.wres) + (long)pass * HPP * FPH * 64;
         for (int i = tid; i < HPP * FPH * 64; i += NTHR) wl[i] = src[i];
-        if constexpr (kQkvBiasFragMajor) {
-            for (int i = tid; i < HPP * 3 * NTH * 64; i += NTHR) {
-                const int ln = i & 63, t = i >> 6, hl = t / (3 * NTH), pn = t - hl * (3 * NTH), part = pn / NTH, nt = pn - part * NTH;
-                const int ch0 = part * C + (pass * HPP + hl) * HD + nt * 16;
-                f32x4 v;
-                if (part == 2) { const float bv = a.bqkv[ch0 + (ln & 15)]; v = (f32x4){bv, bv, bv, bv}; }
-                else v = *reinterpret_cast<const f32x4 *>(a.bqkv + ch0 + 4 * (ln >> 4));
-                reinterpret_cast<f32x4 *>(bl)[i] = v;
-            }
-        }
         const f32x4 *bsrc = reinterpret_cast<const f32x4 *>(a.btab32 + (long)pass * HPP * kQkvBiasFloatsPerHead);
         for (int i = tid; i < HPP * kQkvBiasFloatsPerHead / 4; i += NTHR) reinterpret_cast<f32x4 *>(bt32)[i] = bsrc[i];
     }
@@ -224,19 +172,14 @@ qkv_attn_r_kernel(QkvAttnRArgs a) {
             }
         } else {
             const unsigned org = (unsigned)((y0 * a.W + x0) * C * 2);
-            if constexpr ((NUNIF_QKV_DIET & 32) != 0) {
-                // the lane's offsets rebuilt from the lane id (an opaque copy: hoisted out of the window loop they are three more
-                // registers carried — and spilled — across it): ~15 VALU per window
-                int rl = r16;
-                asm("" : "+v"(rl));
+            // the lane's offsets rebuilt from the lane id (an opaque copy: hoisted out of the window loop they are three more
+            // registers carried — and spilled — across it): ~15 VALU per window
+            int rl = r16;
+            asm("" : "+v"(rl));
 #pragma unroll
-                for (int mt = 0; mt < 3; ++mt) {
-                    const int tk = win_token(mt, rl), iy = (tk * 43) >> 8, ix = tk - 6 * iy;        // tk / 6 for tk < 36
-                    vo[mt] = org + (unsigned)(((iy * a.W + ix) * C + 8 * grp) * 2);
-                }
-            } else {
-#pragma unroll
-                for (int mt = 0; mt < 3; ++mt) vo[mt] = org + xoff[mt];
+            for (int mt = 0; mt < 3; ++mt) {
+                const int tk = win_token(mt, rl), iy = (tk * 43) >> 8, ix = tk - 6 * iy;        // tk / 6 for tk < 36
+                vo[mt] = org + (unsigned)(((iy * a.W + ix) * C + 8 * grp) * 2);
             }
         }
 #pragma unroll
@@ -261,45 +204,24 @@ qkv_attn_r_kernel(QkvAttnRArgs a) {
 
     // initial accumulator of output tile (part, nt) of local head hl (global head `head`)
     auto qkv_bias = [&](int hl, int head, int part, int nt) -> f32x4 {
-        if constexpr (kQkvBiasFragMajor) {
-            return reinterpret_cast<const f32x4 *>(bl)[(hl * 3 * NTH + part * NTH + nt) * 64 + lane];
-        } else {
-            const int ch0 = part * C + head * HD + nt * 16;
-            if (part == 2) { const float bv = bl[ch0 + r16]; return (f32x4){bv, bv, bv, bv}; }
-            return *reinterpret_cast<const f32x4 *>(bl + ch0 + 4 * grp);
-        }
+        const int ch0 = part * C + head * HD + nt * 16;
+        if (part == 2) { const float bv = bl[ch0 + r16]; return (f32x4){bv, bv, bv, bv}; }
+        return *reinterpret_cast<const f32x4 *>(bl + ch0 + 4 * grp);
     };
     // C operand of the score tile (query tile qt, key tile kt) of local head hl
     auto bias_frag = [&](int hl, int qt, int kt) -> f32x4 {
-        if constexpr (kQkvBiasFragMajor)
-            return reinterpret_cast<const f32x4 *>(bt32)[((hl * 3 + qt) * 3 + kt) * 64 + lane];
-        else
-            return *reinterpret_cast<const f32x4 *>(bt32 + (hl * 36 + tokc[qt]) * kBiasStride + 4 * grp + 16 * kt);
+        return *reinterpret_cast<const f32x4 *>(bt32 + (hl * 36 + tokc[qt]) * kBiasStride + 4 * grp + 16 * kt);
     };
     f16x8 xf[3][KS];
-    unsigned vo[3], von[3] = {0u, 0u, 0u};      // von: the next window's offsets while this window's pixel-major stores still read vo
+    unsigned vo[3];
     int wb, wy, wx;
     bool special;
     f16x8 wnx = wl[lane];                  // first weight fragment of the next head (see the head loop)
-    // DIET & 128 (C = 96, window-major): TWO passes over the wave's windows — first the windows that need no shift-region term (all but
-    // the last row / column of a shifted map) through the unrolled heads with no region registers and the early x request, then the
-    // others through the rolled form.  One loop over both kinds made hipcc allocate for their union: 15 per-lane constants in
-    // scratch, reloaded per window (+7.4 % FETCH_SIZE, profiles/r06n_attn_fetch_by_variant.txt).  MODE 0: one pass over all windows.
-    constexpr bool kTwoLoops = (NUNIF_QKV_DIET & 128) && C == 96 && WM && HD == 16;
-    const int cx0 = cx, cy0 = cy, cb0 = cb;
-    auto run_windows = [&](auto mode_tag) {
-    constexpr int MODE = decltype(mode_tag)::value;            // 0: every window, 1: the plain ones, 2: the ones with two shift regions
+    // (The window loop and the head loop stay wrapped in lambdas called once: written inline, hipcc allocates registers differently.)
+    auto run_windows = [&]() {
     int wi = w0;
-    cx = cx0; cy = cy0; cb = cb0;
     decode(wb, wy, wx, special);
-    // step(): on to the next window of this pass
-    auto skip = [&]() {
-        if constexpr (MODE != 0) {
-            while (wi < a.n_windows && special != (MODE == 2)) { advance(); wi += wstride; decode(wb, wy, wx, special); }
-        }
-    };
-    auto step = [&]() { advance(); wi += wstride; decode(wb, wy, wx, special); skip(); };
-    skip();
+    auto step = [&]() { advance(); wi += wstride; decode(wb, wy, wx, special); };      // on to the wave's next window
     if (wi < a.n_windows) load_x(wb, wy, wx, special, xf, vo);
 #pragma unroll 1
     while (wi < a.n_windows) {
@@ -310,21 +232,13 @@ qkv_attn_r_kernel(QkvAttnRArgs a) {
         const unsigned wm_base = (unsigned)__builtin_amdgcn_readfirstlane((unsigned)wq * (unsigned)(HEADS * 36 * HD * 2));
 
         // C = 96: the six heads unrolled (every LDS address an immediate); C = 192 does not fit that way (143 spilled registers).
-        // DIET & 16 (head_dim 16): the windows that need no shift-region term — all but the last row / column of a shifted map — take
-        // a path of their own (SP = false) with K = 16 score MFMAs; the others the K = 32 form with the region one-hots, rolled.
-        // DIET & 64: the same split with K = 32 score MFMAs on both paths — the common path then carries NO region registers (the term is
-        // a constant over every row there and drops out of the softmax; rkr / rqr were 12 registers live across all six heads, and at
-        // 128 registers the early x request of DIET & 32 had pushed 15 per-lane constants into scratch)
-        constexpr bool kSplitK16 = (NUNIF_QKV_DIET & 16) && HD == 16;
-        constexpr bool kSplit = (((NUNIF_QKV_DIET & 16) || (NUNIF_QKV_DIET & 64)) && HD == 16) || MODE != 0;
-        // (C = 192, pixel-major stores: they read vo, so the early request goes through a second offset set there)
-        constexpr bool kEarlyX = (NUNIF_QKV_DIET & 32) && (NUNIF_QKV_DIET & 8) && ((C == 96 && WM) || (C == 192 && NUNIF_QKV_UNROLL192 == 2)) && !kSplitK16 && MODE != 2;
-        auto run_heads = [&](auto sp_tag) {
-        constexpr bool SP = decltype(sp_tag)::value;
+        // C = 96 window-major: the next window's x is requested inside the last head (below)
+        constexpr bool kEarlyX = C == 96 && WM;
+        auto run_heads = [&]() {
         const bool sp_now = special;            // (kEarlyX decodes the NEXT window inside the last head)
         // shift regions of this window (only the last window row / column straddles two regions)
         f16x4 rkr[3], rqr[3];
-        if (special && (SP || !kSplit)) {
+        if (special) {
             const bool last_y = wy == nwy - 1, last_x = wx == nwx - 1;
 #pragma unroll
             for (int mt = 0; mt < 3; ++mt) {
@@ -341,45 +255,36 @@ qkv_attn_r_kernel(QkvAttnRArgs a) {
 #pragma unroll
             for (int mt = 0; mt < 3; ++mt) { rkr[mt] = rk0; rqr[mt] = rq0; }
         }
-        constexpr int kHeadUnroll = ((NUNIF_QKV_DIET & 8) && (C == 96 || NUNIF_QKV_UNROLL192) && !(kSplit && SP)) ? HPP : 1;
+        constexpr int kHeadUnroll = C == 96 ? HPP : 1;
 #pragma unroll kHeadUnroll
         for (int hl = 0; hl < HPP; ++hl) {
             const int head = pass * HPP + hl;
             const f16x8 *wh = wl + (hl * FPH) * 64 + lane;
             // ---- q, k (channels x tokens) and v (tokens x channels: operands swapped) of this head ----------------
-            // Round 6: every LDS operand is requested one step before the MFMAs that consume it (weight fragment f + 1 and the
-            // next part's bias behind the MFMAs of fragment f; the first fragment of the NEXT head — carried in wnx across the
-            // head and the window loop — behind the last): the round-5 form issued each ds_read directly in front of its
-            // s_waitcnt lgkmcnt(0), 18 exposed LDS round trips per head and wave (31 % of the wave cycles in s_waitcnt,
-            // profiles/r05b_sq.txt SQ_WAIT_ANY).
-            constexpr int PF = C == 96 ? NUNIF_QKV_PF : NUNIF_QKV_PF192;
+            // C = 96: every weight fragment is requested one step before the MFMAs that consume it (fragment f + 1 behind the
+            // MFMAs of fragment f; the first fragment of the NEXT head — carried in wnx across the head and the window loop —
+            // behind the last): the round-5 form issued each ds_read directly in front of its s_waitcnt lgkmcnt(0), 18 exposed
+            // LDS round trips per head and wave (31 % of the wave cycles in s_waitcnt, profiles/r05b_sq.txt SQ_WAIT_ANY).
+            constexpr bool kPrefetchW = C == 96;              // weight fragments one step ahead for C = 96, not for C = 192
             f16x4 qt4[NTH][3], kt4[NTH][3], vt4[NTH][3];
             f16x8 wq2[2];
-            wq2[0] = (PF & 1) ? wnx : wh[0];
-            f32x4 bnx = qkv_bias(hl, head, 0, 0);
+            wq2[0] = kPrefetchW ? wnx : wh[0];
+            f32x4 bnx = qkv_bias(hl, head, 0, 0);       // (requested here, ahead of the loop: where hipcc places the first bias read)
 #pragma unroll
             for (int part = 0; part < 3; ++part) {
 #pragma unroll
                 for (int nt = 0; nt < NTH; ++nt) {
-                    const int ch0 = part * C + head * HD + nt * 16;
                     const int fidx = (part * NTH + nt) * KS;
                     f32x4 acc[3];
-                    if constexpr (!(PF & 2)) bnx = qkv_bias(hl, head, part, nt);
+                    // bias of the output tile: parts 0 / 1 four channels per lane group, part 2 (operands swapped) one per column
+                    bnx = qkv_bias(hl, head, part, nt);
 #pragma unroll
                     for (int mt = 0; mt < 3; ++mt) acc[mt] = bnx;
-                    // bias of the next output tile: parts 0 / 1 four channels per lane group, part 2 (operands swapped) one per column
-                    if constexpr ((PF & 2) != 0) {
-                        const int nf = part * NTH + nt + 1;
-                        if (nf < 3 * NTH) {
-                            bnx = qkv_bias(hl, head, nf / NTH, nf % NTH);
-                        }
-                    }
-                    (void)ch0;
 #pragma unroll
                     for (int ks = 0; ks < KS; ++ks) {
                         const int f = fidx + ks;
                         // the fragment after the head's last one is the next head's first (the next window's first after the last head)
-                        if constexpr ((PF & 1) != 0)
+                        if constexpr (kPrefetchW)
                             wq2[(f + 1) & 1] = (f + 1 < FPH) ? wh[(f + 1) * 64] : (hl + 1 < HPP ? wh[FPH * 64] : wl[lane]);
                         else wq2[f & 1] = wh[f * 64];
                         const f16x8 w = wq2[f & 1];
@@ -394,23 +299,15 @@ qkv_attn_r_kernel(QkvAttnRArgs a) {
                     }
                 }
             }
-            if constexpr ((PF & 1) != 0) wnx = wq2[FPH & 1];
+            if constexpr (kPrefetchW) wnx = wq2[FPH & 1];
             if constexpr (kEarlyX) {
-                // DIET & 32: x is dead once the LAST head's q / k / v exist — the next window's x is requested here, one softmax phase
+                // x is dead once the LAST head's q / k / v exist — the next window's x is requested here, one softmax phase
                 // (~1 000 issue cycles x 4 waves) ahead of the top of the next trip, where it used to be requested AND awaited.
                 // (Needs the unrolled head loop: `hl` is a constant here.  The window-major stores do not read vo.)
                 if (hl == HPP - 1) {
                     step();
-                    if (wi < a.n_windows) {
-                        if constexpr (WM) load_x(wb, wy, wx, special, xf, vo);
-                        else load_x(wb, wy, wx, special, xf, von);
-                    }
+                    if (wi < a.n_windows) load_x(wb, wy, wx, special, xf, vo);
                 }
-            }
-            f32x4 sb[3];                                   // score accumulators' initial values (bias rows) of the coming query tile
-            if constexpr ((PF & 4) != 0) {
-#pragma unroll
-                for (int kt = 0; kt < 3; ++kt) sb[kt] = bias_frag(hl, 0, kt);
             }
 
             // ---- attention of this head: 3 q tiles x 3 key tiles ---------------------------------------------------
@@ -418,33 +315,19 @@ qkv_attn_r_kernel(QkvAttnRArgs a) {
             for (int qt = 0; qt < 3; ++qt) {
                 f32x4 s[3];
                 {
-                    if constexpr (!(PF & 4)) {
+                    f32x4 sb[3];                           // score accumulators' initial values (bias rows) of this query tile
 #pragma unroll
-                        for (int kt = 0; kt < 3; ++kt) sb[kt] = bias_frag(hl, qt, kt);
-                    }
+                    for (int kt = 0; kt < 3; ++kt) sb[kt] = bias_frag(hl, qt, kt);
 #pragma unroll
                     for (int kt = 0; kt < 3; ++kt) {
                         f32x4 acc = sb[kt];
                         if constexpr (HD == 16) {
-                            if constexpr (kSplit && !SP && !kSplitK16) {
-                                acc = MFMA_16x16x32(cat8r(kt4[0][kt], zero4), cat8r(qt4[0][qt], zero4), acc);
-                            } else if constexpr (kSplit && !SP) {
-                                // K = 16 is the whole head: v_mfma_f32_16x16x16_f16 takes q and k as they leave the converts (no
-                                // 4-register operands to assemble, ~10 v_mov per head); the shift-region term is a constant over
-                                // every row of these windows
-                                acc = __builtin_amdgcn_mfma_f32_16x16x16f16(kt4[0][kt], qt4[0][qt], acc, 0, 0, 0);
-                            } else {
-                                acc = MFMA_16x16x32(cat8r(kt4[0][kt], rkr[kt]), cat8r(qt4[0][qt], rqr[qt]), acc);
-                            }
+                            acc = MFMA_16x16x32(cat8r(kt4[0][kt], rkr[kt]), cat8r(qt4[0][qt], rqr[qt]), acc);
                         } else {
                             acc = MFMA_16x16x32(cat8r(kt4[0][kt], kt4[1][kt]), cat8r(qt4[0][qt], qt4[1][qt]), acc);
                             if (sp_now) acc = MFMA_16x16x32(cat8r(rkr[kt], zero4), cat8r(rqr[qt], zero4), acc);
                         }
                         s[kt] = acc;
-                    }
-                    if ((PF & 4) && qt + 1 < 3) {           // the next query tile's bias rows travel behind this tile's softmax
-#pragma unroll
-                        for (int kt = 0; kt < 3; ++kt) sb[kt] = bias_frag(hl, qt + 1, kt);
                     }
                 }
                 // 9 real keys per lane: tiles 0 and 1 whole, register 0 of tile 2 (key 32 + grp); registers 1-3 of tile 2 are padding
@@ -483,19 +366,15 @@ qkv_attn_r_kernel(QkvAttnRArgs a) {
                     // of this store cover ONE contiguous 512-byte run (16 tokens x 32 B) instead of sixteen 8-byte pieces 192 B
                     // apart (1.48x write amplification in the r02 counters).  Pairing with the neighbouring head's tile (held
                     // across one trip of the head loop) was measured slower (504 vs 457 us): plain 8-byte stores
-                    if constexpr ((NUNIF_QKV_DIET & 1) != 0) {
-                        // the base is pinned in an SGPR pair (an opaque asm: hipcc otherwise re-associates the sum into 64-bit
-                        // per-lane arithmetic) so that the store is `global_store_dwordx2 v_off, v_data, s[base]`
-                        unsigned long hb = reinterpret_cast<unsigned long>(a.att) + (wm_base + (unsigned)(head * (36 * HD * 2)));
-                        asm("" : "+s"(hb));
-                        typedef __attribute__((address_space(1))) char gchar;        // (an integer -> pointer cast would be a FLAT store)
-                        typedef __attribute__((address_space(1))) f16x4 gf16x4;
-                        unsigned lo = wm_off[qt];
-                        asm("" : "+v"(lo));         // keeps the zero-extension next to the add (hoisted, it becomes a 64-bit VGPR pair)
-                        if (store) *reinterpret_cast<gf16x4 *>(reinterpret_cast<gchar *>(hb) + lo) = ov[0];
-                    } else {
-                        if (store) *reinterpret_cast<f16x4 *>(ab + ((head * 36 + tokc[qt]) * HD + 4 * grp) * 2) = ov[0];
-                    }
+                    // The base is pinned in an SGPR pair (an opaque asm: hipcc otherwise re-associates the sum into 64-bit
+                    // per-lane arithmetic) so that the store is `global_store_dwordx2 v_off, v_data, s[base]`
+                    unsigned long hb = reinterpret_cast<unsigned long>(a.att) + (wm_base + (unsigned)(head * (36 * HD * 2)));
+                    asm("" : "+s"(hb));
+                    typedef __attribute__((address_space(1))) char gchar;        // (an integer -> pointer cast would be a FLAT store)
+                    typedef __attribute__((address_space(1))) f16x4 gf16x4;
+                    unsigned lo = wm_off[qt];
+                    asm("" : "+v"(lo));         // keeps the zero-extension next to the add (hoisted, it becomes a 64-bit VGPR pair)
+                    if (store) *reinterpret_cast<gf16x4 *>(reinterpret_cast<gchar *>(hb) + lo) = ov[0];
                 } else {
                     if (store) *reinterpret_cast<f16x4 *>(ab + (vo[qt] + (unsigned)st_delta) + head * (HD * 2)) = ov[0];
                 }
@@ -503,40 +382,22 @@ qkv_attn_r_kernel(QkvAttnRArgs a) {
             if constexpr (kHeadUnroll > 1) __builtin_amdgcn_sched_barrier(0);   // unrolled heads stay apart: nothing of head h + 1 is scheduled into head h
         }
         };
-        if constexpr (MODE == 1) {
-            run_heads(std::false_type{});
-        } else if constexpr (MODE == 2) {
-            run_heads(std::true_type{});
-        } else if constexpr (kSplit) {
-            if (special) run_heads(std::true_type{}); else run_heads(std::false_type{});
-        } else {
-            run_heads(std::true_type{});
-        }
+        run_heads();
 
-        if constexpr (kEarlyX && !WM) {
-#pragma unroll
-            for (int mt = 0; mt < 3; ++mt) vo[mt] = von[mt];
-        }
         if constexpr (!kEarlyX) {
             step();
             if (wi < a.n_windows) load_x(wb, wy, wx, special, xf, vo);
         }
     }
     };
-    if constexpr (kTwoLoops) {
-        run_windows(std::integral_constant<int, 1>{});
-        if (a.shift > 0) run_windows(std::integral_constant<int, 2>{});
-    } else {
-        run_windows(std::integral_constant<int, 0>{});
-    }
+    run_windows();
 }
 
 int qkv_attn_r_frags(int C) { return 3 * (C / 16) * (C / 32); }
 
 template <int C, int HD, int HPP, int WAVES = 8, bool WM = false>
 static int launch_r(const QkvAttnRArgs &a, int grid, hipStream_t s) {
-    constexpr size_t smem = (size_t)HPP * 3 * (HD / 16) * (C / 32) * 1024 + HPP * kQkvBiasFloatsPerHead * 4 +
-                            (kQkvBiasFragMajor ? (size_t)HPP * 3 * (HD / 16) * 1024 : (size_t)3 * C * 4);
+    constexpr size_t smem = (size_t)HPP * 3 * (HD / 16) * (C / 32) * 1024 + HPP * kQkvBiasFloatsPerHead * 4 + (size_t)3 * C * 4;
     static bool configured = false;
     if (!configured) {
         NUNIF_HIP_CHECK(hipFuncSetAttribute((const void *)qkv_attn_r_kernel<C, HD, HPP, WAVES, WM>,
