@@ -59,6 +59,28 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 #if defined(__HIPCC__)
+#define MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
+
+// two 4-half register pairs as one 8-half MFMA operand
+__device__ __forceinline__ f16x8 cat8(f16x4 lo, f16x4 hi) {
+    return (f16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+}
+
+// global -> LDS without a trip through registers: each lane moves 16 B to LDS[m0 + 16 * lane]; m0 is wave-uniform
+__device__ __forceinline__ void dma16(const void *src, unsigned lds_byte_addr) {
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(lds_byte_addr) : "memory");
+}
+
+// float <-> unsigned key with the same order (negative values flipped whole, others get the sign bit): integer atomicMin /
+// atomicMax and radix selection then work on floats
+__device__ __forceinline__ unsigned int order_key(float v) {
+    const unsigned int b = __float_as_uint(v);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float key_value(unsigned int k) {
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
 // An MFMA accumulator lane (token l&15, lane group g = l>>4) holds channels 4g..4g+3 of a 16-channel tile: 8 bytes of
 // fp16, and a wave-wide store of them touches 16 rows x 32 B — quarter cache lines.  Two v_permlane16_swap turn the
 // chunks of two adjacent tiles (A: channels 4g.., B: channels 16+4g..) into ONE run of 8 consecutive channels per lane,

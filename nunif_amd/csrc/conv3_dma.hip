@@ -38,18 +38,11 @@
 
 namespace nunif {
 
-#define MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
-
 namespace {
 constexpr int kTH = 8, kTW = 32;                        // output patch of a workgroup (4 waves x 2 rows x 32 columns)
 constexpr int kHH = kTH + 2, kHW = kTW + 2;             // halo
 constexpr int kHaloPix = kHH * kHW;                     // 340
 constexpr int kCH = 8;                                  // fragments (KiB) per weight chunk
-
-__device__ __forceinline__ void dma16(const void *src, unsigned lds_byte_addr) {
-    // each lane moves 16 B to LDS[m0 + 16 * lane]; m0 is wave-uniform
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(lds_byte_addr) : "memory");
-}
 }  // namespace
 
 // NTT output tiles in NPASS passes of NT = NTT / NPASS over the SAME halo (64 -> 128: two passes of four tiles; eight tiles x four

@@ -18,8 +18,6 @@
 
 namespace nunif {
 
-#define MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
-
 constexpr int kC3TH = 8, kC3TW = 32;                     // output patch of a workgroup (4 waves x 2 rows x 32 columns)
 constexpr int kC3HH = kC3TH + 2, kC3HW = kC3TW + 2;      // halo
 

@@ -5,10 +5,10 @@
 // blend_size None -> plain overwrite).  State-dict keys are the reference's.
 #include <algorithm>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
+#include "host_weights.h"
 #include "swin_kernels.h"
 
 namespace nunif {
@@ -19,22 +19,6 @@ int launch_stitch(const float *tile_out, float *y, const nunif_tile_grid *g, int
 using namespace nunif;
 
 namespace {
-
-struct HostT { const float *data; std::vector<int64_t> shape; int64_t numel; };
-typedef std::map<std::string, HostT> TMap;
-
-struct Buf {
-    void *p = nullptr; size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return NUNIF_HIP_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        if (hipMalloc(&p, bytes) != hipSuccess) { set_error("hipMalloc(%zu) failed", bytes); return NUNIF_HIP_ENOMEM; }
-        cap = bytes;
-        return NUNIF_HIP_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
 
 struct ConvW { f16 *stream = nullptr; float *bias = nullptr; int N = 0, n_real = 0, Cin = 0, k = 3, stride = 1;
                f16 *gemm_w = nullptr;           // 2x2 stride-2 convs: the same weights in gemm_kernel's [n-tile][k-step] order
@@ -49,7 +33,7 @@ struct C3W { float *w = nullptr, *b = nullptr; int C = 0; f16 *frag = nullptr; }
 
 }  // namespace
 
-struct nunif_cunet {
+struct nunif_cunet : DeviceOwner {
     // kind 0 / 1: CUNet / UpCUNet; 2: waifu2x.vgg_7 (vgg_7.py:6-30: seven 3x3 VALID convs, scale 1, offset 7);
     // 3: waifu2x.upconv_7 (upconv_7.py:6-35: six 3x3 VALID convs + ConvTranspose2d(256, 3, 4, 2, 3), scale 2, offset 14)
     int kind = 0;
@@ -57,13 +41,12 @@ struct nunif_cunet {
     int no_clip = 0;
     int up = 0;                 // 1: UpCUNet (unet1 ends in ConvTranspose2d(64, 3, 4, 2, 3); scale 2, offset 36)
     UpW u1bottom_up;            // that head as a 2x2-window gather GEMM (K = 4*64) with a pixel-shuffle store
-    std::vector<void *> owned;
     // unet1
     C3W u1c1a; ConvW u1c1b, u1down, u1c2a, u1c2b, u1c3, u1bottom; SEW u1se2; UpW u1up;
     // unet2
     C3W u2c1a; ConvW u2c1b, u2down1, u2c2a, u2c2b, u2down2, u2c3a, u2c3b, u2c4a, u2c4b, u2c5, u2bottom;
     SEW u2se2, u2se3, u2se4; UpW u2up3, u2up4;
-    Buf t[12], z1, sums, scale, tile_out;
+    DeviceBuf t[12], z1, sums, scale, tile_out;
     // debug taps (tests only): when on, the map each launch wrote is copied device-side at once (the 12 buffers are reused down the
     // net); the launches themselves are the ones that run with taps off
     struct Tap { std::string name; void *dev; size_t bytes; };
@@ -74,110 +57,62 @@ struct nunif_cunet {
 
 namespace {
 
-int find(const TMap &m, const std::string &key, const HostT **out) {
-    auto it = m.find(key);
-    if (it == m.end()) { set_error("state_dict is missing '%s'", key.c_str()); return NUNIF_HIP_EMISSING; }
-    *out = &it->second;
-    return NUNIF_HIP_OK;
-}
-
-template <typename T>
-int upload(nunif_cunet *h, const std::vector<T> &host, T **dev) {
-    void *p = nullptr;
-    if (hipMalloc(&p, host.size() * sizeof(T)) != hipSuccess) { set_error("hipMalloc failed"); return NUNIF_HIP_ENOMEM; }
-    h->owned.push_back(p);
-    NUNIF_HIP_CHECK(hipMemcpy(p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
-    *dev = reinterpret_cast<T *>(p);
-    return NUNIF_HIP_OK;
-}
-
-int upload_f32(nunif_cunet *h, const HostT *t, float **dev) {
-    std::vector<float> v(t->data, t->data + t->numel);
-    return upload(h, v, dev);
-}
-
 // Conv2d weight [Cout][Cin][k][k] -> MFMA A fragments in [k-step][n-tile] order, reduction index = tap*Cin + ci
 // cin_real < cin: the producer stores its cin_real channels padded with zeros to cin (a multiple of 32)
-int make_conv(nunif_cunet *h, const TMap &m, const std::string &key, int cin, int cout, int k, int stride, ConvW *c,
+int make_conv(nunif_cunet *h, const TensorMap &m, const std::string &key, int cin, int cout, int k, int stride, ConvW *c,
               int cin_real = 0) {
-    const HostT *w, *b;
+    const HostTensor *w, *b;
     int rc;
     if (cin_real <= 0) cin_real = cin;
     if ((rc = find(m, key + ".weight", &w)) || (rc = find(m, key + ".bias", &b))) return rc;
     NUNIF_REQUIRE(w->numel == (int64_t)cout * cin_real * k * k && b->numel == cout, "%s: unexpected shape", key.c_str());
     NUNIF_REQUIRE(cin % 32 == 0, "%s: Cin=%d must be a multiple of 32", key.c_str(), cin);
     const int N = (cout + 15) / 16 * 16, NT = N / 16, KS = k * k * cin / 32;
-    std::vector<f16> stream((size_t)KS * NT * 512 + 8192, (f16)0.0f);
-    for (int ks = 0; ks < KS; ++ks)
-        for (int nt = 0; nt < NT; ++nt)
-            for (int l = 0; l < 64; ++l)
-                for (int j = 0; j < 8; ++j) {
-                    const int n = nt * 16 + (l & 15), kk = ks * 32 + (l >> 4) * 8 + j;
-                    const int tap = kk / cin, ci = kk % cin;
-                    const float v = (n < cout && ci < cin_real) ? w->data[((size_t)n * cin_real + ci) * k * k + tap] : 0.0f;
-                    stream[(((size_t)ks * NT + nt) * 64 + l) * 8 + j] = (f16)v;
-                }
+    const float *wd = w->data;
+    std::vector<f16> stream = pack_ks_nt(cout, N, k * k * cin, [=](int n, int kk) {
+        const int tap = kk / cin, ci = kk % cin;
+        return ci < cin_real ? wd[((size_t)n * cin_real + ci) * k * k + tap] : 0.0f;
+    });
     std::vector<float> bias(N, 0.0f);
     for (int n = 0; n < cout; ++n) bias[n] = b->data[n];
     c->N = N; c->n_real = cout; c->Cin = cin; c->k = k; c->stride = stride;
-    if ((rc = upload(h, stream, &c->stream))) return rc;
+    if ((rc = h->upload(stream, &c->stream))) return rc;
     if (k == 3 && stride == 1 && cin_real == cin && (cin == 128 || cin == 256) && cout > 64 && cout % 64 == 0) {
         for (int sl = 0; sl < cout / 64; ++sl) {
-            std::vector<f16> part((size_t)KS * 4 * 512 + 8192, (f16)0.0f);
-            for (int ks = 0; ks < KS; ++ks)
-                std::copy(stream.begin() + ((size_t)ks * NT + 4 * sl) * 512, stream.begin() + ((size_t)ks * NT + 4 * sl + 4) * 512,
-                          part.begin() + (size_t)ks * 4 * 512);
             f16 *dev = nullptr;
-            if ((rc = upload(h, part, &dev))) return rc;
+            if ((rc = h->upload(stream_slice(stream, KS, NT, 4 * sl, 4), &dev))) return rc;
             c->slice.push_back(dev);
         }
     }
     if (k == 3 && stride == 1 && cin_real == 64 && cin == 64 && cout == 3) {
-        std::vector<f16> hw((size_t)4 * 512 + 8192, (f16)0.0f);
-        for (int nt = 0; nt < 2; ++nt)
-            for (int ks = 0; ks < 2; ++ks)
-                for (int l = 0; l < 64; ++l)
-                    for (int j = 0; j < 8; ++j) {
-                        const int n = nt * 16 + (l & 15), ci = ks * 32 + (l >> 4) * 8 + j, tap = n / 3, co = n % 3;
-                        hw[(((size_t)nt * 2 + ks) * 64 + l) * 8 + j] = n < 27 ? (f16)w->data[((size_t)co * 64 + ci) * 9 + tap] : (f16)0.0f;
-                    }
-        if ((rc = upload(h, hw, &c->head_w))) return rc;
+        // tap-scatter head: row n = 3 tap + co over the 64 input channels
+        if ((rc = h->upload(pack_nt_ks(27, 32, 64, [=](int n, int ci) { return wd[((size_t)(n % 3) * 64 + ci) * 9 + n / 3]; }),
+                            &c->head_w)))
+            return rc;
     }
     if (k == 2 && stride == 2 && cin_real == cin && N == cout && N % 32 == 0) {
         // k = stride: a 2 x 2 gather GEMM (the PatchDown form of gemm_kernel: every input pixel is read exactly once, the token
         // tile's whole K extent sits in registers) instead of the K-looped conv_kernel with its nine-tap machinery
-        std::vector<f16> packed((size_t)N * k * k * cin + 8192, (f16)0.0f);
-        for (int nt = 0; nt < NT; ++nt)
-            for (int ks = 0; ks < KS; ++ks)
-                std::copy(stream.begin() + ((size_t)ks * NT + nt) * 512, stream.begin() + ((size_t)ks * NT + nt + 1) * 512,
-                          packed.begin() + ((size_t)nt * KS + ks) * 512);
-        if ((rc = upload(h, packed, &c->gemm_w))) return rc;
+        if ((rc = h->upload(ks_nt_to_nt_ks(stream, KS, NT), &c->gemm_w))) return rc;
     }
-    return upload(h, bias, &c->bias);
+    return h->upload(bias, &c->bias);
 }
 
 // ConvTranspose2d(cin, cout, 2, 2) weight [cin][cout][2][2] -> Linear cin -> 4*cout with pixel-shuffle column order
 // n = q*cout + co, q = i*2 + j  (gemm_kernel mode 1), fragments in [n-tile][k-step] order
-int make_up(nunif_cunet *h, const TMap &m, const std::string &key, int cin, int cout, UpW *u) {
-    const HostT *w, *b;
+int make_up(nunif_cunet *h, const TensorMap &m, const std::string &key, int cin, int cout, UpW *u) {
+    const HostTensor *w, *b;
     int rc;
     if ((rc = find(m, key + ".weight", &w)) || (rc = find(m, key + ".bias", &b))) return rc;
     NUNIF_REQUIRE(w->numel == (int64_t)cin * cout * 4 && b->numel == cout, "%s: unexpected shape", key.c_str());
-    const int N = 4 * cout, NT = N / 16, KS = cin / 32;
-    std::vector<f16> packed((size_t)N * cin + 8192, (f16)0.0f);
-    for (int nt = 0; nt < NT; ++nt)
-        for (int ks = 0; ks < KS; ++ks)
-            for (int l = 0; l < 64; ++l)
-                for (int j = 0; j < 8; ++j) {
-                    const int n = nt * 16 + (l & 15), ci = ks * 32 + (l >> 4) * 8 + j;
-                    const int q = n / cout, co = n % cout;
-                    packed[(((size_t)nt * KS + ks) * 64 + l) * 8 + j] = (f16)w->data[((size_t)ci * cout + co) * 4 + q];
-                }
+    const int N = 4 * cout;
+    const float *wd = w->data;
+    std::vector<f16> packed = pack_nt_ks(N, N, cin, [=](int n, int ci) { return wd[((size_t)ci * cout + n % cout) * 4 + n / cout]; });
     std::vector<float> bias(N);
     for (int n = 0; n < N; ++n) bias[n] = b->data[n % cout];
     u->N = N; u->K = cin; u->cq = cout;
-    if ((rc = upload(h, packed, &u->w))) return rc;
-    return upload(h, bias, &u->bias);
+    if ((rc = h->upload(packed, &u->w))) return rc;
+    return h->upload(bias, &u->bias);
 }
 
 // ConvTranspose2d(cin, cout, 4, 2, 3), weight [cin][cout][4][4]:  out[oy][ox] = b + sum in[iy][ix] W[ky][kx] over
@@ -185,34 +120,29 @@ int make_up(nunif_cunet *h, const TMap &m, const std::string &key, int cin, int 
 // (2j-1 .. 2j) x (2i-1 .. 2i): window row dy contributes to output row parity a through ky = a + 2 (1 - dy) (same for
 // columns).  So the head is a gather GEMM over the (H-1)^2 windows, K = (dy*2+dx)*cin + ci (gemm_kernel taps with
 // kw = 2), N = co*4 + a*2 + b, stored by gemm_kernel mode 2 with oshift = -1 into the (2H-4)^2 plane.
-int make_deconv4(nunif_cunet *h, const TMap &m, const std::string &key, int cin, int cout, UpW *u) {
-    const HostT *w, *b;
+int make_deconv4(nunif_cunet *h, const TensorMap &m, const std::string &key, int cin, int cout, UpW *u) {
+    const HostTensor *w, *b;
     int rc;
     if ((rc = find(m, key + ".weight", &w)) || (rc = find(m, key + ".bias", &b))) return rc;
     NUNIF_REQUIRE(w->numel == (int64_t)cin * cout * 16 && b->numel == cout, "%s: unexpected shape", key.c_str());
-    const int n_real = 4 * cout, N = (n_real + 15) / 16 * 16, NT = N / 16, K = 4 * cin, KS = K / 32;
-    std::vector<f16> packed((size_t)N * K + 8192, (f16)0.0f);
-    for (int nt = 0; nt < NT; ++nt)
-        for (int ks = 0; ks < KS; ++ks)
-            for (int l = 0; l < 64; ++l)
-                for (int j = 0; j < 8; ++j) {
-                    const int n = nt * 16 + (l & 15), k = ks * 32 + (l >> 4) * 8 + j;
-                    if (n >= n_real) continue;
-                    const int co = n / 4, a = (n >> 1) & 1, bb = n & 1;
-                    const int tap = k / cin, ci = k % cin, dy = tap >> 1, dx = tap & 1;
-                    const int ky = a + 2 * (1 - dy), kx = bb + 2 * (1 - dx);
-                    packed[(((size_t)nt * KS + ks) * 64 + l) * 8 + j] = (f16)w->data[(((size_t)ci * cout + co) * 4 + ky) * 4 + kx];
-                }
+    const int n_real = 4 * cout, N = (n_real + 15) / 16 * 16, K = 4 * cin;
+    const float *wd = w->data;
+    std::vector<f16> packed = pack_nt_ks(n_real, N, K, [=](int n, int k) {
+        const int co = n / 4, a = (n >> 1) & 1, bb = n & 1;
+        const int tap = k / cin, ci = k % cin, dy = tap >> 1, dx = tap & 1;
+        const int ky = a + 2 * (1 - dy), kx = bb + 2 * (1 - dx);
+        return wd[(((size_t)ci * cout + co) * 4 + ky) * 4 + kx];
+    });
     std::vector<float> bias(N, 0.0f);
     for (int n = 0; n < n_real; ++n) bias[n] = b->data[n / 4];
     u->N = N; u->K = K; u->cq = cout;
-    if ((rc = upload(h, packed, &u->w))) return rc;
-    return upload(h, bias, &u->bias);
+    if ((rc = h->upload(packed, &u->w))) return rc;
+    return h->upload(bias, &u->bias);
 }
 
 // cout_pad > cout: the extra output channels get zero weights / bias (LeakyReLU(0) = 0), so the next conv sees Cin % 32 == 0
-int make_c3(nunif_cunet *h, const TMap &m, const std::string &key, int cout, C3W *c, int cout_pad = 0) {
-    const HostT *w, *b;
+int make_c3(nunif_cunet *h, const TensorMap &m, const std::string &key, int cout, C3W *c, int cout_pad = 0) {
+    const HostTensor *w, *b;
     int rc;
     if ((rc = find(m, key + ".weight", &w)) || (rc = find(m, key + ".bias", &b))) return rc;
     NUNIF_REQUIRE(w->numel == (int64_t)cout * 27 && b->numel == cout, "%s: unexpected shape (3 input channels)", key.c_str());
@@ -221,36 +151,32 @@ int make_c3(nunif_cunet *h, const TMap &m, const std::string &key, int cout, C3W
         if (cout % 16 == 0) {
             // the same conv as cout / 16 MFMA A fragments for stem_fused_kernel (swin_stem.hip): row n, k = ci*9 + ky*3 + kx
             // (the weight's own layout), k = 27: the bias (the B operand carries a constant one there), k > 27: zero
-            std::vector<f16> fr((size_t)cout / 16 * 512);
-            for (int nt = 0; nt < cout / 16; ++nt)
-                for (int l = 0; l < 64; ++l)
-                    for (int j = 0; j < 8; ++j) {
-                        const int n = nt * 16 + (l & 15), k = (l >> 4) * 8 + j;
-                        fr[((size_t)nt * 64 + l) * 8 + j] = (f16)(k < 27 ? w->data[(size_t)n * 27 + k] : (k == 27 ? b->data[n] : 0.0f));
-                    }
-            if ((rc = upload(h, fr, &c->frag))) return rc;
+            const float *wd = w->data, *bd = b->data;
+            if ((rc = h->upload(pack_nt_ks(cout, cout, 32, [=](int n, int k) {
+                     return k < 27 ? wd[(size_t)n * 27 + k] : (k == 27 ? bd[n] : 0.0f); }, false, 0), &c->frag)))
+                return rc;
         }
-        if ((rc = upload_f32(h, w, &c->w))) return rc;
-        return upload_f32(h, b, &c->b);
+        if ((rc = h->upload_f32(w, &c->w))) return rc;
+        return h->upload_f32(b, &c->b);
     }
     std::vector<float> wp((size_t)cout_pad * 27, 0.0f), bp(cout_pad, 0.0f);
     std::copy(w->data, w->data + (size_t)cout * 27, wp.begin());
     std::copy(b->data, b->data + cout, bp.begin());
     c->C = cout_pad;
-    if ((rc = upload(h, wp, &c->w))) return rc;
-    return upload(h, bp, &c->b);
+    if ((rc = h->upload(wp, &c->w))) return rc;
+    return h->upload(bp, &c->b);
 }
 
-int make_se(nunif_cunet *h, const TMap &m, const std::string &key, int C, SEW *s) {
-    const HostT *w1, *b1, *w2, *b2;
+int make_se(nunif_cunet *h, const TensorMap &m, const std::string &key, int C, SEW *s) {
+    const HostTensor *w1, *b1, *w2, *b2;
     int rc;
     if ((rc = find(m, key + ".conv1.weight", &w1)) || (rc = find(m, key + ".conv1.bias", &b1)) ||
         (rc = find(m, key + ".conv2.weight", &w2)) || (rc = find(m, key + ".conv2.bias", &b2)))
         return rc;
     NUNIF_REQUIRE(w1->numel == (int64_t)C * C / 8 && w2->numel == (int64_t)C * C / 8, "%s: unexpected shape", key.c_str());
     s->C = C;
-    if ((rc = upload_f32(h, w1, &s->w1)) || (rc = upload_f32(h, b1, &s->b1)) || (rc = upload_f32(h, w2, &s->w2)) ||
-        (rc = upload_f32(h, b2, &s->b2)))
+    if ((rc = h->upload_f32(w1, &s->w1)) || (rc = h->upload_f32(b1, &s->b1)) || (rc = h->upload_f32(w2, &s->w2)) ||
+        (rc = h->upload_f32(b2, &s->b2)))
         return rc;
     return NUNIF_HIP_OK;
 }
@@ -542,19 +468,12 @@ int forward_impl(nunif_cunet *h, const float *x, const float *frame, const nunif
 extern "C" int nunif_hip_cunet_create(const nunif_tensor_desc *tensors, int32_t n_tensors, int32_t no_clip,
                                       nunif_cunet **handle) {
     NUNIF_REQUIRE(tensors && handle && n_tensors > 0, "cunet_create: NULL argument");
-    TMap m;
-    for (int i = 0; i < n_tensors; ++i) {
-        HostT t;
-        t.data = tensors[i].data;
-        t.numel = 1;
-        for (int d = 0; d < tensors[i].ndim; ++d) { t.shape.push_back(tensors[i].shape[d]); t.numel *= tensors[i].shape[d]; }
-        m[tensors[i].name] = t;
-    }
+    TensorMap m = tensor_map(tensors, n_tensors);
     nunif_cunet *h = new nunif_cunet();
     h->no_clip = no_clip;
     int rc = NUNIF_HIP_OK;
     do {
-        const HostT *bw;
+        const HostTensor *bw;
         if (m.count("net.12.weight")) {                  // nn.Sequential key layout of vgg_7 / upconv_7
             bw = &m["net.12.weight"];
             const bool upconv = bw->shape.size() == 4 && bw->shape[2] == 4;
@@ -635,7 +554,7 @@ extern "C" int nunif_hip_cunet_get_tap(nunif_cunet *h, int32_t index, char *name
 extern "C" void nunif_hip_cunet_destroy(nunif_cunet *h) {
     if (!h) return;
     h->clear_taps();
-    for (void *p : h->owned) (void)hipFree(p);
+    h->free_all();
     for (auto &b : h->t) b.release();
     h->z1.release(); h->sums.release(); h->scale.release(); h->tile_out.release();
     delete h;

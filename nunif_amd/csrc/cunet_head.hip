@@ -17,8 +17,6 @@
 
 namespace nunif {
 
-#define MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
-
 template <int TW>                                        // tile = 16 x TW outputs (TW 16 or 32)
 struct HeadGeom {
     static constexpr int kTH = 16, kIH = kTH + 2, kIW = TW + 2, kPix = kIH * kIW;             // 324 / 612 input pixels

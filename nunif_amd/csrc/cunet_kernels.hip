@@ -17,8 +17,6 @@
 
 namespace nunif {
 
-#define MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
-
 // RES = true: the WHOLE weight stream (ksteps x NT fragments <= 80 KiB) is copied into LDS once and the workgroup is persistent
 // over pixel groups — no barrier and no weight latency inside the k loop.  With NT x MF <= 16 MFMAs per k-step the ring's
 // one-chunk prefetch distance (2 k-steps, ~500 cycles) is shorter than an L2 round trip and every chunk boundary stalled

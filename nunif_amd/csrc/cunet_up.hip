@@ -20,8 +20,6 @@
 
 namespace nunif {
 
-#define MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
-
 namespace {
 constexpr int kC = 64;                               // Cin = Cq = 64
 constexpr int kKS = 2;
@@ -33,10 +31,6 @@ constexpr int kD = 4;
 constexpr int kWBytes = kNT * kKS * 1024;            // 32 768
 constexpr int kSmem = kWBytes + kNT * 16 * 4;
 static_assert(kTrips % kD == 0, "the ring slot of a trip is static");
-
-__device__ __forceinline__ void dma16(const void *src, unsigned lds_byte_addr) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(lds_byte_addr) : "memory");
-}
 }  // namespace
 
 template <bool SCALE>

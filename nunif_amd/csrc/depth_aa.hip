@@ -15,23 +15,13 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
+#include "host_weights.h"
 #include "swin_kernels.h"
 
 namespace nunif {
-
-#define MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
-
-__device__ __forceinline__ unsigned int daa_key(float v) {
-    const unsigned int u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float daa_unkey(unsigned int k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 
 __global__ void daa_minmax_init_kernel(unsigned int *mm) { mm[0] = 0xFFFFFFFFu; mm[1] = 0u; }
 
@@ -51,7 +41,7 @@ __global__ void __launch_bounds__(256) daa_minmax_kernel(const float *__restrict
         }
         __syncthreads();
     }
-    if (threadIdx.x == 0) { atomicMin(mm, daa_key(smn[0])); atomicMax(mm + 1, daa_key(smx[0])); }
+    if (threadIdx.x == 0) { atomicMin(mm, order_key(smn[0])); atomicMax(mm + 1, order_key(smx[0])); }
 }
 
 struct DaaInArgs {
@@ -73,7 +63,7 @@ __global__ void __launch_bounds__(256) daa_in_kernel(DaaInArgs a) {
     const long t = id / a.Wq;
     const int yq = (int)(t % a.Hq), b = (int)(t / a.Hq);
     float mn = 0.f, scale = 1.f;
-    if (a.mm) { mn = daa_unkey(a.mm[0]); scale = daa_unkey(a.mm[1]) - mn; }
+    if (a.mm) { mn = key_value(a.mm[0]); scale = key_value(a.mm[1]) - mn; }
     float in[4];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -112,10 +102,6 @@ struct Wmha8Args {
     int B, H, W, n_windows, shift;   // shift: 0 or 4 (zero padding on all four sides)
 };
 
-__device__ __forceinline__ f16x8 cat8d(f16x4 lo, f16x4 hi) {
-    return (f16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-
 __global__ void __launch_bounds__(256) wmha8_kernel(Wmha8Args a) {
     __shared__ __attribute__((aligned(16))) f16x8 wl[8 * 64];
     __shared__ __attribute__((aligned(16))) float tb[64 * 64], bq[96], bp[32];
@@ -126,7 +112,7 @@ __global__ void __launch_bounds__(256) wmha8_kernel(Wmha8Args a) {
     if (tid < 32) bp[tid] = a.bproj[tid];
     __syncthreads();
     const f16x4 zero4 = {(f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f};
-    const f16x8 zero8 = cat8d(zero4, zero4);
+    const f16x8 zero8 = cat8(zero4, zero4);
     const int nwx = (a.W + 2 * a.shift) / 8, nwy = (a.H + 2 * a.shift) / 8;
     const f16x8 *wq = wl + lane;
 
@@ -172,7 +158,7 @@ __global__ void __launch_bounds__(256) wmha8_kernel(Wmha8Args a) {
 #pragma unroll
                 for (int kt = 0; kt < 4; ++kt) {
                     const f32x4 bias = *reinterpret_cast<const f32x4 *>(tb + (16 * qt + r16) * 64 + 16 * kt + 4 * grp);
-                    s[kt] = MFMA_16x16x32(cat8d(k4[kt], zero4), cat8d(q4[qt], zero4), bias);
+                    s[kt] = MFMA_16x16x32(cat8(k4[kt], zero4), cat8(q4[qt], zero4), bias);
                     mx = fmaxf(mx, fmaxf(fmaxf(s[kt][0], s[kt][1]), fmaxf(s[kt][2], s[kt][3])));
                 }
                 mx = fmaxf(mx, __shfl_xor(mx, 16));
@@ -190,8 +176,8 @@ __global__ void __launch_bounds__(256) wmha8_kernel(Wmha8Args a) {
                 sum += __shfl_xor(sum, 32);
                 const float inv = 1.0f / sum;
                 f32x4 o = {0.f, 0.f, 0.f, 0.f};
-                o = MFMA_16x16x32(cat8d(v4[0], v4[1]), cat8d(p[0], p[1]), o);
-                o = MFMA_16x16x32(cat8d(v4[2], v4[3]), cat8d(p[2], p[3]), o);
+                o = MFMA_16x16x32(cat8(v4[0], v4[1]), cat8(p[0], p[1]), o);
+                o = MFMA_16x16x32(cat8(v4[2], v4[3]), cat8(p[2], p[3]), o);
                 o4[hh][qt] = (f16x4){(f16)(o[0] * inv), (f16)(o[1] * inv), (f16)(o[2] * inv), (f16)(o[3] * inv)};
             }
         }
@@ -201,7 +187,7 @@ __global__ void __launch_bounds__(256) wmha8_kernel(Wmha8Args a) {
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) {
                 f32x4 acc = *reinterpret_cast<const f32x4 *>(bp + nt * 16 + 4 * grp);
-                acc = MFMA_16x16x32(wq[(6 + nt) * 64], cat8d(o4[0][mt], o4[1][mt]), acc);
+                acc = MFMA_16x16x32(wq[(6 + nt) * 64], cat8(o4[0][mt], o4[1][mt]), acc);
                 if (inside[mt]) {
                     f16 *px = a.x + pix[mt] * 32 + nt * 16 + 4 * grp;
                     const f16x4 xr = *reinterpret_cast<const f16x4 *>(px);
@@ -239,7 +225,7 @@ __global__ void __launch_bounds__(256) daa_out_kernel(DaaOutArgs a) {
     for (int k = 0; k < 32; ++k) acc = fmaf((float)p[k], sw[k * 4 + n], acc);
     float v = a.src[id];
     if (a.mm) {
-        const float mn = daa_unkey(a.mm[0]), scale = daa_unkey(a.mm[1]) - mn;
+        const float mn = key_value(a.mm[0]), scale = key_value(a.mm[1]) - mn;
         float z = (v - mn) / scale;
         if (z != z) z = 0.f;
         v = (z + acc) * scale + mn;                                   // forward(clamp=False) * scale + min
@@ -255,59 +241,19 @@ __global__ void __launch_bounds__(256) daa_out_kernel(DaaOutArgs a) {
 using namespace nunif;
 
 namespace {
-struct HostT { const float *data; std::vector<int64_t> shape; int64_t numel; };
-typedef std::map<std::string, HostT> TMap;
-int find(const TMap &m, const std::string &key, const HostT **out) {
-    auto it = m.find(key);
-    if (it == m.end()) { set_error("state_dict is missing '%s'", key.c_str()); return NUNIF_HIP_EMISSING; }
-    *out = &it->second;
-    return NUNIF_HIP_OK;
-}
-struct Buf {
-    void *p = nullptr; size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return NUNIF_HIP_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        if (hipMalloc(&p, bytes) != hipSuccess) { set_error("hipMalloc(%zu) failed", bytes); return NUNIF_HIP_ENOMEM; }
-        cap = bytes;
-        return NUNIF_HIP_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
 struct DaaBlock { f16 *wfrag = nullptr, *w1 = nullptr, *w3 = nullptr; float *bqkv = nullptr, *bproj = nullptr, *btab = nullptr, *b1 = nullptr, *b3 = nullptr; };
 double gelu_d(double v) { return 0.5 * v * (1.0 + erf(v * 0.70710678118654752440)); }
-template <typename F>
-void put_frag(std::vector<f16> &dst, size_t frag, int nt, int ks, bool chained, F wt) {
-    for (int l = 0; l < 64; ++l)
-        for (int j = 0; j < 8; ++j) {
-            const int g = l >> 4, n = nt * 16 + (l & 15);
-            const int k = chained ? ks * 32 + (j < 4 ? 4 * g + j : 16 + 4 * g + (j - 4)) : ks * 32 + g * 8 + j;
-            dst[(frag * 64 + l) * 8 + j] = (f16)wt(n, k);
-        }
-}
 }  // namespace
 
-struct nunif_depth_aa {
-    std::vector<void *> owned;
+struct nunif_depth_aa : DeviceOwner {
     float *w_in = nullptr, *w_out = nullptr;
     DaaBlock blk[3];
-    Buf f, t1, t2, mm;
+    DeviceBuf f, t1, t2, mm;
 };
 
 namespace {
-template <typename T>
-int upload(nunif_depth_aa *h, const std::vector<T> &host, T **dev) {
-    void *p = nullptr;
-    if (hipMalloc(&p, host.size() * sizeof(T)) != hipSuccess) { set_error("hipMalloc failed"); return NUNIF_HIP_ENOMEM; }
-    h->owned.push_back(p);
-    NUNIF_HIP_CHECK(hipMemcpy(p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
-    *dev = reinterpret_cast<T *>(p);
-    return NUNIF_HIP_OK;
-}
-
-int make_daa_block(nunif_depth_aa *h, const TMap &m, const std::string &p, DaaBlock *bk) {
-    const HostT *wqkv, *bqkv, *wp, *bp, *w1, *b1, *w3, *b3, *tw0, *tb0, *tw2, *tb2;
+int make_daa_block(nunif_depth_aa *h, const TensorMap &m, const std::string &p, DaaBlock *bk) {
+    const HostTensor *wqkv, *bqkv, *wp, *bp, *w1, *b1, *w3, *b3, *tw0, *tb0, *tw2, *tb2;
     int rc;
     if ((rc = find(m, p + "mha.mha.qkv_proj.weight", &wqkv)) || (rc = find(m, p + "mha.mha.qkv_proj.bias", &bqkv)) ||
         (rc = find(m, p + "mha.mha.head_proj.weight", &wp)) || (rc = find(m, p + "mha.mha.head_proj.bias", &bp)) ||
@@ -331,7 +277,7 @@ int make_daa_block(nunif_depth_aa *h, const TMap &m, const std::string &p, DaaBl
             put_frag(frags, (size_t)6 + nt, nt, 0, true, [=](int n, int k) { return pd[(size_t)n * 32 + k]; });
         std::vector<float> bq(96), bpv(bp->data, bp->data + 32);
         for (int n = 0; n < 96; ++n) bq[n] = bqkv->data[n] * (n < 32 ? qs : 1.0f);
-        if ((rc = upload(h, frags, &bk->wfrag)) || (rc = upload(h, bq, &bk->bqkv)) || (rc = upload(h, bpv, &bk->bproj))) return rc;
+        if ((rc = h->upload(frags, &bk->wfrag)) || (rc = h->upload(bq, &bk->bqkv)) || (rc = h->upload(bpv, &bk->bproj))) return rc;
     }
     {   // WindowScoreBias(8): 64 x 64 table from the to_bias MLP on (dy, dx) / 7
         const int hidden = (int)tb0->numel;
@@ -345,25 +291,21 @@ int make_daa_block(nunif_depth_aa *h, const TMap &m, const std::string &p, DaaBl
                     o += (double)tw2->data[j] * gelu_d((double)tw0->data[j * 2] * dy + (double)tw0->data[j * 2 + 1] * dx + (double)tb0->data[j]);
                 tab[q * 64 + k] = (float)o * 1.4426950408889634f;
             }
-        if ((rc = upload(h, tab, &bk->btab))) return rc;
+        if ((rc = h->upload(tab, &bk->btab))) return rc;
     }
     {
-        std::vector<f16> packed((size_t)32 * 32 + 8192, (f16)0.f);
         const float *wd = w1->data;
-        for (int nt = 0; nt < 2; ++nt) put_frag(packed, (size_t)nt, nt, 0, false, [=](int n, int k) { return wd[(size_t)n * 32 + k]; });
+        std::vector<f16> packed = pack_nt_ks(32, 32, 32, [=](int n, int k) { return wd[(size_t)n * 32 + k]; });
         std::vector<float> bb(b1->data, b1->data + 32);
-        if ((rc = upload(h, packed, &bk->w1)) || (rc = upload(h, bb, &bk->b1))) return rc;
+        if ((rc = h->upload(packed, &bk->w1)) || (rc = h->upload(bb, &bk->b1))) return rc;
     }
     {
-        std::vector<f16> stream((size_t)9 * 2 * 512 + 8192, (f16)0.f);
         const float *wd = w3->data;
-        for (int ks = 0; ks < 9; ++ks)
-            for (int nt = 0; nt < 2; ++nt)
-                put_frag(stream, (size_t)ks * 2 + nt, nt, ks, false, [=](int n, int k) {
-                    const int tap = k / 32, ci = k % 32;
-                    return wd[((size_t)n * 32 + ci) * 9 + tap]; });
+        std::vector<f16> stream = pack_ks_nt(32, 32, 9 * 32, [=](int n, int k) {
+            const int tap = k / 32, ci = k % 32;
+            return wd[((size_t)n * 32 + ci) * 9 + tap]; });
         std::vector<float> bb(b3->data, b3->data + 32);
-        if ((rc = upload(h, stream, &bk->w3)) || (rc = upload(h, bb, &bk->b3))) return rc;
+        if ((rc = h->upload(stream, &bk->w3)) || (rc = h->upload(bb, &bk->b3))) return rc;
     }
     return NUNIF_HIP_OK;
 }
@@ -371,18 +313,11 @@ int make_daa_block(nunif_depth_aa *h, const TMap &m, const std::string &p, DaaBl
 
 extern "C" int nunif_hip_depth_aa_create(const nunif_tensor_desc *tensors, int32_t n_tensors, nunif_depth_aa **handle) {
     NUNIF_REQUIRE(tensors && handle && n_tensors > 0, "depth_aa_create: NULL argument");
-    TMap m;
-    for (int i = 0; i < n_tensors; ++i) {
-        HostT t;
-        t.data = tensors[i].data;
-        t.numel = 1;
-        for (int d = 0; d < tensors[i].ndim; ++d) { t.shape.push_back(tensors[i].shape[d]); t.numel *= tensors[i].shape[d]; }
-        m[tensors[i].name] = t;
-    }
+    const TensorMap m = tensor_map(tensors, n_tensors);
     nunif_depth_aa *h = new nunif_depth_aa();
     int rc = NUNIF_HIP_OK;
     do {
-        const HostT *wi, *bi, *wo, *bo;
+        const HostTensor *wi, *bi, *wo, *bo;
         if ((rc = find(m, "proj_in.weight", &wi)) || (rc = find(m, "proj_in.bias", &bi)) ||
             (rc = find(m, "proj_out.weight", &wo)) || (rc = find(m, "proj_out.bias", &bo)))
             break;
@@ -392,7 +327,7 @@ extern "C" int nunif_hip_depth_aa_create(const nunif_tensor_desc *tensors, int32
         for (int co = 0; co < 32; ++co) win[4 * 32 + co] = bi->data[co];
         for (int k = 0; k < 32; ++k) for (int n = 0; n < 4; ++n) wout[k * 4 + n] = wo->data[n * 32 + k];
         for (int n = 0; n < 4; ++n) wout[32 * 4 + n] = bo->data[n];
-        if ((rc = upload(h, win, &h->w_in)) || (rc = upload(h, wout, &h->w_out))) break;
+        if ((rc = h->upload(win, &h->w_in)) || (rc = h->upload(wout, &h->w_out))) break;
         for (int i = 0; i < 3 && !rc; ++i) rc = make_daa_block(h, m, "blocks." + std::to_string(i) + ".", &h->blk[i]);
     } while (0);
     if (rc) { nunif_hip_depth_aa_destroy(h); return rc; }
@@ -402,7 +337,7 @@ extern "C" int nunif_hip_depth_aa_create(const nunif_tensor_desc *tensors, int32
 
 extern "C" void nunif_hip_depth_aa_destroy(nunif_depth_aa *h) {
     if (!h) return;
-    for (void *p : h->owned) (void)hipFree(p);
+    h->free_all();
     h->f.release(); h->t1.release(); h->t2.release(); h->mm.release();
     delete h;
 }

@@ -30,16 +30,14 @@
 #include <type_traits>
 #include <cmath>
 #include <cstring>
-#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
 
+#include "host_weights.h"
 #include "swin_kernels.h"
 
 namespace nunif {
-
-#define MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
 
 constexpr int kHd = 64, kPatch = 14, kKp = 608;   // 3*14*14 = 588 padded to 19 k-steps
 
@@ -343,26 +341,6 @@ using namespace nunif;
 
 // =====================================================================================================================
 namespace {
-struct HostT { const float *data; std::vector<int64_t> shape; int64_t numel; };
-typedef std::map<std::string, HostT> TMap;
-int find(const TMap &m, const std::string &key, const HostT **out) {
-    auto it = m.find(key);
-    if (it == m.end()) { set_error("state_dict is missing '%s'", key.c_str()); return NUNIF_HIP_EMISSING; }
-    *out = &it->second;
-    return NUNIF_HIP_OK;
-}
-struct Buf {
-    void *p = nullptr; size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return NUNIF_HIP_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        if (hipMalloc(&p, bytes) != hipSuccess) { set_error("hipMalloc(%zu) failed", bytes); return NUNIF_HIP_ENOMEM; }
-        cap = bytes;
-        return NUNIF_HIP_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
 struct Lin { f16 *w = nullptr; float *b = nullptr; int N = 0, K = 0; float *ws = nullptr; };     // gemm_kernel packing [nt][ks]; ws: row sums (LayerNorm-folded Linears)
 struct Cnv { f16 *w = nullptr; float *b = nullptr; int N = 0, Cin = 0, k = 3, cmaj = 0; };     // conv_kernel stream [ks][nt]
 struct Blk { float *g1, *b1, *g2, *b2; Lin qkv, proj, fc1, fc2[4], fc2_full, qkv_ln, fc1_ln; int n_fc2; f16 *fc2c = nullptr; };   // fc2c: fc2_full in the chained k order (depth_mlp.hip)   // *_ln: norm1 / norm2 folded in (ViT-S)   // fc2 (K = 4 D) = 2 or 4 GEMMs of K = 768 / 1024
@@ -371,7 +349,7 @@ struct Fus { Rcu r1, r2; Lin out; };
 // Video-Depth-Anything's temporal modules (depth_temporal.hip): a temporal attention block = LayerNorm + [Wq | Wk | Wv] (no bias, Wq
 // scaled by hd^-1/2 log2 e) + to_out, the three position tables, the K0 / V0 ring caches of the window; a module = GroupNorm,
 // proj_in, two attention blocks, GEGLU feed-forward (ff1: C -> 8 C, ff2: 4 C -> C), proj_out
-struct TAtt { Lin qkv, out; float *g = nullptr, *b = nullptr, *pq = nullptr, *pk = nullptr, *pv = nullptr; Buf kc, vc; };
+struct TAtt { Lin qkv, out; float *g = nullptr, *b = nullptr, *pq = nullptr, *pk = nullptr, *pv = nullptr; DeviceBuf kc, vc; };
 struct TMod { int C = 0; float *gn_g = nullptr, *gn_b = nullptr, *ff_g = nullptr, *ff_b = nullptr; Lin proj_in, proj_out, ff1, ff2; TAtt at[2]; };
 constexpr int kTLen = 32;                // temporal_max_len: the attention window (this frame + 31 cached)
 }  // namespace
@@ -415,19 +393,18 @@ struct SplitLease {
 };
 }  // namespace
 
-struct nunif_depth_anything {
-    std::vector<void *> owned;
+struct nunif_depth_anything : DeviceOwner {
     int D = 384, heads = 6, depth = 12, taps[4] = {2, 5, 8, 11};
     int OC[4] = {48, 96, 192, 384}, OCP[4] = {64, 96, 192, 384}, feat_ch = 64;
     float max_depth = 0.f;                 // > 0: metric head (Sigmoid * max_depth)
     Lin patch; float *cls = nullptr, *norm_g = nullptr, *norm_b = nullptr;
     std::vector<Blk> blk;
     Lin proj[4], rs0, rs1, rs3g; std::vector<Cnv> rs3; Cnv rn[4]; Fus fus[4]; Cnv oc1, oc2; float *w_final = nullptr;
-    Buf a_col, pe, t, y, qkv, att, hid, lnstats, mlp_flags, feat[4], rnb[4], m1, m2, m3, m4, m5, part, col;
+    DeviceBuf a_col, pe, t, y, qkv, att, hid, lnstats, mlp_flags, feat[4], rnb[4], m1, m2, m3, m4, m5, part, col;
     // the reassemble branch of tap k (project -> resize -> layer_rn conv) on a stream of its own, beside the encoder layers that
     // follow the tap: per-branch temporaries, fork / join events (forward())
-    Buf bm1[4], bm2[4], bpart[4];
-    Buf bt1[3], br1[3];               // RCU1 of refinenets 1-3 beside the encoder: conv1's map, RCU1(skip) (forward())
+    DeviceBuf bm1[4], bm2[4], bpart[4];
+    DeviceBuf bt1[3], br1[3];               // RCU1 of refinenets 1-3 beside the encoder: conv1's map, RCU1(skip) (forward())
     hipStream_t side[3] = {nullptr, nullptr, nullptr};
     hipEvent_t ev_fork[3] = {nullptr, nullptr, nullptr}, ev_join[3] = {nullptr, nullptr, nullptr};
     // Video-Depth-Anything (streaming): four temporal modules (on layer_3, layer_4, path_4, path_3) and the state of the window —
@@ -436,71 +413,46 @@ struct nunif_depth_anything {
     bool temporal = false;
     TMod tm[4];
     int t_len = 0, t_start = 0, t_P[4] = {0, 0, 0, 0};
-    Buf ta, th, tqkv, tatt, thid, tgg, tpart;
+    DeviceBuf ta, th, tqkv, tatt, thid, tgg, tpart;
 };
 
 namespace {
-template <typename T>
-int upload(nunif_depth_anything *h, const std::vector<T> &host, T **dev) {
-    void *p = nullptr;
-    if (hipMalloc(&p, host.size() * sizeof(T)) != hipSuccess) { set_error("hipMalloc failed"); return NUNIF_HIP_ENOMEM; }
-    h->owned.push_back(p);
-    NUNIF_HIP_CHECK(hipMemcpy(p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
-    *dev = reinterpret_cast<T *>(p);
-    return NUNIF_HIP_OK;
-}
-int up_f32(nunif_depth_anything *h, const HostT *t, float **dev) {
-    std::vector<float> v(t->data, t->data + t->numel);
-    return upload(h, v, dev);
-}
-template <typename F>
-void put_frag(std::vector<f16> &dst, size_t frag, int nt, int ks, F wt) {
-    for (int l = 0; l < 64; ++l)
-        for (int j = 0; j < 8; ++j)
-            dst[(frag * 64 + l) * 8 + j] = (f16)wt(nt * 16 + (l & 15), ks * 32 + (l >> 4) * 8 + j);
-}
 // Linear / 1x1 / pixel-shuffle GEMM: W'(n, k) given by wt (zero outside the real range), N and K already padded
 template <typename F, typename G>
 int make_lin(nunif_depth_anything *h, int N, int K, F wt, G bias, Lin *L) {
-    const int NT = N / 16, KS = K / 32;
-    std::vector<f16> packed((size_t)N * K + 8192, (f16)0.f);
-    for (int nt = 0; nt < NT; ++nt)
-        for (int ks = 0; ks < KS; ++ks) put_frag(packed, (size_t)nt * KS + ks, nt, ks, wt);
+    std::vector<f16> packed = pack_nt_ks(N, N, K, wt);
     std::vector<float> b(N);
     for (int n = 0; n < N; ++n) b[n] = bias(n);
     L->N = N; L->K = K;
-    int rc = upload(h, packed, &L->w);
-    return rc ? rc : upload(h, b, &L->b);
+    int rc = h->upload(packed, &L->w);
+    return rc ? rc : h->upload(b, &L->b);
 }
 // k x k conv, stream [ks][nt], reduction index = tap*Cin + ci (Cin padded), wt(n, tap, ci)
 template <typename F, typename G>
 int make_cnv(nunif_depth_anything *h, int N, int Cin, int k, F wt, G bias, Cnv *C, int cmaj = 0) {
     const int NT = N / 16, KS = k * k * Cin / 32;
-    std::vector<f16> stream((size_t)KS * NT * 512 + 8192, (f16)0.f);
+    std::vector<f16> stream;
     if (cmaj) {
         // chunk-major (conv3_lds_cm_kernel): [chunk of `cmaj` channels][tap][32-channel half][n-tile]
+        stream.assign((size_t)KS * NT * kFragHalfs + kRingPadHalfs, (f16)0.f);
         size_t frag = 0;
         for (int q = 0; q < Cin / cmaj; ++q)
             for (int tap = 0; tap < k * k; ++tap)
                 for (int c = 0; c < cmaj / 32; ++c)
                     for (int nt = 0; nt < NT; ++nt, ++frag)
-                        for (int l = 0; l < 64; ++l)
-                            for (int j = 0; j < 8; ++j)
-                                stream[(frag * 64 + l) * 8 + j] = (f16)wt(nt * 16 + (l & 15), tap, q * cmaj + c * 32 + (l >> 4) * 8 + j);
+                        put_frag(stream, frag, nt, c, false, [&](int n, int kk) { return wt(n, tap, q * cmaj + kk); });
     } else {
-        for (int ks = 0; ks < KS; ++ks)
-            for (int nt = 0; nt < NT; ++nt)
-                put_frag(stream, (size_t)ks * NT + nt, nt, ks, [&](int n, int kk) { return wt(n, kk / Cin, kk % Cin); });
+        stream = pack_ks_nt(N, N, k * k * Cin, [&](int n, int kk) { return wt(n, kk / Cin, kk % Cin); });
     }
     std::vector<float> b(N);
     for (int n = 0; n < N; ++n) b[n] = bias(n);
     C->N = N; C->Cin = Cin; C->k = k; C->cmaj = cmaj;
-    int rc = upload(h, stream, &C->w);
-    return rc ? rc : upload(h, b, &C->b);
+    int rc = h->upload(stream, &C->w);
+    return rc ? rc : h->upload(b, &C->b);
 }
-int conv_from(nunif_depth_anything *h, const TMap &m, const std::string &key, int cout, int cin, int cin_pad, int k, bool has_bias,
+int conv_from(nunif_depth_anything *h, const TensorMap &m, const std::string &key, int cout, int cin, int cin_pad, int k, bool has_bias,
               Cnv *C, int cmaj = 0) {
-    const HostT *w, *b = nullptr;
+    const HostTensor *w, *b = nullptr;
     int rc;
     if ((rc = find(m, key + ".weight", &w)) || (has_bias && (rc = find(m, key + ".bias", &b)))) return rc;
     NUNIF_REQUIRE(w->numel == (int64_t)cout * cin * k * k, "%s: unexpected shape", key.c_str());
@@ -561,20 +513,13 @@ int launch_da_layernorm(const f16 *x, const float *g, const float *b, f16 *y, lo
 extern "C" int nunif_hip_depth_anything_create_ex(const nunif_tensor_desc *tensors, int32_t n_tensors, const int32_t *taps,
                                                   float max_depth, nunif_depth_anything **handle) {
     NUNIF_REQUIRE(tensors && handle && n_tensors > 0, "depth_anything_create: NULL argument");
-    TMap m;
-    for (int i = 0; i < n_tensors; ++i) {
-        HostT t;
-        t.data = tensors[i].data;
-        t.numel = 1;
-        for (int d = 0; d < tensors[i].ndim; ++d) { t.shape.push_back(tensors[i].shape[d]); t.numel *= tensors[i].shape[d]; }
-        m[tensors[i].name] = t;
-    }
+    const TensorMap m = tensor_map(tensors, n_tensors);
     nunif_depth_anything *h = new nunif_depth_anything();
     h->max_depth = max_depth > 0.f ? max_depth : 0.f;
     int rc = NUNIF_HIP_OK;
     do {
         const std::string P = "pretrained.", H = "depth_head.";
-        const HostT *w, *b, *t1, *t2;
+        const HostTensor *w, *b, *t1, *t2;
         if ((rc = find(m, P + "patch_embed.proj.weight", &w)) || (rc = find(m, P + "patch_embed.proj.bias", &b))) break;
         const int kD = (int)b->numel;
         if ((kD != 384 && kD != 768 && kD != 1024) || w->numel != (int64_t)kD * 588) {
@@ -599,9 +544,9 @@ extern "C" int nunif_hip_depth_anything_create_ex(const nunif_tensor_desc *tenso
             if ((rc = make_lin(h, kD, kKp, [=](int n, int k) { return k < 588 ? wd[(size_t)n * 588 + k] : 0.f; },
                                [=](int n) { return bd[n]; }, &h->patch))) break;
         }
-        if ((rc = find(m, P + "cls_token", &t1)) || (rc = up_f32(h, t1, &h->cls))) break;
-        if ((rc = find(m, P + "norm.weight", &t1)) || (rc = find(m, P + "norm.bias", &t2)) || (rc = up_f32(h, t1, &h->norm_g)) ||
-            (rc = up_f32(h, t2, &h->norm_b)))
+        if ((rc = find(m, P + "cls_token", &t1)) || (rc = h->upload_f32(t1, &h->cls))) break;
+        if ((rc = find(m, P + "norm.weight", &t1)) || (rc = find(m, P + "norm.bias", &t2)) || (rc = h->upload_f32(t1, &h->norm_g)) ||
+            (rc = h->upload_f32(t2, &h->norm_b)))
             break;
         const float qs = (1.0f / sqrtf((float)kHd)) * 1.4426950408889634f;
         h->blk.resize(depth);
@@ -611,7 +556,7 @@ extern "C" int nunif_hip_depth_anything_create_ex(const nunif_tensor_desc *tenso
         for (int i = 0; i < depth && !rc; ++i) {
             const std::string bp = P + "blocks." + std::to_string(i) + ".";
             Blk &bk = h->blk[i];
-            const HostT *g1, *b1, *g2, *b2, *wq, *bq, *wp, *bpj, *w1, *bb1, *w2, *bb2, *ls1, *ls2;
+            const HostTensor *g1, *b1, *g2, *b2, *wq, *bq, *wp, *bpj, *w1, *bb1, *w2, *bb2, *ls1, *ls2;
             if ((rc = find(m, bp + "norm1.weight", &g1)) || (rc = find(m, bp + "norm1.bias", &b1)) ||
                 (rc = find(m, bp + "norm2.weight", &g2)) || (rc = find(m, bp + "norm2.bias", &b2)) ||
                 (rc = find(m, bp + "attn.qkv.weight", &wq)) || (rc = find(m, bp + "attn.qkv.bias", &bq)) ||
@@ -623,7 +568,7 @@ extern "C" int nunif_hip_depth_anything_create_ex(const nunif_tensor_desc *tenso
             if (wq->numel != (int64_t)3 * kD * kD || w1->numel != (int64_t)4 * kD * kD || w2->numel != (int64_t)4 * kD * kD) {
                 set_error("%s: unexpected shapes for embed %d", bp.c_str(), kD); rc = NUNIF_HIP_EINVAL; break;
             }
-            if ((rc = up_f32(h, g1, &bk.g1)) || (rc = up_f32(h, b1, &bk.b1)) || (rc = up_f32(h, g2, &bk.g2)) || (rc = up_f32(h, b2, &bk.b2))) break;
+            if ((rc = h->upload_f32(g1, &bk.g1)) || (rc = h->upload_f32(b1, &bk.b1)) || (rc = h->upload_f32(g2, &bk.g2)) || (rc = h->upload_f32(b2, &bk.b2))) break;
             const float *d;
             const float *e;
             d = wq->data; e = bq->data;
@@ -653,7 +598,7 @@ extern "C" int nunif_hip_depth_anything_create_ex(const nunif_tensor_desc *tenso
                         for (int k = 0; k < kD; ++k) acc += (double)(float)(f16)(w[(size_t)n * kD + k] * ga[k] * (n < kD ? scale_upto : 1.f));
                         ws[n] = (float)acc;
                     }
-                    return upload(h, ws, &L->ws);
+                    return h->upload(ws, &L->ws);
                 };
                 if ((rc = fold(wq->data, bq->data, g1->data, b1->data, 3 * kD, qs, &bk.qkv_ln))) break;
                 if ((rc = fold(w1->data, bb1->data, g2->data, b2->data, 4 * kD, 1.f, &bk.fc1_ln))) break;
@@ -671,16 +616,12 @@ extern "C" int nunif_hip_depth_anything_create_ex(const nunif_tensor_desc *tenso
                         // (tile 2 ks) and 32 ks + 16 + 4 g + 0..3 (tile 2 ks + 1).  Fragment order [ks / 4][tile][ks % 4]: the
                         // kernel's 24 concurrent streams then sit on different L2 channels (depth_mlp.hip)
                         const int NT = kD / 16, KS = 4 * kD / 32;
-                        std::vector<f16> pc((size_t)NT * KS * 512 + 8192, (f16)0.f);
+                        std::vector<f16> pc((size_t)NT * KS * kFragHalfs + kRingPadHalfs, (f16)0.f);
                         for (int nt = 0; nt < NT; ++nt)
                             for (int ks = 0; ks < KS; ++ks)
-                                for (int l = 0; l < 64; ++l)
-                                    for (int j = 0; j < 8; ++j) {
-                                        const int g = l >> 4, n = nt * 16 + (l & 15);
-                                        const int k = ks * 32 + (j < 4 ? 4 * g + j : 16 + 4 * g + (j - 4));
-                                        pc[((((size_t)(ks >> 2) * NT + nt) * 4 + (ks & 3)) * 64 + l) * 8 + j] = (f16)(wd[(size_t)n * 4 * kD + k] * ls[n]);
-                                    }
-                        rc = upload(h, pc, &bk.fc2c);
+                                put_frag(pc, ((size_t)(ks >> 2) * NT + nt) * 4 + (ks & 3), nt, ks, true,
+                                         [=](int n, int k) { return wd[(size_t)n * 4 * kD + k] * ls[n]; });
+                        rc = h->upload(pc, &bk.fc2c);
                     }
                 }
                 for (int q = 0; q < bk.n_fc2 && !rc; ++q)
@@ -691,13 +632,13 @@ extern "C" int nunif_hip_depth_anything_create_ex(const nunif_tensor_desc *tenso
         }
         if (rc) break;
         // ---- DPT head.  out_channels from projects.{i}, fusion width from layer1_rn; channel counts are stored padded to 32
-        const HostT *rnw;
+        const HostTensor *rnw;
         if ((rc = find(m, H + "scratch.layer1_rn.weight", &rnw))) break;
         const int F = (int)rnw->shape[0];
         if (F != 64 && F != 128 && F != 256) { set_error("depth_anything: DPT features %d unsupported (64, 128, 256)", F); rc = NUNIF_HIP_EUNSUPPORTED; break; }
         h->feat_ch = F;
         for (int i = 0; i < 4 && !rc; ++i) {
-            const HostT *pw, *pb;
+            const HostTensor *pw, *pb;
             if ((rc = find(m, H + "projects." + std::to_string(i) + ".weight", &pw)) ||
                 (rc = find(m, H + "projects." + std::to_string(i) + ".bias", &pb)))
                 break;
@@ -758,7 +699,7 @@ extern "C" int nunif_hip_depth_anything_create_ex(const nunif_tensor_desc *tenso
                 (rc = conv_from(h, m, r + "resConfUnit2.conv1", F, F, F, 3, true, &f.r2.c1)) ||
                 (rc = conv_from(h, m, r + "resConfUnit2.conv2", F, F, F, 3, true, &f.r2.c2)))
                 break;
-            const HostT *ow, *ob;
+            const HostTensor *ow, *ob;
             if ((rc = find(m, r + "out_conv.weight", &ow)) || (rc = find(m, r + "out_conv.bias", &ob))) break;
             const float *wd = ow->data, *bd = ob->data;
             rc = make_lin(h, F, F, [=](int n, int kk) { return wd[(size_t)n * F + kk]; }, [=](int n) { return bd[n]; }, &f.out);
@@ -771,7 +712,7 @@ extern "C" int nunif_hip_depth_anything_create_ex(const nunif_tensor_desc *tenso
         std::vector<float> wf(33);
         for (int k = 0; k < 32; ++k) wf[k] = w->data[k];
         wf[32] = b->data[0];
-        if ((rc = upload(h, wf, &h->w_final))) break;
+        if ((rc = h->upload(wf, &h->w_final))) break;
         // ---- Video-Depth-Anything: head.motion_modules.{0..3} (published key layout; the caller maps `head.` to `depth_head.`)
         if (m.find(H + "motion_modules.0.temporal_transformer.proj_in.weight") == m.end()) break;
         h->temporal = true;
@@ -782,7 +723,7 @@ extern "C" int nunif_hip_depth_anything_create_ex(const nunif_tensor_desc *tenso
             tmod.C = C;
             if (C % 64 || hd % 8) { set_error("motion_modules.%d: %d channels unsupported (a multiple of 64)", i, C); rc = NUNIF_HIP_EUNSUPPORTED; break; }
             const std::string T = H + "motion_modules." + std::to_string(i) + ".temporal_transformer.", B0 = T + "transformer_blocks.0.";
-            const HostT *g1, *b1, *wi, *bi, *wo, *bo, *fg, *fb, *w1, *bb1, *w2, *bb2;
+            const HostTensor *g1, *b1, *wi, *bi, *wo, *bo, *fg, *fb, *w1, *bb1, *w2, *bb2;
             if ((rc = find(m, T + "norm.weight", &g1)) || (rc = find(m, T + "norm.bias", &b1)) ||
                 (rc = find(m, T + "proj_in.weight", &wi)) || (rc = find(m, T + "proj_in.bias", &bi)) ||
                 (rc = find(m, T + "proj_out.weight", &wo)) || (rc = find(m, T + "proj_out.bias", &bo)) ||
@@ -794,10 +735,10 @@ extern "C" int nunif_hip_depth_anything_create_ex(const nunif_tensor_desc *tenso
                 w2->numel != (int64_t)4 * C * C) {
                 set_error("motion_modules.%d: unexpected shapes for %d channels", i, C); rc = NUNIF_HIP_EINVAL; break;
             }
-            if ((rc = up_f32(h, g1, &tmod.gn_g)) || (rc = up_f32(h, b1, &tmod.gn_b)) || (rc = up_f32(h, fg, &tmod.ff_g)) ||
-                (rc = up_f32(h, fb, &tmod.ff_b)))
+            if ((rc = h->upload_f32(g1, &tmod.gn_g)) || (rc = h->upload_f32(b1, &tmod.gn_b)) || (rc = h->upload_f32(fg, &tmod.ff_g)) ||
+                (rc = h->upload_f32(fb, &tmod.ff_b)))
                 break;
-            auto plain = [&](const HostT *w, const HostT *b, int N, int K, Lin *L) {
+            auto plain = [&](const HostTensor *w, const HostTensor *b, int N, int K, Lin *L) {
                 const float *wd = w->data, *bd = b ? b->data : nullptr;
                 return make_lin(h, N, K, [=](int n, int k) { return wd[(size_t)n * K + k]; }, [=](int n) { return bd ? bd[n] : 0.f; }, L);
             };
@@ -808,7 +749,7 @@ extern "C" int nunif_hip_depth_anything_create_ex(const nunif_tensor_desc *tenso
             for (int a = 0; a < 2 && !rc; ++a) {
                 TAtt &at = tmod.at[a];
                 const std::string A = B0 + "attention_blocks." + std::to_string(a) + ".";
-                const HostT *ng, *nb, *wq, *wk, *wv, *wo2, *bo2;
+                const HostTensor *ng, *nb, *wq, *wk, *wv, *wo2, *bo2;
                 if ((rc = find(m, B0 + "norms." + std::to_string(a) + ".weight", &ng)) ||
                     (rc = find(m, B0 + "norms." + std::to_string(a) + ".bias", &nb)) || (rc = find(m, A + "to_q.weight", &wq)) ||
                     (rc = find(m, A + "to_k.weight", &wk)) || (rc = find(m, A + "to_v.weight", &wv)) ||
@@ -817,7 +758,7 @@ extern "C" int nunif_hip_depth_anything_create_ex(const nunif_tensor_desc *tenso
                 if (wq->numel != (int64_t)C * C || wk->numel != (int64_t)C * C || wv->numel != (int64_t)C * C || wo2->numel != (int64_t)C * C) {
                     set_error("%s: unexpected shapes for %d channels", A.c_str(), C); rc = NUNIF_HIP_EINVAL; break;
                 }
-                if ((rc = up_f32(h, ng, &at.g)) || (rc = up_f32(h, nb, &at.b)) || (rc = plain(wo2, bo2, C, C, &at.out))) break;
+                if ((rc = h->upload_f32(ng, &at.g)) || (rc = h->upload_f32(nb, &at.b)) || (rc = plain(wo2, bo2, C, C, &at.out))) break;
                 const float *q = wq->data, *k = wk->data, *v = wv->data;
                 if ((rc = make_lin(h, 3 * C, C, [=](int n, int kk) {
                         return n < C ? q[(size_t)n * C + kk] * qs : n < 2 * C ? k[(size_t)(n - C) * C + kk] : v[(size_t)(n - 2 * C) * C + kk]; },
@@ -852,7 +793,7 @@ extern "C" int nunif_hip_depth_anything_create_ex(const nunif_tensor_desc *tenso
                         tk[(size_t)j * C + n] = (float)ak;
                         tv[(size_t)j * C + n] = (float)av;
                     }
-                if ((rc = upload(h, tq, &at.pq)) || (rc = upload(h, tk, &at.pk)) || (rc = upload(h, tv, &at.pv))) break;
+                if ((rc = h->upload(tq, &at.pq)) || (rc = h->upload(tk, &at.pk)) || (rc = h->upload(tv, &at.pv))) break;
             }
         }
     } while (0);
@@ -868,15 +809,15 @@ extern "C" int nunif_hip_depth_anything_create(const nunif_tensor_desc *tensors,
 
 extern "C" void nunif_hip_depth_anything_destroy(nunif_depth_anything *h) {
     if (!h) return;
-    for (void *p : h->owned) (void)hipFree(p);
-    Buf *bufs[] = {&h->a_col, &h->pe, &h->t, &h->y, &h->qkv, &h->att, &h->hid, &h->lnstats, &h->mlp_flags, &h->feat[0], &h->feat[1], &h->feat[2],
+    h->free_all();
+    DeviceBuf *bufs[] = {&h->a_col, &h->pe, &h->t, &h->y, &h->qkv, &h->att, &h->hid, &h->lnstats, &h->mlp_flags, &h->feat[0], &h->feat[1], &h->feat[2],
                    &h->feat[3], &h->rnb[0], &h->rnb[1], &h->rnb[2], &h->rnb[3], &h->m1, &h->m2, &h->m3, &h->m4, &h->m5, &h->part, &h->col};
-    for (Buf *b : bufs) b->release();
+    for (DeviceBuf *b : bufs) b->release();
     for (int i = 0; i < 4; ++i) { h->bm1[i].release(); h->bm2[i].release(); h->bpart[i].release(); }
     for (int i = 0; i < 3; ++i) { h->bt1[i].release(); h->br1[i].release(); }
     for (TMod &tmod : h->tm)
         for (TAtt &at : tmod.at) { at.kc.release(); at.vc.release(); }
-    for (Buf *b : {&h->ta, &h->th, &h->tqkv, &h->tatt, &h->thid, &h->tgg, &h->tpart}) b->release();
+    for (DeviceBuf *b : {&h->ta, &h->th, &h->tqkv, &h->tatt, &h->thid, &h->tgg, &h->tpart}) b->release();
     for (int i = 0; i < 3; ++i) {
         if (h->side[i]) (void)hipStreamDestroy(h->side[i]);
         if (h->ev_fork[i]) (void)hipEventDestroy(h->ev_fork[i]);

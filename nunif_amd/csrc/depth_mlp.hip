@@ -29,8 +29,6 @@
 
 namespace nunif {
 
-#define MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
-
 namespace {
 constexpr int kD = 384, kH = 1536;
 constexpr int kKS1 = kD / 32;            // 12 k-steps of fc1

@@ -35,11 +35,6 @@ struct FwdWarpArgs {
     double shift_d;
 };
 
-__device__ __forceinline__ unsigned int order_key(float v) {
-    const unsigned int b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
 // weights / targets of source column xs (padded coordinates) for eye sign sgn (+1 left, -1 right)
 __device__ __forceinline__ void bilinear_target(float depth, float sgn, float shift_size, float shift_conv, int xs,
                                                 int Wp, int &fl, int &ce, float &fw, float &cw) {

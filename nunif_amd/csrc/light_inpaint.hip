@@ -16,10 +16,10 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
+#include "host_weights.h"
 #include "swin_kernels.h"
 
 namespace nunif {
@@ -423,29 +423,6 @@ using namespace nunif;
 // =====================================================================================================================
 namespace {
 
-struct HostT { const float *data; std::vector<int64_t> shape; int64_t numel; };
-typedef std::map<std::string, HostT> TMap;
-
-int find(const TMap &m, const std::string &key, const HostT **out) {
-    auto it = m.find(key);
-    if (it == m.end()) { set_error("state_dict is missing '%s'", key.c_str()); return NUNIF_HIP_EMISSING; }
-    *out = &it->second;
-    return NUNIF_HIP_OK;
-}
-
-struct Buf {
-    void *p = nullptr; size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return NUNIF_HIP_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        if (hipMalloc(&p, bytes) != hipSuccess) { set_error("hipMalloc(%zu) failed", bytes); return NUNIF_HIP_ENOMEM; }
-        cap = bytes;
-        return NUNIF_HIP_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-
 struct Lin { f16 *w = nullptr; float *bias = nullptr; int N = 0, K = 0; };                 // gemm_kernel packing [nt][ks]
 struct Conv3 {                                                  // conv_kernel stream [ks][nt]
     f16 *stream = nullptr; float *bias = nullptr; int N = 0, n_real = 0, Cin = 0;
@@ -464,8 +441,7 @@ struct GBlock {
 
 }  // namespace
 
-struct nunif_light_inpaint {
-    std::vector<void *> owned;
+struct nunif_light_inpaint : DeviceOwner {
     f16 *mask_bias = nullptr;
     Lin patch, down, up;
     // video = inpaint.light_video_inpaint_v1: patch slope 0.1, enc1 unshifted, enc2 = [2-D, temporal, 2-D, temporal, 2-D] with
@@ -476,82 +452,55 @@ struct nunif_light_inpaint {
     Conv3 to_image;
     Lin to_image1;
     Gauss15 gauss;
-    Buf x1, x2, a, pi, vt, st, g, po, y, z, ti, mtok, mf0, mf1, mf2, hard, soft;
+    DeviceBuf x1, x2, a, pi, vt, st, g, po, y, z, ti, mtok, mf0, mf1, mf2, hard, soft;
 };
 
 namespace {
 
-template <typename T>
-int upload(nunif_light_inpaint *h, const std::vector<T> &host, T **dev) {
-    void *p = nullptr;
-    if (hipMalloc(&p, host.size() * sizeof(T)) != hipSuccess) { set_error("hipMalloc failed"); return NUNIF_HIP_ENOMEM; }
-    h->owned.push_back(p);
-    NUNIF_HIP_CHECK(hipMemcpy(p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
-    *dev = reinterpret_cast<T *>(p);
-    return NUNIF_HIP_OK;
-}
-
-// W[n][k] (n < n_real, k < K) -> MFMA A fragments in [n-tile][k-step] order (+ 16 KiB of zeros for the ring prefetch)
+// W[n][k] (n < n_real, k < K) -> MFMA A fragments in [n-tile][k-step] order
 template <typename F>
 int make_lin(nunif_light_inpaint *h, int n_real, int K, F wt, const std::vector<float> &bias, Lin *L) {
-    const int N = (n_real + 31) / 32 * 32, KS = K / 32;
-    std::vector<f16> packed((size_t)N * K + 8192, (f16)0.f);
-    for (int nt = 0; nt < N / 16; ++nt)
-        for (int ks = 0; ks < KS; ++ks)
-            for (int l = 0; l < 64; ++l)
-                for (int j = 0; j < 8; ++j) {
-                    const int n = nt * 16 + (l & 15), k = ks * 32 + (l >> 4) * 8 + j;
-                    packed[(((size_t)nt * KS + ks) * 64 + l) * 8 + j] = (f16)(n < n_real ? wt(n, k) : 0.f);
-                }
+    const int N = (n_real + 31) / 32 * 32;
+    std::vector<f16> packed = pack_nt_ks(n_real, N, K, wt);
     std::vector<float> b(N, 0.f);
     std::copy(bias.begin(), bias.end(), b.begin());
     L->N = N; L->K = K;
-    int rc = upload(h, packed, &L->w);
-    return rc ? rc : upload(h, b, &L->bias);
+    int rc = h->upload(packed, &L->w);
+    return rc ? rc : h->upload(b, &L->bias);
 }
 
 // 3x3 conv weight [cout][cin_real][3][3] -> conv_kernel stream [k-step][n-tile], k = tap * cin + ci (cin = cin_real padded)
-int make_conv3(nunif_light_inpaint *h, const TMap &m, const std::string &key, int cin_real, int cin, int cout, Conv3 *c) {
-    const HostT *w, *b;
+int make_conv3(nunif_light_inpaint *h, const TensorMap &m, const std::string &key, int cin_real, int cin, int cout, Conv3 *c) {
+    const HostTensor *w, *b;
     int rc;
     if ((rc = find(m, key + ".weight", &w)) || (rc = find(m, key + ".bias", &b))) return rc;
     NUNIF_REQUIRE(w->numel == (int64_t)cout * cin_real * 9 && b->numel == cout, "%s: unexpected shape", key.c_str());
     const int N = (cout + 31) / 32 * 32, NT = N / 16, KS = 9 * cin / 32;
-    std::vector<f16> stream((size_t)KS * NT * 512 + 8192, (f16)0.f);
-    for (int ks = 0; ks < KS; ++ks)
-        for (int nt = 0; nt < NT; ++nt)
-            for (int l = 0; l < 64; ++l)
-                for (int j = 0; j < 8; ++j) {
-                    const int n = nt * 16 + (l & 15), kk = ks * 32 + (l >> 4) * 8 + j;
-                    const int tap = kk / cin, ci = kk % cin;
-                    const float v = (n < cout && ci < cin_real) ? w->data[((size_t)n * cin_real + ci) * 9 + tap] : 0.f;
-                    stream[(((size_t)ks * NT + nt) * 64 + l) * 8 + j] = (f16)v;
-                }
+    const float *wd = w->data;
+    std::vector<f16> stream = pack_ks_nt(cout, N, 9 * cin, [=](int n, int kk) {
+        const int tap = kk / cin, ci = kk % cin;
+        return ci < cin_real ? wd[((size_t)n * cin_real + ci) * 9 + tap] : 0.f;
+    });
     std::vector<float> bias(N, 0.f);
     std::copy(b->data, b->data + cout, bias.begin());
     c->N = N; c->n_real = cout; c->Cin = cin;
-    if ((rc = upload(h, stream, &c->stream))) return rc;
+    if ((rc = h->upload(stream, &c->stream))) return rc;
     if ((NT == 6 || NT == 12) && cout == N && cin <= 128) {
         const int parts[2] = {NT == 6 ? 4 : 8, NT == 6 ? 2 : 4};
         int nt0 = 0;
         for (int q = 0; q < 2; ++q) {
             const int nts = parts[q];
-            std::vector<f16> sl((size_t)KS * nts * 512 + 8192, (f16)0.f);
-            for (int ks = 0; ks < KS; ++ks)
-                for (int nt = 0; nt < nts; ++nt)
-                    std::copy(stream.begin() + ((size_t)ks * NT + nt0 + nt) * 512, stream.begin() + ((size_t)ks * NT + nt0 + nt + 1) * 512,
-                              sl.begin() + ((size_t)ks * nts + nt) * 512);
-            if ((rc = upload(h, sl, &c->slice_stream[q]))) return rc;
+            if ((rc = h->upload(stream_slice(stream, KS, NT, nt0, nts), &c->slice_stream[q]))) return rc;
             c->slice_nt[q] = nts;
             nt0 += nts;
         }
         c->n_slices = 2;
     }
-    return upload(h, bias, &c->bias);
+    return h->upload(bias, &c->bias);
 }
 
-int make_plain(nunif_light_inpaint *h, const TMap &m, const std::string &key, int n_real, int K, Lin *L) {
-    const HostT *w, *b;
+int make_plain(nunif_light_inpaint *h, const TensorMap &m, const std::string &key, int n_real, int K, Lin *L) {
+    const HostTensor *w, *b;
     int rc;
     if ((rc = find(m, key + ".weight", &w)) || (rc = find(m, key + ".bias", &b))) return rc;
     NUNIF_REQUIRE(w->numel == (int64_t)n_real * K && b->numel == n_real, "%s: unexpected shape", key.c_str());
@@ -560,9 +509,9 @@ int make_plain(nunif_light_inpaint *h, const TMap &m, const std::string &key, in
                     std::vector<float>(b->data, b->data + n_real), L);
 }
 
-int make_gblock(nunif_light_inpaint *h, const TMap &m, const std::string &p, int C, int ws, int shift, GBlock *g,
+int make_gblock(nunif_light_inpaint *h, const TensorMap &m, const std::string &p, int C, int ws, int shift, GBlock *g,
                 int ratio = 2, int temporal = 0) {
-    const HostT *n1, *n2;
+    const HostTensor *n1, *n2;
     int rc;
     if ((rc = find(m, p + "norm1.weight", &n1)) || (rc = find(m, p + "norm2.weight", &n2))) return rc;
     // ratio <= 0: take the gate width from the checkpoint (lv2_mlp_ratio of the video nets: 1 small, 2 medium / large)
@@ -570,11 +519,11 @@ int make_gblock(nunif_light_inpaint *h, const TMap &m, const std::string &p, int
     g->C = C; g->V = V; g->ws = ws; g->shift = shift; g->temporal = temporal;
     const int N = temporal ? 12 : ws * ws;
     NUNIF_REQUIRE(n1->numel == C && n2->numel == V && (V == C || V == 2 * C), "%s: LayerNorm shapes", p.c_str());
-    if ((rc = upload(h, std::vector<float>(n1->data, n1->data + C), &g->ln1)) ||
-        (rc = upload(h, std::vector<float>(n2->data, n2->data + V), &g->ln2)))
+    if ((rc = h->upload(std::vector<float>(n1->data, n1->data + C), &g->ln1)) ||
+        (rc = h->upload(std::vector<float>(n2->data, n2->data + V), &g->ln2)))
         return rc;
     if (temporal) {
-        const HostT *sw, *sb;
+        const HostTensor *sw, *sb;
         if ((rc = find(m, p + "gmlp.gmlp.proj_spatial.weight", &sw)) || (rc = find(m, p + "gmlp.gmlp.proj_spatial.bias", &sb)))
             return rc;
         NUNIF_REQUIRE(sw->numel == 144 && sb->numel == 12, "%s: temporal mixing matrix must be 12 x 12", p.c_str());
@@ -711,18 +660,11 @@ int run_gblock_any(nunif_light_inpaint *h, const GBlock &g, f16 *x, int B, int h
 
 extern "C" int nunif_hip_light_inpaint_create(const nunif_tensor_desc *tensors, int32_t n_tensors, nunif_light_inpaint **handle) {
     NUNIF_REQUIRE(tensors && handle && n_tensors > 0, "light_inpaint_create: NULL argument");
-    TMap m;
-    for (int i = 0; i < n_tensors; ++i) {
-        HostT t;
-        t.data = tensors[i].data;
-        t.numel = 1;
-        for (int d = 0; d < tensors[i].ndim; ++d) { t.shape.push_back(tensors[i].shape[d]); t.numel *= tensors[i].shape[d]; }
-        m[tensors[i].name] = t;
-    }
+    const TensorMap m = tensor_map(tensors, n_tensors);
     nunif_light_inpaint *h = new nunif_light_inpaint();
     int rc = NUNIF_HIP_OK;
     do {
-        const HostT *mb, *pw, *pb, *dw, *db, *uw, *ub;
+        const HostTensor *mb, *pw, *pb, *dw, *db, *uw, *ub;
         // inpaint.light_video_inpaint_v1 has `patch` = Conv2d(3, 96, 4, 4) (same k = c*16 + ky*4 + kx order as the
         // pixel_unshuffle(4) + 1x1 conv of the image net) and a 1x1 `to_image`
         h->video = m.count("patch.weight") ? 1 : 0;
@@ -741,7 +683,7 @@ extern "C" int nunif_hip_light_inpaint_create(const nunif_tensor_desc *tensors, 
         h->C = C;
         std::vector<f16> mbh(C);
         for (int i = 0; i < C; ++i) mbh[i] = (f16)mb->data[i];
-        if ((rc = upload(h, mbh, &h->mask_bias))) break;
+        if ((rc = h->upload(mbh, &h->mask_bias))) break;
         {   // patch: 1x1 conv 48 -> C on the pixel_unshuffle(4) channels (input padded to 64)
             const float *wd = pw->data;
             if ((rc = make_lin(h, C, 64, [=](int n, int k) { return k < 48 ? wd[(size_t)n * 48 + k] : 0.f; },
@@ -771,7 +713,7 @@ extern "C" int nunif_hip_light_inpaint_create(const nunif_tensor_desc *tensors, 
                                  temporal[i]);
             if (rc) break;
             if ((rc = make_gblock(h, m, "dec1.", C, 16, 0, &h->dec1))) break;
-            const HostT *tw, *tb;
+            const HostTensor *tw, *tb;
             if ((rc = find(m, "to_image.weight", &tw)) || (rc = find(m, "to_image.bias", &tb))) break;
             NUNIF_REQUIRE(tw->numel == (int64_t)48 * C && tb->numel == 48, "to_image: unexpected shape");
             const float *wd = tw->data;
@@ -799,8 +741,8 @@ extern "C" int nunif_hip_light_inpaint_create(const nunif_tensor_desc *tensors, 
 
 extern "C" void nunif_hip_light_inpaint_destroy(nunif_light_inpaint *h) {
     if (!h) return;
-    for (void *p : h->owned) (void)hipFree(p);
-    for (Buf *b : {&h->x1, &h->x2, &h->a, &h->pi, &h->vt, &h->st, &h->g, &h->po, &h->y, &h->z, &h->ti, &h->mtok, &h->mf0, &h->mf1,
+    h->free_all();
+    for (DeviceBuf *b : {&h->x1, &h->x2, &h->a, &h->pi, &h->vt, &h->st, &h->g, &h->po, &h->y, &h->z, &h->ti, &h->mtok, &h->mf0, &h->mf1,
                    &h->mf2, &h->hard, &h->soft})
         b->release();
     delete h;

@@ -17,15 +17,13 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
+#include "host_weights.h"
 #include "swin_kernels.h"
 
 namespace nunif {
-
-#define MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
 
 // ---------------------------------------------------------------------------------------------------------------------
 struct RfInputArgs {
@@ -80,10 +78,6 @@ struct WmhaArgs {
     int sy, sx;              // WindowMHA2d shift: the map is ZERO-padded by (sy, sx) on both sides, windows tile the
                              // padded map, padded positions act as (all-zero input) tokens and are cropped away again
 };
-
-__device__ __forceinline__ f16x8 cat8f(f16x4 lo, f16x4 hi) {
-    return (f16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
 
 // One window (WS x WS <= 16 tokens = one MFMA tile) per wave; C channels = C/32 heads of 32; weights resident in LDS.
 template <int WS, int C>
@@ -141,7 +135,7 @@ __global__ void __launch_bounds__(256) wmha_kernel(WmhaArgs a) {
         const f32x4 bias = *reinterpret_cast<const f32x4 *>(tb + r16 * 16 + 4 * grp);          // [query l&15][keys 4g..]
 #pragma unroll
         for (int hh = 0; hh < HEADS; ++hh) {
-            f32x4 s = MFMA_16x16x32(cat8f(k4[2 * hh], k4[2 * hh + 1]), cat8f(q4[2 * hh], q4[2 * hh + 1]), bias);
+            f32x4 s = MFMA_16x16x32(cat8(k4[2 * hh], k4[2 * hh + 1]), cat8(q4[2 * hh], q4[2 * hh + 1]), bias);
             float mx = fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));
             mx = fmaxf(mx, __shfl_xor(mx, 16));
             mx = fmaxf(mx, __shfl_xor(mx, 32));
@@ -151,11 +145,11 @@ __global__ void __launch_bounds__(256) wmha_kernel(WmhaArgs a) {
             sum += __shfl_xor(sum, 16);
             sum += __shfl_xor(sum, 32);
             const float inv = 1.0f / sum;
-            const f16x8 pf = cat8f((f16x4){(f16)p0, (f16)p1, (f16)p2, (f16)p3}, zero4);
+            const f16x8 pf = cat8((f16x4){(f16)p0, (f16)p1, (f16)p2, (f16)p3}, zero4);
 #pragma unroll
             for (int dt = 0; dt < 2; ++dt) {
                 f32x4 o = {0.f, 0.f, 0.f, 0.f};
-                o = MFMA_16x16x32(cat8f(v4[2 * hh + dt], zero4), pf, o);
+                o = MFMA_16x16x32(cat8(v4[2 * hh + dt], zero4), pf, o);
                 o4[2 * hh + dt] = (f16x4){(f16)(o[0] * inv), (f16)(o[1] * inv), (f16)(o[2] * inv), (f16)(o[3] * inv)};
             }
         }
@@ -165,7 +159,7 @@ __global__ void __launch_bounds__(256) wmha_kernel(WmhaArgs a) {
             f32x4 acc = *reinterpret_cast<const f32x4 *>(bp + nt * 16 + 4 * grp);
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks)
-                acc = MFMA_16x16x32(wq[(3 * NT * KS + nt * KS + ks) * 64], cat8f(o4[2 * ks], o4[2 * ks + 1]), acc);
+                acc = MFMA_16x16x32(wq[(3 * NT * KS + nt * KS + ks) * 64], cat8(o4[2 * ks], o4[2 * ks + 1]), acc);
             if (inside && r16 < N) {
                 f16 *px = a.x + pix * C + nt * 16 + 4 * grp;
                 const f16x4 xr = *reinterpret_cast<const f16x4 *>(px);
@@ -405,29 +399,6 @@ using namespace nunif;
 // =====================================================================================================================
 namespace {
 
-struct HostT { const float *data; std::vector<int64_t> shape; int64_t numel; };
-typedef std::map<std::string, HostT> TMap;
-
-int find(const TMap &m, const std::string &key, const HostT **out) {
-    auto it = m.find(key);
-    if (it == m.end()) { set_error("state_dict is missing '%s'", key.c_str()); return NUNIF_HIP_EMISSING; }
-    *out = &it->second;
-    return NUNIF_HIP_OK;
-}
-
-struct Buf {
-    void *p = nullptr; size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return NUNIF_HIP_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        if (hipMalloc(&p, bytes) != hipSuccess) { set_error("hipMalloc(%zu) failed", bytes); return NUNIF_HIP_ENOMEM; }
-        cap = bytes;
-        return NUNIF_HIP_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-
 struct WaBlock {
     f16 *wfrag = nullptr; float *bqkv = nullptr, *bproj = nullptr, *btab = nullptr;
     f16 *w1 = nullptr; float *b1 = nullptr;          // conv_mlp[0] 1x1, gemm_kernel packing [nt][ks]
@@ -437,42 +408,20 @@ struct WaBlock {
 
 }  // namespace
 
-struct nunif_row_flow {
-    std::vector<void *> owned;
+struct nunif_row_flow : DeviceOwner {
     float *w_in = nullptr, *w_out = nullptr;
     WaBlock blk[2];
-    Buf f, t1, t2;
+    DeviceBuf f, t1, t2;
 };
 
 namespace {
 
-template <typename H, typename T>
-int upload(H *h, const std::vector<T> &host, T **dev) {
-    void *p = nullptr;
-    if (hipMalloc(&p, host.size() * sizeof(T)) != hipSuccess) { set_error("hipMalloc failed"); return NUNIF_HIP_ENOMEM; }
-    h->owned.push_back(p);
-    NUNIF_HIP_CHECK(hipMemcpy(p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
-    *dev = reinterpret_cast<T *>(p);
-    return NUNIF_HIP_OK;
-}
-
-// MFMA A fragment (nt, ks): lane l holds W[nt*16 + (l&15)][k(ks, l>>4, j)], j = 0..7
-template <typename F>
-void put_frag(std::vector<f16> &dst, size_t frag, int nt, int ks, bool chained, F wt) {
-    for (int l = 0; l < 64; ++l)
-        for (int j = 0; j < 8; ++j) {
-            const int g = l >> 4, n = nt * 16 + (l & 15);
-            const int k = chained ? ks * 32 + (j < 4 ? 4 * g + j : 16 + 4 * g + (j - 4)) : ks * 32 + g * 8 + j;
-            dst[(frag * 64 + l) * 8 + j] = (f16)wt(n, k);
-        }
-}
-
 double gelu_erf_d(double v) { return 0.5 * v * (1.0 + erf(v * 0.70710678118654752440)); }
 
-template <typename H>
-int make_block(H *h, const TMap &m, const std::string &p, int window, int C, WaBlock *bk) {
+// h: the row_flow or the MLBW handle
+int make_block(DeviceOwner *h, const TensorMap &m, const std::string &p, int window, int C, WaBlock *bk) {
     const int NT = C / 16, KS = C / 32;
-    const HostT *wqkv, *bqkv, *wp, *bp, *w1, *b1, *w3, *b3, *tw0, *tb0, *tw2, *tb2;
+    const HostTensor *wqkv, *bqkv, *wp, *bp, *w1, *b1, *w3, *b3, *tw0, *tb0, *tw2, *tb2;
     int rc;
     if ((rc = find(m, p + "mha.mha.qkv_proj.weight", &wqkv)) || (rc = find(m, p + "mha.mha.qkv_proj.bias", &bqkv)) ||
         (rc = find(m, p + "mha.mha.head_proj.weight", &wp)) || (rc = find(m, p + "mha.mha.head_proj.bias", &bp)) ||
@@ -486,7 +435,7 @@ int make_block(H *h, const TMap &m, const std::string &p, int window, int C, WaB
     bk->window = window;
     const float qs = (1.0f / sqrtf(32.0f)) * 1.4426950408889634f;       // head_dim^-0.5 * log2(e), folded into q
     {
-        std::vector<f16> frags((size_t)4 * NT * KS * 512);
+        std::vector<f16> frags((size_t)4 * NT * KS * kFragHalfs);
         const float *wd = wqkv->data;
         for (int part = 0; part < 3; ++part)
             for (int nt = 0; nt < NT; ++nt)
@@ -497,10 +446,10 @@ int make_block(H *h, const TMap &m, const std::string &p, int window, int C, WaB
         for (int nt = 0; nt < NT; ++nt)
             for (int ks = 0; ks < KS; ++ks)
                 put_frag(frags, (size_t)3 * NT * KS + nt * KS + ks, nt, ks, true, [=](int n, int k) { return pd[(size_t)n * C + k]; });
-        if ((rc = upload(h, frags, &bk->wfrag))) return rc;
+        if ((rc = h->upload(frags, &bk->wfrag))) return rc;
         std::vector<float> bq(3 * C), bpv(bp->data, bp->data + C);
         for (int n = 0; n < 3 * C; ++n) bq[n] = bqkv->data[n] * (n < C ? qs : 1.0f);
-        if ((rc = upload(h, bq, &bk->bqkv)) || (rc = upload(h, bpv, &bk->bproj))) return rc;
+        if ((rc = h->upload(bq, &bk->bqkv)) || (rc = h->upload(bpv, &bk->bproj))) return rc;
     }
     {   // WindowScoreBias (attention.py:375-419): to_bias MLP on the normalised relative offsets, evaluated once here
         const int hidden = (int)tb0->numel, N = window * window;
@@ -517,27 +466,21 @@ int make_block(H *h, const TMap &m, const std::string &p, int window, int C, WaB
                 tab[q * 16 + k] = (float)o * 1.4426950408889634f;
             }
         for (int q = N; q < 16; ++q) for (int k = 0; k < N; ++k) tab[q * 16 + k] = 0.f;     // padded queries: any finite row
-        if ((rc = upload(h, tab, &bk->btab))) return rc;
+        if ((rc = h->upload(tab, &bk->btab))) return rc;
     }
-    {   // conv_mlp[0]: 1x1 as a Linear, gemm_kernel packing [nt][ks] (+16 KiB pad for the ring prefetch)
-        std::vector<f16> packed((size_t)C * C + 8192, (f16)0.f);
+    {   // conv_mlp[0]: 1x1 as a Linear, gemm_kernel packing [nt][ks]
         const float *wd = w1->data;
-        for (int nt = 0; nt < NT; ++nt)
-            for (int ks = 0; ks < KS; ++ks) put_frag(packed, (size_t)nt * KS + ks, nt, ks, false, [=](int n, int k) { return wd[(size_t)n * C + k]; });
+        std::vector<f16> packed = pack_nt_ks(C, C, C, [=](int n, int k) { return wd[(size_t)n * C + k]; });
         std::vector<float> bb(b1->data, b1->data + C);
-        if ((rc = upload(h, packed, &bk->w1)) || (rc = upload(h, bb, &bk->b1))) return rc;
+        if ((rc = h->upload(packed, &bk->w1)) || (rc = h->upload(bb, &bk->b1))) return rc;
     }
     {   // conv_mlp[3]: 3x3, conv_kernel stream [ks][nt], k = tap*C + ci
-        const int KS3 = 9 * C / 32;
-        std::vector<f16> stream((size_t)KS3 * NT * 512 + 8192, (f16)0.f);
         const float *wd = w3->data;
-        for (int ks = 0; ks < KS3; ++ks)
-            for (int nt = 0; nt < NT; ++nt)
-                put_frag(stream, (size_t)ks * NT + nt, nt, ks, false, [=](int n, int k) {
-                    const int tap = k / C, ci = k % C;
-                    return wd[((size_t)n * C + ci) * 9 + tap]; });
+        std::vector<f16> stream = pack_ks_nt(C, C, 9 * C, [=](int n, int k) {
+            const int tap = k / C, ci = k % C;
+            return wd[((size_t)n * C + ci) * 9 + tap]; });
         std::vector<float> bb(b3->data, b3->data + C);
-        if ((rc = upload(h, stream, &bk->w3)) || (rc = upload(h, bb, &bk->b3))) return rc;
+        if ((rc = h->upload(stream, &bk->w3)) || (rc = h->upload(bb, &bk->b3))) return rc;
     }
     return NUNIF_HIP_OK;
 }
@@ -546,18 +489,11 @@ int make_block(H *h, const TMap &m, const std::string &p, int window, int C, WaB
 
 extern "C" int nunif_hip_row_flow_create(const nunif_tensor_desc *tensors, int32_t n_tensors, nunif_row_flow **handle) {
     NUNIF_REQUIRE(tensors && handle && n_tensors > 0, "row_flow_create: NULL argument");
-    TMap m;
-    for (int i = 0; i < n_tensors; ++i) {
-        HostT t;
-        t.data = tensors[i].data;
-        t.numel = 1;
-        for (int d = 0; d < tensors[i].ndim; ++d) { t.shape.push_back(tensors[i].shape[d]); t.numel *= tensors[i].shape[d]; }
-        m[tensors[i].name] = t;
-    }
+    const TensorMap m = tensor_map(tensors, n_tensors);
     nunif_row_flow *h = new nunif_row_flow();
     int rc = NUNIF_HIP_OK;
     do {
-        const HostT *w0, *b0, *wl, *bl;
+        const HostTensor *w0, *b0, *wl, *bl;
         if ((rc = find(m, "blocks.0.weight", &w0)) || (rc = find(m, "blocks.0.bias", &b0)) ||
             (rc = find(m, "last_layer.1.weight", &wl)) || (rc = find(m, "last_layer.1.bias", &bl)))
             break;
@@ -567,7 +503,7 @@ extern "C" int nunif_hip_row_flow_create(const nunif_tensor_desc *tensors, int32
         for (int co = 0; co < 64; ++co) win[24 * 64 + co] = b0->data[co];
         for (int i = 0; i < 72; ++i) wout[i] = wl->data[i];
         wout[72] = bl->data[0];
-        if ((rc = upload(h, win, &h->w_in)) || (rc = upload(h, wout, &h->w_out))) break;
+        if ((rc = h->upload(win, &h->w_in)) || (rc = h->upload(wout, &h->w_out))) break;
         if ((rc = make_block(h, m, "blocks.1.", 4, 64, &h->blk[0]))) break;
         if ((rc = make_block(h, m, "blocks.2.", 3, 64, &h->blk[1]))) break;
     } while (0);
@@ -578,7 +514,7 @@ extern "C" int nunif_hip_row_flow_create(const nunif_tensor_desc *tensors, int32
 
 extern "C" void nunif_hip_row_flow_destroy(nunif_row_flow *h) {
     if (!h) return;
-    for (void *p : h->owned) (void)hipFree(p);
+    h->free_all();
     h->f.release(); h->t1.release(); h->t2.release();
     delete h;
 }
@@ -666,29 +602,21 @@ extern "C" int nunif_hip_delta_weight_warp(const float *c, const float *delta, c
 }
 
 // ---- MLBW --------------------------------------------------------------------------------------------------------------
-struct nunif_mlbw {
-    std::vector<void *> owned;
+struct nunif_mlbw : DeviceOwner {
     int L = 2, C = 64, n_blocks = 4, hole_mask = 0;
     float *w_in = nullptr, *w_out = nullptr;
     WaBlock blk[4];
     int sy[4] = {0, 0, 0, 0}, sx[4] = {0, 0, 0, 0};
-    Buf f, x1, t1, t2;
+    DeviceBuf f, x1, t1, t2;
 };
 
 extern "C" int nunif_hip_mlbw_create(const nunif_tensor_desc *tensors, int32_t n_tensors, nunif_mlbw **handle) {
     NUNIF_REQUIRE(tensors && handle && n_tensors > 0, "mlbw_create: NULL argument");
-    TMap m;
-    for (int i = 0; i < n_tensors; ++i) {
-        HostT t;
-        t.data = tensors[i].data;
-        t.numel = 1;
-        for (int d = 0; d < tensors[i].ndim; ++d) { t.shape.push_back(tensors[i].shape[d]); t.numel *= tensors[i].shape[d]; }
-        m[tensors[i].name] = t;
-    }
+    const TensorMap m = tensor_map(tensors, n_tensors);
     nunif_mlbw *h = new nunif_mlbw();
     int rc = NUNIF_HIP_OK;
     do {
-        const HostT *wi, *bi, *wo, *bo;
+        const HostTensor *wi, *bi, *wo, *bo;
         if ((rc = find(m, "lv1_in.1.weight", &wi)) || (rc = find(m, "lv1_in.1.bias", &bi)) ||
             (rc = find(m, "lv1_out.1.weight", &wo)) || (rc = find(m, "lv1_out.1.bias", &bo)))
             break;
@@ -712,7 +640,7 @@ extern "C" int nunif_hip_mlbw_create(const nunif_tensor_desc *tensors, int32_t n
         for (int co = 0; co < Cs; ++co) win[27 * Cs + co] = bi->data[co];
         for (int k = 0; k < Cs * 9; ++k) for (int o = 0; o < no; ++o) wout[(size_t)k * no + o] = wo->data[(size_t)o * Cs * 9 + k];
         for (int o = 0; o < no; ++o) wout[(size_t)Cs * 9 * no + o] = bo->data[o];
-        if ((rc = upload(h, win, &h->w_in)) || (rc = upload(h, wout, &h->w_out))) break;
+        if ((rc = h->upload(win, &h->w_in)) || (rc = h->upload(wout, &h->w_out))) break;
         for (int i = 0; i < h->n_blocks && !rc; ++i)
             rc = make_block(h, m, "lv2." + std::to_string(i) + ".", 4, h->C, &h->blk[i]);
     } while (0);
@@ -723,7 +651,7 @@ extern "C" int nunif_hip_mlbw_create(const nunif_tensor_desc *tensors, int32_t n
 
 extern "C" void nunif_hip_mlbw_destroy(nunif_mlbw *h) {
     if (!h) return;
-    for (void *p : h->owned) (void)hipFree(p);
+    h->free_all();
     h->f.release(); h->x1.release(); h->t1.release(); h->t2.release();
     delete h;
 }

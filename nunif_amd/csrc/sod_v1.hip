@@ -248,13 +248,6 @@ __global__ void __launch_bounds__(256) sod_head_kernel(const HeadArgs g) {
 }
 
 // ---- depth_position_from_ratio (convergence_estimator.py:33-59) ----------------------------------------------------------------------
-__device__ __forceinline__ unsigned order_key(float v) {
-    const unsigned b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float key_value(unsigned k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 
 // One workgroup per image.  The four order statistics torch.quantile's linear interpolation needs (floor and ceil rank of q = 0.1
 // and q = 0.9) are found together by a radix select over the ordered bit pattern: four passes of 8 bits, one 256-bin histogram per

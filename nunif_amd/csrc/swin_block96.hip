@@ -30,8 +30,6 @@
 
 namespace nunif {
 
-#define MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
-
 namespace {
 
 constexpr int kC = 96, kKS = 3, kNT = 6, kSH = 6, kHeads = 6;
@@ -55,10 +53,6 @@ struct Block96Args {
     int ps, n_real;
     int B, H, W, shift, n_windows, rev;
 };
-
-__device__ __forceinline__ f16x8 cat8(f16x4 lo, f16x4 hi) {
-    return (f16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
 
 // window-local token t (0..35) -> (iy, ix) in the 6x6 window: 2x2 blocks, blocks row-major over a 3x3 grid
 __device__ __forceinline__ void tok_yx(int t, int &iy, int &ix) {

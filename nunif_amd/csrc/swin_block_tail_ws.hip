@@ -38,8 +38,6 @@
 
 namespace nunif {
 
-#define MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
-
 typedef __attribute__((address_space(3))) void lds_void;
 
 constexpr int kWsC = 192;

@@ -18,15 +18,9 @@
 
 namespace nunif {
 
-#define MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
-
 namespace {
 constexpr int kWaves = 8;
 constexpr int kMF = 2;
-
-__device__ __forceinline__ void dma16(const void *src, unsigned lds_byte_addr) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(lds_byte_addr) : "memory");
-}
 }  // namespace
 
 // <96, 12, 12>: four taps (2 x 2) of 96 channels -> 192; <192, 12, 12>: the two taps of ONE row (g.oy) -> 192;

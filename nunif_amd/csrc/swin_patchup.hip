@@ -26,8 +26,6 @@
 
 namespace nunif {
 
-#define MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
-
 namespace {
 constexpr int kKS = 6;                               // K = 192
 constexpr int kNT = 24;                              // 16-column tiles resident per workgroup (384 columns)
@@ -42,11 +40,6 @@ constexpr int kWBytes = kNT * kKS * 1024;            // 147 456
 constexpr int kSmem = kWBytes + 384 * 4;             // + bias
 static_assert(kSmem <= 160 * 1024, "LDS");
 static_assert(kTrips % kD == 0, "the ring slot of a trip is static");
-
-__device__ __forceinline__ void dma16(const void *src, unsigned lds_byte_addr) {
-    // each lane moves 16 B to LDS[m0 + 16 * lane]; m0 is wave-uniform
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(lds_byte_addr) : "memory");
-}
 }  // namespace
 
 template <int CQ>

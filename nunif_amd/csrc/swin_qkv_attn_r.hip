@@ -22,8 +22,6 @@
 
 namespace nunif {
 
-#define MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
-
 // What is compiled today (the measured-off build variants of round 6 and their numbers: docs/history.md, "Removed build variants"):
 // window-major stores are `SGPR base + 32-bit lane constant`, `o * inv` and its fp16 convert are one v_fma_mixlo / mixhi_f16 per
 // value, the six heads of C = 96 are unrolled behind sched_barrier(0) (every LDS address an immediate) with the weight fragments
@@ -43,10 +41,6 @@ struct QkvAttnRArgs {
     int B, H, W, shift, n_windows;
     int rev;                 // 1: walk the windows from the last to the first (snake order, see launch_qkv_attn_r)
 };
-
-__device__ __forceinline__ f16x8 cat8r(f16x4 lo, f16x4 hi) {
-    return (f16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
 
 // o * inv -> fp16, the product rounded ONCE: (f16) fma(o, inv, 0) is v_fma_mixlo / mixhi_f16 (fp32 fma, converted on the way out) —
 // one instruction per value instead of v_mul_f32 + half a v_cvt_pk_f16_f32.  (Written as C so that hipcc counts the wait states
@@ -322,10 +316,10 @@ qkv_attn_r_kernel(QkvAttnRArgs a) {
                     for (int kt = 0; kt < 3; ++kt) {
                         f32x4 acc = sb[kt];
                         if constexpr (HD == 16) {
-                            acc = MFMA_16x16x32(cat8r(kt4[0][kt], rkr[kt]), cat8r(qt4[0][qt], rqr[qt]), acc);
+                            acc = MFMA_16x16x32(cat8(kt4[0][kt], rkr[kt]), cat8(qt4[0][qt], rqr[qt]), acc);
                         } else {
-                            acc = MFMA_16x16x32(cat8r(kt4[0][kt], kt4[1][kt]), cat8r(qt4[0][qt], qt4[1][qt]), acc);
-                            if (sp_now) acc = MFMA_16x16x32(cat8r(rkr[kt], zero4), cat8r(rqr[qt], zero4), acc);
+                            acc = MFMA_16x16x32(cat8(kt4[0][kt], kt4[1][kt]), cat8(qt4[0][qt], qt4[1][qt]), acc);
+                            if (sp_now) acc = MFMA_16x16x32(cat8(rkr[kt], zero4), cat8(rqr[qt], zero4), acc);
                         }
                         s[kt] = acc;
                     }
@@ -344,7 +338,7 @@ qkv_attn_r_kernel(QkvAttnRArgs a) {
                 pf[2] = lone_to_f16x4(__builtin_amdgcn_exp2f(s[2][0] - mx), zf);
                 // ONE fragment [p0 + p1 | p2] serves the denominator (ones x it = the sum of the fp16 probabilities the PV
                 // product actually uses) AND the key-tile-2 part of PV (V of tile 2 sits in the HIGH k-slots of vz, zeros below)
-                const f16x8 psum = cat8r(pf[0] + pf[1], pf[2]);
+                const f16x8 psum = cat8(pf[0] + pf[1], pf[2]);
                 const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
                 const f32x4 sm = MFMA_16x16x32(ones8, psum, z4);
                 const float inv = __builtin_amdgcn_rcpf(sm[0]);
@@ -354,8 +348,8 @@ qkv_attn_r_kernel(QkvAttnRArgs a) {
                 f16x4 ov[NTH];
 #pragma unroll
                 for (int dt = 0; dt < NTH; ++dt) {
-                    f32x4 o = MFMA_16x16x32(cat8r(vt4[dt][0], vt4[dt][1]), cat8r(pf[0], pf[1]), z4);
-                    o = MFMA_16x16x32(cat8r(zero4, vt4[dt][2]), psum, o);
+                    f32x4 o = MFMA_16x16x32(cat8(vt4[dt][0], vt4[dt][1]), cat8(pf[0], pf[1]), z4);
+                    o = MFMA_16x16x32(cat8(zero4, vt4[dt][2]), psum, o);
                     ov[dt] = mul4_to_f16(o, inv);
                 }
                 if constexpr (NTH == 2) {

@@ -22,8 +22,6 @@
 
 namespace nunif {
 
-#define MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
-
 namespace {
 constexpr int kTile = 16;                 // output tile WIDTH; its height is 8 waves x ROWS rows (ROWS = 2: 16 x 16, ROWS = 3: 24 x 16)
 constexpr int kWaves = 8;

@@ -6,10 +6,10 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
+#include "host_weights.h"
 #include "swin_kernels.h"
 
 namespace nunif {
@@ -18,8 +18,6 @@ int launch_stitch(const float *tile_out, float *y, const nunif_tile_grid *g, int
                   int compact = 0);
 
 namespace {
-
-struct HostTensor { const float *data; std::vector<int64_t> shape; int64_t numel; };
 
 struct Linear {          // fragment-packed fp16 weight + fp32 bias, device memory
     f16 *w = nullptr;
@@ -47,29 +45,12 @@ struct Block {
     float *b96_btab = nullptr;
 };
 
-struct DeviceBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return NUNIF_HIP_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        if (hipMalloc(&p, bytes) != hipSuccess) {
-            set_error("hipMalloc(%zu) failed", bytes);
-            return NUNIF_HIP_ENOMEM;
-        }
-        cap = bytes;
-        return NUNIF_HIP_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-
 }  // namespace
 }  // namespace nunif
 
 using namespace nunif;
 
-struct nunif_swin_unet {
+struct nunif_swin_unet : DeviceOwner {       // owns every device allocation made at create time
     int scale_factor = 2;
     int C = 96, heads = 6;
     int C1 = 48, C1P = 64;            // stem conv1 channels (real / padded to a multiple of 32)
@@ -86,7 +67,6 @@ struct nunif_swin_unet {
     int block96 = 0;                  // NUNIF_BLOCK96=1: C = 96 blocks as ONE kernel (swin_block96.hip) instead of attention + tail
     bool has_proj2 = false;
     std::vector<Block> swin[5];
-    std::vector<void *> owned;        // every device allocation made at create time
     DeviceBuf s1, f1, f2, f3, g1, qkv, att, hid, tile_out;
     // token -> pixel tables of the window-major C = 96 tail (launch_winmap_build), one per shift, for the geometry last seen
     DeviceBuf winmap[2];
@@ -102,69 +82,21 @@ struct nunif_swin_unet {
 namespace nunif {
 namespace {
 
-typedef std::map<std::string, HostTensor> TensorMap;
+int pad16(int n) { return (n + 15) / 16 * 16; }
 
-int find(const TensorMap &m, const std::string &key, const HostTensor **out) {
-    auto it = m.find(key);
-    if (it == m.end()) {
-        set_error("state_dict is missing '%s'", key.c_str());
-        return NUNIF_HIP_EMISSING;
-    }
-    *out = &it->second;
-    return NUNIF_HIP_OK;
-}
-
-template <typename T>
-int upload(nunif_swin_unet *h, const std::vector<T> &host, T **dev) {
-    void *p = nullptr;
-    if (hipMalloc(&p, host.size() * sizeof(T)) != hipSuccess) {
-        set_error("hipMalloc(%zu) failed", host.size() * sizeof(T));
-        return NUNIF_HIP_ENOMEM;
-    }
-    h->owned.push_back(p);
-    NUNIF_HIP_CHECK(hipMemcpy(p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
-    *dev = reinterpret_cast<T *>(p);
-    return NUNIF_HIP_OK;
-}
-
-// Fragment-major packing for the MFMA A operand (v_mfma_f32_16x16x32_f16): fragment (nt, ks) is 64 lanes x 8 halfs,
-// lane l holds W[nt*16 + (l&15)][ks*32 + (l>>4)*8 + 0..7]; rows beyond n_real are zero.  `wt(n,k)` returns fp32.
-//
-// `chained` packing is for a GEMM whose B operand is not loaded from memory but taken straight from the fp32
-// accumulators of the previous GEMM (proj -> mlp.0 -> mlp.3 in proj_mlp_kernel): a lane of a 16x16 accumulator
-// tile holds channels 4*(l>>4)+r, so the 8 k-slots of lane group g in K-chunk ks are the channels
-// {32ks + 4g + 0..3} (tile 2ks) and {32ks + 16 + 4g + 0..3} (tile 2ks+1).  The reduction order over k is free, so
-// the permutation is absorbed here at zero run-time cost.
-template <typename F>
-std::vector<f16> pack_a_fragments(int n_real, int K, F wt, bool chained) {
-    const int N = (n_real + 15) / 16 * 16;
-    // + 16 KiB of zeros: the LDS-ring kernels prefetch one 8-KiB chunk past the last fragment they consume
-    std::vector<f16> packed((size_t)N * K + 8192, (f16)0.0f);
-    const int KS = K / 32;
-    for (int nt = 0; nt < N / 16; ++nt)
-        for (int ks = 0; ks < KS; ++ks)
-            for (int l = 0; l < 64; ++l)
-                for (int j = 0; j < 8; ++j) {
-                    const int g = l >> 4;
-                    const int n = nt * 16 + (l & 15);
-                    const int k = chained ? ks * 32 + (j < 4 ? 4 * g + j : 16 + 4 * g + (j - 4)) : ks * 32 + g * 8 + j;
-                    packed[(((size_t)nt * KS + ks) * 64 + l) * 8 + j] = (f16)(n < n_real ? wt(n, k) : 0.0f);
-                }
-    return packed;
-}
-
+// fragment layout, plain and chained k order: host_weights.h (put_frag).  `wt(n,k)` returns fp32.
 template <typename F>
 int make_linear(nunif_swin_unet *h, int n_real, int K, F wt, const float *bias, Linear *L, bool chained = false,
                 std::vector<f16> *keep = nullptr) {
-    const int N = (n_real + 15) / 16 * 16;
-    std::vector<f16> packed = pack_a_fragments(n_real, K, wt, chained);
+    const int N = pad16(n_real);
+    std::vector<f16> packed = pack_nt_ks(n_real, N, K, wt, chained);
     std::vector<float> b(N, 0.0f);
     for (int n = 0; n < n_real; ++n) b[n] = bias[n];
     L->N = N; L->n_real = n_real; L->K = K;
     if (keep) *keep = packed;
-    int rc = upload(h, packed, &L->w);
+    int rc = h->upload(packed, &L->w);
     if (rc) return rc;
-    return upload(h, b, &L->bias);
+    return h->upload(b, &L->bias);
 }
 
 int make_plain_linear(nunif_swin_unet *h, const TensorMap &m, const std::string &key, int n_real, int K, Linear *L,
@@ -196,7 +128,7 @@ int make_stage(nunif_swin_unet *h, const TensorMap &m, const std::string &key, i
             NUNIF_REQUIRE(n1->numel == dim && n2->numel == dim, "%snorm: shape", p.c_str());
             NUNIF_REQUIRE(m.find(p + "norm1.bias") == m.end(), "%snorm1: LayerNorm with bias is not a reference variant", p.c_str());
             std::vector<float> g1(n1->data, n1->data + dim), g2(n2->data, n2->data + dim);
-            if ((rc = upload(h, g1, &bl.norm1)) || (rc = upload(h, g2, &bl.norm2))) return rc;
+            if ((rc = h->upload(g1, &bl.norm1)) || (rc = h->upload(g2, &bl.norm2))) return rc;
         }
         if (!bl.fast) {
             if ((rc = make_plain_linear(h, m, p + "attn.proj", dim, dim, &bl.proj)) ||
@@ -209,8 +141,8 @@ int make_stage(nunif_swin_unet *h, const TensorMap &m, const std::string &key, i
             if ((rc = find(m, p + "attn.qkv.weight", &w)) || (rc = find(m, p + "attn.qkv.bias", &b))) return rc;
             const float qs = (1.0f / sqrtf((float)(dim / heads))) * 1.4426950408889634f;
             const float *wd = w->data;
-            std::vector<f16> hs = pack_a_fragments(3 * dim, dim, [=](int n, int k) {
-                return wd[(size_t)n * dim + k] * (n < dim ? qs : 1.0f); }, false);
+            std::vector<f16> hs = pack_nt_ks(3 * dim, 3 * dim, dim, [=](int n, int k) {
+                return wd[(size_t)n * dim + k] * (n < dim ? qs : 1.0f); });
             // per head: Wq tiles, Wk tiles, Wv tiles, each (nt, ks) fragment-major — the order qkv_attn_r_kernel reads them
             const int KS = dim / 32, NTH = (dim / heads) / 16, nf = 3 * (dim / 16) * KS;
             std::vector<f16> stream((size_t)nf * 512, (f16)0.0f);
@@ -218,15 +150,12 @@ int make_stage(nunif_swin_unet *h, const TensorMap &m, const std::string &key, i
             for (int hh = 0; hh < heads; ++hh)
                 for (int part = 0; part < 3; ++part)
                     for (int nt = 0; nt < NTH; ++nt)
-                        for (int ks = 0; ks < KS; ++ks) {
-                            const size_t frag = (size_t)(part * (dim / 16) + hh * NTH + nt) * KS + ks;
-                            std::copy(hs.begin() + frag * 512, hs.begin() + (frag + 1) * 512, stream.begin() + fi * 512);
-                            ++fi;
-                        }
-            if ((rc = upload(h, stream, &bl.qkv_res))) return rc;
+                        for (int ks = 0; ks < KS; ++ks)
+                            copy_frag(hs, (size_t)(part * (dim / 16) + hh * NTH + nt) * KS + ks, stream, &fi);
+            if ((rc = h->upload(stream, &bl.qkv_res))) return rc;
             std::vector<float> rb(3 * dim);
             for (int n = 0; n < 3 * dim; ++n) rb[n] = b->data[n] * (n < dim ? qs : 1.0f);
-            if ((rc = upload(h, rb, &bl.qkv_rbias))) return rc;
+            if ((rc = h->upload(rb, &bl.qkv_rbias))) return rc;
         }
         std::vector<f16> hp, h0, h3;
         if (bl.fast) {
@@ -239,11 +168,7 @@ int make_stage(nunif_swin_unet *h, const TensorMap &m, const std::string &key, i
             const int nf = proj_mlp_stream_frags(dim);
             std::vector<f16> stream((size_t)(nf + 15) / 16 * 16 * 512, (f16)0.0f);     // whole 16-fragment chunks
             size_t fi = 0;
-            auto put = [&](const std::vector<f16> &src, int frag) {
-                std::copy(src.begin() + (size_t)frag * 512, src.begin() + (size_t)(frag + 1) * 512,
-                          stream.begin() + fi * 512);
-                ++fi;
-            };
+            auto put = [&](const std::vector<f16> &src, int frag) { copy_frag(src, frag, stream, &fi); };
             for (int sx = 0; sx < KS; ++sx)
                 for (int ks = 0; ks < KS; ++ks) { put(hp, (2 * sx) * KS + ks); put(hp, (2 * sx + 1) * KS + ks); }
             for (int sx = 0; sx < SH; ++sx) {
@@ -251,16 +176,13 @@ int make_stage(nunif_swin_unet *h, const TensorMap &m, const std::string &key, i
                 for (int nt = 0; nt < NT; ++nt) put(h3, nt * SH + sx);
             }
             NUNIF_REQUIRE((int)fi == nf, "internal: tail stream has %zu fragments, expected %d", fi, nf);
-            if ((rc = upload(h, stream, &bl.tail_stream))) return rc;
+            if ((rc = h->upload(stream, &bl.tail_stream))) return rc;
             if (dim == 192) {
                 // weight-stationary tail: output-channel slice w of 4 owns proj / mlp.3 tiles 3w..3w+2 and mlp.0 tiles 6w..6w+5
                 //   Wp [w][nt 3][ks 6] (plain k order) | W0 [w][nt 6][ks 6] | W3 [w][nt 3][ks 12] (both chained)
                 std::vector<f16> ws((size_t)proj_mlp_ws_stream_frags() * 512, (f16)0.0f);
                 size_t wi = 0;
-                auto putw = [&](const std::vector<f16> &src, int frag) {
-                    std::copy(src.begin() + (size_t)frag * 512, src.begin() + (size_t)(frag + 1) * 512, ws.begin() + wi * 512);
-                    ++wi;
-                };
+                auto putw = [&](const std::vector<f16> &src, int frag) { copy_frag(src, frag, ws, &wi); };
                 for (int w = 0; w < 4; ++w)
                     for (int nt = 0; nt < 3; ++nt)
                         for (int ks = 0; ks < KS; ++ks) putw(hp, (3 * w + nt) * KS + ks);
@@ -271,7 +193,7 @@ int make_stage(nunif_swin_unet *h, const TensorMap &m, const std::string &key, i
                     for (int nt = 0; nt < 3; ++nt)
                         for (int ks = 0; ks < SH; ++ks) putw(h3, (3 * w + nt) * SH + ks);
                 NUNIF_REQUIRE((int)wi == proj_mlp_ws_stream_frags(), "internal: ws tail stream has %zu fragments", wi);
-                if ((rc = upload(h, ws, &bl.tail_ws))) return rc;
+                if ((rc = h->upload(ws, &bl.tail_ws))) return rc;
             }
         }
         const HostTensor *tab;
@@ -283,14 +205,11 @@ int make_stage(nunif_swin_unet *h, const TensorMap &m, const std::string &key, i
             const HostTensor *pw;
             if ((rc = find(m, p + "attn.proj.weight", &pw))) return rc;
             const float *pd = pw->data;
-            std::vector<f16> hpc = pack_a_fragments(dim, dim, [=](int n, int k) { return pd[(size_t)n * dim + k]; }, true);
+            std::vector<f16> hpc = pack_nt_ks(dim, dim, dim, [=](int n, int k) { return pd[(size_t)n * dim + k]; }, true);
             const int KS = dim / 32, NT = dim / 16, SH = 2 * dim / 32;
             std::vector<f16> stream((size_t)swin_block96_tail_frags() * 512, (f16)0.0f);
             size_t fi = 0;
-            auto put = [&](const std::vector<f16> &src, int frag) {
-                std::copy(src.begin() + (size_t)frag * 512, src.begin() + (size_t)(frag + 1) * 512, stream.begin() + fi * 512);
-                ++fi;
-            };
+            auto put = [&](const std::vector<f16> &src, int frag) { copy_frag(src, frag, stream, &fi); };
             for (int sx = 0; sx < KS; ++sx)
                 for (int ks = 0; ks < KS; ++ks) { put(hpc, (2 * sx) * KS + ks); put(hpc, (2 * sx + 1) * KS + ks); }
             for (int sx = 0; sx < SH; ++sx) {
@@ -298,7 +217,7 @@ int make_stage(nunif_swin_unet *h, const TensorMap &m, const std::string &key, i
                 for (int nt = 0; nt < NT; ++nt) put(h3, nt * SH + sx);
             }
             NUNIF_REQUIRE((int)fi == swin_block96_tail_frags(), "internal: block96 stream has %zu fragments", fi);
-            if ((rc = upload(h, stream, &bl.b96_tail))) return rc;
+            if ((rc = h->upload(stream, &bl.b96_tail))) return rc;
             // R[h][i] = log2(e) * table[120 - i][h]: the keys of a 2 x 2 block are then at +0, +1, +11, +12 from the
             // lane's index (swin_block96.hip); floats 124.. of a head = -1000 (padded keys)
             const int stride = swin_block96_btab_floats() / heads;
@@ -307,7 +226,7 @@ int make_stage(nunif_swin_unet *h, const TensorMap &m, const std::string &key, i
                 for (int i2 = 0; i2 < 121; ++i2) rt[(size_t)hh * stride + i2] = tab->data[(size_t)(120 - i2) * heads + hh] * 1.4426950408889634f;
                 rt[(size_t)hh * stride + 121] = rt[(size_t)hh * stride + 122] = rt[(size_t)hh * stride + 123] = 0.0f;
             }
-            if ((rc = upload(h, rt, &bl.b96_btab))) return rc;
+            if ((rc = h->upload(rt, &bl.b96_btab))) return rc;
         }
         // bias[h][q][key] = table[(yq-yk+5)*11 + (xq-xk+5)][h]  (torchvision relative_position_index, window 6x6);
         // the 12 padding key columns get -1e30 so that exp() makes them exactly 0.
@@ -322,7 +241,7 @@ int make_stage(nunif_swin_unet *h, const TensorMap &m, const std::string &key, i
                     }
                     bias[((size_t)hh * 36 + q) * 48 + k] = v;
                 }
-        if ((rc = upload(h, bias, &bl.attn_bias))) return rc;
+        if ((rc = h->upload(bias, &bl.attn_bias))) return rc;
         // fp32 table read as the MFMA C operand: [heads][36 queries][52], log2(e) * bias.  Key COLUMNS follow the token
         // placement of qkv_attn_r_kernel (win_token, swin_qkv_attn_r.hip): columns 0..31 = keys 0..31, column 32 + 4 g =
         // key 32 + g (register 0 of lane group g in key tile 2); the other columns of tile 2 are padding the kernel never
@@ -335,7 +254,7 @@ int make_stage(nunif_swin_unet *h, const TensorMap &m, const std::string &key, i
                     btab32[((size_t)hh * 36 + q) * 52 + k] =
                         key >= 0 ? bias[((size_t)hh * 36 + q) * 48 + key] * 1.4426950408889634f : -1000.0f;
                 }
-        if ((rc = upload(h, btab32, &bl.attn_btab32))) return rc;
+        if ((rc = h->upload(btab32, &bl.attn_btab32))) return rc;
     }
     return NUNIF_HIP_OK;
 }
@@ -590,17 +509,7 @@ extern "C" int nunif_hip_swin_unet_create(const nunif_tensor_desc *tensors, int3
     NUNIF_REQUIRE(tensors && handle && n_tensors > 0, "swin_unet_create: NULL argument");
     NUNIF_REQUIRE(scale_factor == 1 || scale_factor == 2 || scale_factor == 4 || scale_factor == 8,
                   "swin_unet_create: scale_factor %d unsupported (1, 2, 4, 8)", scale_factor);
-    TensorMap m;
-    for (int i = 0; i < n_tensors; ++i) {
-        HostTensor t;
-        t.data = tensors[i].data;
-        t.numel = 1;
-        for (int d = 0; d < tensors[i].ndim; ++d) {
-            t.shape.push_back(tensors[i].shape[d]);
-            t.numel *= tensors[i].shape[d];
-        }
-        m[tensors[i].name] = t;
-    }
+    const TensorMap m = tensor_map(tensors, n_tensors);
     nunif_swin_unet *h = new nunif_swin_unet();
     (void)hipGetDevice(&h->device);
     if (const char *v = getenv("NUNIF_BLOCK96")) h->block96 = atoi(v);
@@ -626,7 +535,7 @@ extern "C" int nunif_hip_swin_unet_create(const nunif_tensor_desc *tensors, int3
         h->top_dim = h->has_proj2 ? 2 * C : C;
         {
             std::vector<float> w(w0->data, w0->data + w0->numel), b(b0->data, b0->data + b0->numel);
-            if ((rc = upload(h, w, &h->stem1_w)) || (rc = upload(h, b, &h->stem1_b))) break;
+            if ((rc = h->upload(w, &h->stem1_w)) || (rc = h->upload(b, &h->stem1_b))) break;
         }
         {   // conv2 [C][C1][3][3] -> W[n][k = (dy*3+dx)*C1P + ci], zero for the padded input channels
             const float *wd = w2->data;
@@ -639,18 +548,13 @@ extern "C" int nunif_hip_swin_unet_create(const nunif_tensor_desc *tensors, int3
         }
         if (stem_fused_supported(C1, C)) {
             const float *w0d = w0->data, *b0d = b0->data, *wd = w2->data;
-            std::vector<f16> p1 = pack_a_fragments(C1, 32, [=](int n, int k) {
-                return k < 27 ? w0d[(size_t)n * 27 + k] : (k == 27 ? b0d[n] : 0.0f); }, false);
-            const int K2 = 448, KS = K2 / 32, NT = C / 16;
-            std::vector<f16> p2 = pack_a_fragments(C, K2, [=](int n, int k) {
+            std::vector<f16> p1 = pack_nt_ks(C1, pad16(C1), 32, [=](int n, int k) {
+                return k < 27 ? w0d[(size_t)n * 27 + k] : (k == 27 ? b0d[n] : 0.0f); });
+            const int K2 = 448;
+            std::vector<f16> stream = pack_ks_nt(C, C, K2, [=](int n, int k) {
                 const int tap = k / C1, ci = k % C1;
-                return k < 9 * C1 ? wd[((size_t)n * C1 + ci) * 9 + tap] : 0.0f; }, false);
-            std::vector<f16> stream((size_t)KS * NT * 512, (f16)0.0f);
-            for (int ks = 0; ks < KS; ++ks)
-                for (int nt = 0; nt < NT; ++nt)
-                    std::copy(p2.begin() + ((size_t)nt * KS + ks) * 512, p2.begin() + ((size_t)nt * KS + ks + 1) * 512,
-                              stream.begin() + ((size_t)ks * NT + nt) * 512);
-            if ((rc = upload(h, p1, &h->stemf_w1)) || (rc = upload(h, stream, &h->stemf_w2))) break;
+                return k < 9 * C1 ? wd[((size_t)n * C1 + ci) * 9 + tap] : 0.0f; }, false, 0);
+            if ((rc = h->upload(p1, &h->stemf_w1)) || (rc = h->upload(stream, &h->stemf_w2))) break;
         }
         if ((rc = make_stage(h, m, P + "swin1", C, 2, &h->swin[0]))) break;
         if ((rc = make_stage(h, m, P + "swin2", 2 * C, 2, &h->swin[1]))) break;
@@ -717,8 +621,8 @@ extern "C" int nunif_hip_swin_unet_create(const nunif_tensor_desc *tensors, int3
             if ((rc = find(m, P + "to_image.proj.weight", &tw))) break;
             const float *wd = tw->data;
             const int nr = 3 * scale_factor * scale_factor, K = h->top_dim;
-            std::vector<f16> ch = pack_a_fragments(nr, K, [=](int n, int k) { return wd[(size_t)n * K + k]; }, true);
-            if ((rc = upload(h, ch, &h->to_image_chained))) break;
+            std::vector<f16> ch = pack_nt_ks(nr, pad16(nr), K, [=](int n, int k) { return wd[(size_t)n * K + k]; }, true);
+            if ((rc = h->upload(ch, &h->to_image_chained))) break;
         }
     } while (0);
     if (rc) {
@@ -754,7 +658,7 @@ extern "C" int nunif_hip_swin_unet_get_tap(nunif_swin_unet *h, int32_t index, ch
 extern "C" void nunif_hip_swin_unet_destroy(nunif_swin_unet *h) {
     if (!h) return;
     h->clear_taps();
-    for (void *p : h->owned) (void)hipFree(p);
+    h->free_all();
     for (DeviceBuf *b : {&h->s1, &h->f1, &h->f2, &h->f3, &h->g1, &h->qkv, &h->att, &h->hid, &h->tile_out, &h->winmap[0], &h->winmap[1]}) b->release();
     delete h;
 }

@@ -16,10 +16,10 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
+#include "host_weights.h"
 #include "swin_kernels.h"
 
 namespace nunif {
@@ -272,29 +272,6 @@ using namespace nunif;
 // =====================================================================================================================
 namespace {
 
-struct HostT { const float *data; std::vector<int64_t> shape; int64_t numel; };
-typedef std::map<std::string, HostT> TMap;
-
-int find(const TMap &m, const std::string &key, const HostT **out) {
-    auto it = m.find(key);
-    if (it == m.end()) { set_error("state_dict is missing '%s'", key.c_str()); return NUNIF_HIP_EMISSING; }
-    *out = &it->second;
-    return NUNIF_HIP_OK;
-}
-
-struct Buf {
-    void *p = nullptr; size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return NUNIF_HIP_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        if (hipMalloc(&p, bytes) != hipSuccess) { set_error("hipMalloc(%zu) failed", bytes); return NUNIF_HIP_ENOMEM; }
-        cap = bytes;
-        return NUNIF_HIP_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-
 struct Lin { f16 *w = nullptr; float *b = nullptr; int N = 0, n_real = 0, K = 0; };       // gemm_kernel packing [nt][ks]
 struct Conv3 { f16 *w = nullptr; float *b = nullptr; int Cin = 0, N = 0; };                 // conv_kernel stream [ks][nt]
 
@@ -307,74 +284,47 @@ struct WacBlock {
 
 }  // namespace
 
-struct nunif_swin_unet_v2 {
+struct nunif_swin_unet_v2 : DeviceOwner {
     int scale = 2, C = 96, C2 = 192;
-    std::vector<void *> owned;
     float *ir1_w = nullptr, *ir1_b = nullptr, *ir2_w = nullptr, *ir2_b = nullptr, *res_w = nullptr, *scale_bias = nullptr;
     WacBlock ir_blk[2];
     Conv3 patch;
     std::vector<WacBlock> wac1, wac2, wac3;
     Lin down1, up1, to_image;
-    Buf ir, irf, irf2, f1, f1b, skip, f2, f2b, tmpA, tmpB, qkv, rimg;
+    DeviceBuf ir, irf, irf2, f1, f1b, skip, f2, f2b, tmpA, tmpB, qkv, rimg;
 };
 
 namespace {
-
-template <typename T>
-int upload(nunif_swin_unet_v2 *h, const std::vector<T> &host, T **dev) {
-    void *p = nullptr;
-    if (hipMalloc(&p, host.size() * sizeof(T)) != hipSuccess) { set_error("hipMalloc failed"); return NUNIF_HIP_ENOMEM; }
-    h->owned.push_back(p);
-    NUNIF_HIP_CHECK(hipMemcpy(p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
-    *dev = reinterpret_cast<T *>(p);
-    return NUNIF_HIP_OK;
-}
-
-// MFMA A fragment (nt, ks): lane l holds W[nt*16 + (l&15)][ks*32 + (l>>4)*8 + j], j = 0..7
-template <typename F>
-void put_frag(std::vector<f16> &dst, size_t frag, int nt, int ks, F wt) {
-    for (int l = 0; l < 64; ++l)
-        for (int j = 0; j < 8; ++j)
-            dst[(frag * 64 + l) * 8 + j] = (f16)wt(nt * 16 + (l & 15), ks * 32 + (l >> 4) * 8 + j);
-}
 
 // rows n < n_real of a [n_real][K_real] matrix (wt), zero beyond; K padded to a multiple of 32
 template <typename F, typename G>
 int make_lin(nunif_swin_unet_v2 *h, int n_real, int K_real, F wt, G bias, Lin *L) {
     const int N = (n_real + 15) / 16 * 16, K = (K_real + 31) / 32 * 32;
-    std::vector<f16> packed((size_t)N * K + 8192, (f16)0.f);      // + 16 KiB: the ring prefetches one chunk past the end
-    for (int nt = 0; nt < N / 16; ++nt)
-        for (int ks = 0; ks < K / 32; ++ks)
-            put_frag(packed, (size_t)nt * (K / 32) + ks, nt, ks,
-                     [&](int n, int k) { return (n < n_real && k < K_real) ? wt(n, k) : 0.f; });
+    std::vector<f16> packed = pack_nt_ks(n_real, N, K, [&](int n, int k) { return k < K_real ? wt(n, k) : 0.f; });
     std::vector<float> b(N, 0.f);
     for (int n = 0; n < n_real; ++n) b[n] = bias(n);
     L->N = N; L->n_real = n_real; L->K = K;
-    int rc = upload(h, packed, &L->w);
-    return rc ? rc : upload(h, b, &L->b);
+    int rc = h->upload(packed, &L->w);
+    return rc ? rc : h->upload(b, &L->b);
 }
 
 // 3x3 conv [N][Cin][3][3] -> conv_kernel stream, k = tap * Cin + ci
-int make_conv3(nunif_swin_unet_v2 *h, const HostT *w, const HostT *b, int N, int Cin, Conv3 *cv) {
+int make_conv3(nunif_swin_unet_v2 *h, const HostTensor *w, const HostTensor *b, int N, int Cin, Conv3 *cv) {
     NUNIF_REQUIRE(w->numel == (int64_t)N * Cin * 9 && b->numel == N && Cin % 32 == 0 && N % 16 == 0, "3x3 conv shape");
-    const int NT = N / 16, KS = 9 * Cin / 32;
-    std::vector<f16> stream((size_t)KS * NT * 512 + 8192, (f16)0.f);
     const float *wd = w->data;
-    for (int ks = 0; ks < KS; ++ks)
-        for (int nt = 0; nt < NT; ++nt)
-            put_frag(stream, (size_t)ks * NT + nt, nt, ks, [=](int n, int k) {
-                const int tap = k / Cin, ci = k % Cin;
-                return wd[((size_t)n * Cin + ci) * 9 + tap]; });
+    std::vector<f16> stream = pack_ks_nt(N, N, 9 * Cin, [=](int n, int k) {
+        const int tap = k / Cin, ci = k % Cin;
+        return wd[((size_t)n * Cin + ci) * 9 + tap]; });
     std::vector<float> bb(b->data, b->data + N);
     cv->Cin = Cin; cv->N = N;
-    int rc = upload(h, stream, &cv->w);
-    return rc ? rc : upload(h, bb, &cv->b);
+    int rc = h->upload(stream, &cv->w);
+    return rc ? rc : h->upload(bb, &cv->b);
 }
 
 double gelu_erf_d(double v) { return 0.5 * v * (1.0 + erf(v * 0.70710678118654752440)); }
 
-int make_wac(nunif_swin_unet_v2 *h, const TMap &m, const std::string &p, int C, int heads, int ws, int shift, WacBlock *bk) {
-    const HostT *wqkv, *bqkv, *wp, *bp, *nw, *w1, *b1, *w2, *b2, *tw0, *tb0, *tw2, *tb2;
+int make_wac(nunif_swin_unet_v2 *h, const TensorMap &m, const std::string &p, int C, int heads, int ws, int shift, WacBlock *bk) {
+    const HostTensor *wqkv, *bqkv, *wp, *bp, *nw, *w1, *b1, *w2, *b2, *tw0, *tb0, *tw2, *tb2;
     int rc;
     if ((rc = find(m, p + "mha.mha.qkv_proj.weight", &wqkv)) || (rc = find(m, p + "mha.mha.qkv_proj.bias", &bqkv)) ||
         (rc = find(m, p + "mha.mha.head_proj.weight", &wp)) || (rc = find(m, p + "mha.mha.head_proj.bias", &bp)) ||
@@ -395,12 +345,12 @@ int make_wac(nunif_swin_unet_v2 *h, const TMap &m, const std::string &p, int C, 
             return rc;
         std::vector<float> bq(3 * C);
         for (int n = 0; n < 3 * C; ++n) bq[n] = bd[n] * (n < C ? qs : 1.f);
-        if ((rc = upload(h, bq, &bk->bqkv))) return rc;
+        if ((rc = h->upload(bq, &bk->bqkv))) return rc;
         const float *pd = wp->data, *pb = bp->data;
         if ((rc = make_lin(h, C, C, [=](int n, int k) { return pd[(size_t)n * C + k]; }, [=](int n) { return pb[n]; }, &bk->proj)))
             return rc;
         std::vector<float> g(nw->data, nw->data + C);
-        if ((rc = upload(h, g, &bk->norm))) return rc;
+        if ((rc = h->upload(g, &bk->norm))) return rc;
     }
     {   // WindowScoreBias (attention.py:375-419): the to_bias MLP on the normalised relative offsets, evaluated once here
         const int hidden = (int)tb0->numel, N = ws * ws;
@@ -416,7 +366,7 @@ int make_wac(nunif_swin_unet_v2 *h, const TMap &m, const std::string &p, int C, 
                                                             (double)tb0->data[j]);
                 tab[(size_t)q * N + k] = (float)o * 1.4426950408889634f;
             }
-        if ((rc = upload(h, tab, &bk->btab))) return rc;
+        if ((rc = h->upload(tab, &bk->btab))) return rc;
     }
     const int mid = (int)w1->shape[0];
     bk->mid = mid;
@@ -512,31 +462,24 @@ extern "C" int nunif_hip_swin_unet_v2_create(const nunif_tensor_desc *tensors, i
     NUNIF_REQUIRE(tensors && handle && n_tensors > 0, "swin_unet_v2_create: NULL argument");
     NUNIF_REQUIRE(scale_factor == 1 || scale_factor == 2 || scale_factor == 4, "swin_unet_v2_create: scale_factor %d (1, 2, 4)",
                   scale_factor);
-    TMap m;
-    for (int i = 0; i < n_tensors; ++i) {
-        HostT t;
-        t.data = tensors[i].data;
-        t.numel = 1;
-        for (int d = 0; d < tensors[i].ndim; ++d) { t.shape.push_back(tensors[i].shape[d]); t.numel *= tensors[i].shape[d]; }
-        m[tensors[i].name] = t;
-    }
+    const TensorMap m = tensor_map(tensors, n_tensors);
     nunif_swin_unet_v2 *h = new nunif_swin_unet_v2();
     h->scale = scale_factor;
     const std::string P = "unet.";
     int rc = NUNIF_HIP_OK;
     do {
-        const HostT *w, *b;
+        const HostTensor *w, *b;
         if ((rc = find(m, P + "ir.path1.0.weight", &w)) || (rc = find(m, P + "ir.path1.0.bias", &b))) break;
         if (w->numel != 16 * 27 || b->numel != 16) { set_error("swin_unet_v2: IR(3, 32) expected"); rc = NUNIF_HIP_EUNSUPPORTED; break; }
         {
             std::vector<float> wv(w->data, w->data + w->numel), bv(b->data, b->data + b->numel);
-            if ((rc = upload(h, wv, &h->ir1_w)) || (rc = upload(h, bv, &h->ir1_b))) break;
+            if ((rc = h->upload(wv, &h->ir1_w)) || (rc = h->upload(bv, &h->ir1_b))) break;
         }
         if ((rc = find(m, P + "ir.path2.1.weight", &w)) || (rc = find(m, P + "ir.path2.1.bias", &b))) break;
         if (w->numel != 64 * 12 || b->numel != 64) { set_error("swin_unet_v2: IR path2 conv 12 -> 64 expected"); rc = NUNIF_HIP_EUNSUPPORTED; break; }
         {
             std::vector<float> wv(w->data, w->data + w->numel), bv(b->data, b->data + b->numel);
-            if ((rc = upload(h, wv, &h->ir2_w)) || (rc = upload(h, bv, &h->ir2_b))) break;
+            if ((rc = h->upload(wv, &h->ir2_w)) || (rc = h->upload(bv, &h->ir2_b))) break;
         }
         if ((rc = make_wac(h, m, P + "ir.path2.2.", 64, 2, 8, 1, &h->ir_blk[0])) ||
             (rc = make_wac(h, m, P + "ir.path2.3.", 64, 2, 8, 0, &h->ir_blk[1])))
@@ -594,7 +537,7 @@ extern "C" int nunif_hip_swin_unet_v2_create(const nunif_tensor_desc *tensors, i
         if (w->numel != (int64_t)3 * s2 * 27 || b->numel != 1) { set_error("swin_unet_v2: to_image shape"); rc = NUNIF_HIP_EINVAL; break; }
         {
             std::vector<float> wv(w->data, w->data + w->numel), bv(b->data, b->data + 1);
-            if ((rc = upload(h, wv, &h->res_w)) || (rc = upload(h, bv, &h->scale_bias))) break;
+            if ((rc = h->upload(wv, &h->res_w)) || (rc = h->upload(bv, &h->scale_bias))) break;
         }
     } while (0);
     if (rc) { nunif_hip_swin_unet_v2_destroy(h); return rc; }
@@ -604,8 +547,8 @@ extern "C" int nunif_hip_swin_unet_v2_create(const nunif_tensor_desc *tensors, i
 
 extern "C" void nunif_hip_swin_unet_v2_destroy(nunif_swin_unet_v2 *h) {
     if (!h) return;
-    for (void *p : h->owned) (void)hipFree(p);
-    for (Buf *b : {&h->ir, &h->irf, &h->irf2, &h->f1, &h->f1b, &h->skip, &h->f2, &h->f2b, &h->tmpA, &h->tmpB, &h->qkv, &h->rimg})
+    h->free_all();
+    for (DeviceBuf *b : {&h->ir, &h->irf, &h->irf2, &h->f1, &h->f1b, &h->skip, &h->f2, &h->f2b, &h->tmpA, &h->tmpB, &h->qkv, &h->rimg})
         b->release();
     delete h;
 }

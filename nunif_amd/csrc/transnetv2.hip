@@ -15,7 +15,7 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "host_weights.h"
 
 namespace nunif {
 namespace {
@@ -353,8 +353,7 @@ void launch(const GemmArgs &g, int nz, hipStream_t s) {
 
 using namespace nunif;
 
-struct nunif_transnetv2 {
-    std::vector<void *> owned;
+struct nunif_transnetv2 : DeviceOwner {
     Layer layer[3][2];
     float *proj_wt = nullptr, *proj_b = nullptr, *sim_wt = nullptr, *sim_b = nullptr, *hist_wt = nullptr, *hist_b = nullptr;
     float *fc1_wt = nullptr, *fc1_b = nullptr, *cls1_w = nullptr, *cls1_b = nullptr, *cls2_w = nullptr, *cls2_b = nullptr;
@@ -375,18 +374,13 @@ int fetch(nunif_transnetv2 *h, const std::map<std::string, const nunif_tensor_de
     size_t have = 1;
     for (int i = 0; i < it->second->ndim; ++i) have *= (size_t)it->second->shape[i];
     NUNIF_REQUIRE(have == n, "transnetv2_create: '%s' has %zu elements, expected %zu", name.c_str(), have, n);
-    void *p = nullptr;
-    if (hipMalloc(&p, n * sizeof(float)) != hipSuccess) { set_error("hipMalloc(%zu) failed", n * sizeof(float)); return NUNIF_HIP_ENOMEM; }
-    h->owned.push_back(p);
-    NUNIF_HIP_CHECK(hipMemcpy(p, it->second->data, n * sizeof(float), hipMemcpyHostToDevice));
-    *dev = (float *)p;
-    return NUNIF_HIP_OK;
+    return h->upload(std::vector<float>(it->second->data, it->second->data + n), dev);
 }
 }  // namespace
 
 extern "C" void nunif_hip_transnetv2_destroy(nunif_transnetv2 *h) {
     if (!h) return;
-    for (void *p : h->owned) (void)hipFree(p);
+    h->free_all();
     if (h->work) (void)hipFree(h->work);
     delete h;
 }
