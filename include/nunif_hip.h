@@ -457,6 +457,66 @@ int nunif_hip_sod_v1_depth_position(const float *saliency, const float *depth, i
                                     void *stream);
 int nunif_hip_sod_v1_ema(const float *z, float *out, int32_t B, float *state, double decay, uint64_t reset_mask, void *stream);
 
+/* stlizer's per-frame networks and warp (nunif/utils/superpoint.py), fp32 operands and accumulation throughout.
+ * Inputs must be finite, with one exception: texels of the warp's image may be NaN (they propagate as in torch).  A NaN score,
+ * descriptor or warp parameter is not treated as torch treats it: the NMS maximum skips a NaN where max_pool2d propagates it,
+ * match returns index 0 and a NaN similarity for a row with a NaN where torch.argmax returns the NaN's index, and the warp's
+ * border clamp turns a NaN coordinate into 0.
+ *
+ * SuperPoint :74-172 as `SuperPoint()` builds it (channels [64, 64, 128, 128, 256], descriptor_dim 256, stride 8), eval mode.
+ * create() takes the weights packed on the host (nunif_amd/nunif/utils/superpoint.py pack_weights); a VGGBlock :55-71 is
+ * conv -> ReLU -> BatchNorm(eps 1e-3), so the 3x3 convs carry their BN as a per-channel affine applied after the ReLU:
+ *   backbone.{0..3}.{0,1}.w  [9*Cin][Cout]   row = (kh*3+kw)*Cin + c;  .bias / .scale / .shift [Cout]
+ *   heads.w                  [1152][512]     detector.0 (columns 0..255) and descriptor.0 (256..511); .bias / .scale / .shift [512]
+ *   detector.w               [256][96]       detector.1 with its BN folded (relu=False), 65 real columns; detector.bias [96]
+ *   descriptor.w             [256][256]      descriptor.1 with its BN folded; descriptor.bias [256]
+ * forward :111-149: image [B,C,H,W] f32 device, C = 3 (reduced to gray :112-114 inside the first conv's gather) or 1; H, W >= 8,
+ * any size (each of the three 2x2 max-pools floors).  With h = H/8, w = W/8 (floored three times) it leaves in the handle the
+ * score map [B,8h,8w] (softmax over 65, dustbin dropped, depth-to-space :122-128) and the L2-normalised dense descriptors
+ * [B,h,w,256] (channels-last), then runs nunif_hip_superpoint_keypoints on the score map.  keypoints [B][8h*8w][2] f32 (x, y),
+ * kp_scores [B][8h*8w] f32 and counts [B] i32 are device buffers; image b has counts[b] valid entries in the row-major order of
+ * torch.where.  keypoints may be NULL (dense outputs only).  The launch plan (buffer layout of one input shape) is kept in the
+ * handle and rebuilt when (B, H, W) changes; calls on one handle must be ordered (one stream at a time).
+ * debug_taps copies one buffer of the last forward: "backbone.0" .. "backbone.3" (block outputs, after the pool where the block
+ * has one), "heads", "descriptors" (all [B,h,w,C] channels-last), "scores", "nms" ([B,1,8h,8w]); shape4 receives the shape.
+ * sample: sample_descriptors :16-27 of the last forward's dense map of image b at n keypoints (x, y) -> out [n][256]. */
+typedef struct nunif_superpoint nunif_superpoint;
+int nunif_hip_superpoint_create(const nunif_tensor_desc *tensors, int32_t n_tensors, nunif_superpoint **handle);
+void nunif_hip_superpoint_destroy(nunif_superpoint *handle);
+int nunif_hip_superpoint_forward(nunif_superpoint *handle, const float *image, int32_t B, int32_t C, int32_t H, int32_t W,
+                                 int32_t nms_radius, int32_t remove_borders, float threshold, float *keypoints,
+                                 float *kp_scores, int32_t *counts, void *stream);
+int nunif_hip_superpoint_debug_taps(nunif_superpoint *handle, const char *name, float *out, int64_t capacity, int64_t *shape4,
+                                    void *stream);
+int nunif_hip_superpoint_sample(nunif_superpoint *handle, int32_t b, const float *keypoints, int32_t n, float *out,
+                                void *stream);
+
+/* batched_nms :30-45 (radius 0..8; cells outside the image count as -inf, as in max_pool2d), the remove_borders band set to -1
+ * :132-137, `score > threshold` and the row-major compaction of torch.where :141-149, on score maps [B,H,W] f32.  Comparisons
+ * only: exact for finite scores.  work: nunif_hip_superpoint_keypoints_work_floats(B, H, W) floats; nms_out [B,H,W] receives the suppressed map
+ * (with the band); keypoints [B][H*W][2] / kp_scores [B][H*W] / counts [B] as in forward, or keypoints NULL for the map only. */
+int64_t nunif_hip_superpoint_keypoints_work_floats(int32_t B, int32_t H, int32_t W);
+int nunif_hip_superpoint_keypoints(const float *scores, int32_t B, int32_t H, int32_t W, int32_t nms_radius,
+                                   int32_t remove_borders, float threshold, float *work, float *nms_out, float *keypoints,
+                                   float *kp_scores, int32_t *counts, void *stream);
+
+/* sample_descriptors :16-27: bilinear grid_sample (align_corners=False, zeros padding) of a channels-last dense map [h,w,C]
+ * (C % 4 == 0, C <= 1024) at (kp + 0.5) / (stride * [w, h]), then the L2 norm over C; keypoints [n][2] (x, y), out [n][C]. */
+int nunif_hip_sample_descriptors(const float *keypoints, int32_t n, const float *dense, int32_t h, int32_t w, int32_t C,
+                                 int32_t stride, float *out, void *stream);
+
+/* find_match_index :206-223 up to its threshold filter: for every row of d1 [n1][D] the max and argmax over j of <d1[i], d2[j]>,
+ * d2 [n2][D]; on equal values the lowest j wins, as torch.argmax.  The n1 x n2 matrix is never written.  work: n1 * 8 bytes;
+ * index [n1] i64, max_similarity [n1] f32.  n1, n2 >= 1, D % 4 == 0. */
+int nunif_hip_superpoint_match(const float *d1, int32_t n1, const float *d2, int32_t n2, int32_t D, void *work, int64_t *index,
+                               float *max_similarity, void *stream);
+
+/* apply_transform :330-378: x, out [B,C,H,W] f32 (distinct buffers); params [B][6] f32 device = shift x, shift y, scale, angle in
+ * degrees, center x, center y.  Inverse rotation / scale / shift about the center in fp32 in the reference's order, then a
+ * four-tap bilinear grid_sample with align_corners=False; padding_mode 0 zeros, 1 border (NUNIF_HIP_EUNSUPPORTED otherwise). */
+int nunif_hip_affine_warp(const float *x, const float *params, float *out, int32_t B, int32_t C, int32_t H, int32_t W,
+                          int32_t padding_mode, void *stream);
+
 /* Test hooks (tests/ only): snapshot every stage's NHWC fp16 output during the next forward calls, then read
  * them back one by one (returns 1 past the last tap).  Names match oracle.swin_unet.unet_forward(taps=...). */
 int nunif_hip_swin_unet_debug_taps(nunif_swin_unet *handle, int32_t enable);

@@ -142,6 +142,18 @@ SIGNATURES = {
                                               c_void_p]),
     "nunif_hip_sod_v1_depth_position": (c_int32, [c_void_p, c_void_p, c_int32, c_int64, c_double, c_void_p, c_void_p]),
     "nunif_hip_sod_v1_ema": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_double, c_uint64, c_void_p]),
+    "nunif_hip_superpoint_create": (c_int32, [ctypes.POINTER(TensorDesc), c_int32, ctypes.POINTER(c_void_p)]),
+    "nunif_hip_superpoint_destroy": (None, [c_void_p]),
+    "nunif_hip_superpoint_forward": (c_int32, [c_void_p, c_void_p] + [c_int32] * 6 + [c_float, c_void_p, c_void_p, c_void_p,
+                                              c_void_p]),
+    "nunif_hip_superpoint_debug_taps": (c_int32, [c_void_p, c_char_p, c_void_p, c_int64, ctypes.POINTER(c_int64), c_void_p]),
+    "nunif_hip_superpoint_sample": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
+    "nunif_hip_superpoint_keypoints_work_floats": (c_int64, [c_int32, c_int32, c_int32]),
+    "nunif_hip_superpoint_keypoints": (c_int32, [c_void_p] + [c_int32] * 5 + [c_float] + [c_void_p] * 6),
+    "nunif_hip_sample_descriptors": (c_int32, [c_void_p, c_int32, c_void_p] + [c_int32] * 4 + [c_void_p, c_void_p]),
+    "nunif_hip_superpoint_match": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                            c_void_p]),
+    "nunif_hip_affine_warp": (c_int32, [c_void_p, c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p]),
     "nunif_hip_swin_unet_debug_taps":(c_int32, [c_void_p, c_int32]),
     "nunif_hip_swin_unet_get_tap": (c_int32, [c_void_p, c_int32, c_char_p, c_int32, c_void_p, c_int64,
                                               ctypes.POINTER(c_int64)]),

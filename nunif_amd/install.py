@@ -72,6 +72,13 @@ PATCHES = [
     # --convergence-mode sod_v1 (iw3/convergence_estimator.py:11-84); iw3/utils.py:44 binds the class by name and picks the engine's
     # up as a consumer.  The net it loads (iw3.sod_v1 / iw3.dsod_v1) comes through the model registry below.
     ("iw3.convergence_estimator", "ConvergenceEstimator"),
+    # stlizer (stlizer/multipass_pipeline.py:162,190,445 reach these through `import nunif.utils.superpoint as KU` and KU.<name>
+    # attribute access, so re-binding them in the defining module is enough): the keypoint network of pass 1, descriptor matching,
+    # and the stabilising warp of pass 4 (nunif/utils/superpoint.py:74-203, :206-223, :330-378).  find_transform (:233-327, an
+    # autograd Adam loop) stays the reference's.  The module imports only torch: strict=True stays independent of PyAV and scipy.
+    ("nunif.utils.superpoint", "SuperPoint"),
+    ("nunif.utils.superpoint", "find_match_index"),
+    ("nunif.utils.superpoint", "apply_transform"),
 ]
 
 # reference packages whose modules may hold ``from ... import`` copies of a patched name

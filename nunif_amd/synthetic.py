@@ -692,3 +692,30 @@ def sod_v1_state_dict(seed, out_gain=0.04, out_bias=0.0):
     sd["u2netp.outconv.weight"] = (out_gain * sign * (0.75 + 0.5 * torch.rand(6, generator=g))).reshape(1, 6, 1, 1)
     sd["u2netp.outconv.bias"] = torch.tensor([float(out_bias)])
     return sd
+
+
+def superpoint_state_dict(seed):
+    """Seeded SuperPoint weights in the reference's key layout (``nunif/utils/superpoint.py``).  Convolutions get He gain so that
+    activations stay O(1) through the eight blocks, every bias is non-zero, and BatchNorm gets non-trivial statistics (scale
+    0.75-1.25, shift, a mean near the post-ReLU mean, variance 0.5-1.5) so that a wrong affine or a wrong fold shows.  The
+    detector's last conv is scaled by 6: the 65-way softmax is then peaky (scores up to 0.97-0.99) and a threshold of 0.01 leaves
+    tens to a few hundred keypoints per image instead of none."""
+    from .nunif.utils.superpoint import state_dict_shapes
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for key, shape in state_dict_shapes().items():
+        if key.endswith("num_batches_tracked"):
+            sd[key] = torch.tensor(100, dtype=torch.long)
+        elif key.endswith("bn.weight"):
+            sd[key] = 0.75 + 0.5 * torch.rand(shape, generator=g)
+        elif key.endswith("bn.running_var"):
+            sd[key] = 0.5 + torch.rand(shape, generator=g)
+        elif key.endswith("bn.running_mean"):
+            sd[key] = 0.3 + 0.2 * torch.randn(shape, generator=g)
+        elif key.endswith(".bias"):                              # conv.bias and bn.bias
+            sd[key] = 0.1 * torch.randn(shape, generator=g)
+        else:
+            fan_in = shape[1] * shape[2] * shape[3]
+            sd[key] = torch.randn(shape, generator=g) * math.sqrt(2.0 / fan_in)
+    sd["detector.1.conv.weight"] = sd["detector.1.conv.weight"] * 6.0
+    return sd
