@@ -24,6 +24,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import _hip
+from ..engine import HipEngine
 
 PATCH = 14
 
@@ -42,45 +43,20 @@ def interpolate_pos_embed(pos_embed, gh, gw):
     return torch.cat([cls, patch.permute(0, 2, 3, 1).reshape(1, gh * gw, EMBED)], dim=1)
 
 
-class HipDepthAnythingV2:
+class HipDepthAnythingV2(HipEngine):
     metric_depth = False
 
     def __init__(self, state_dict, device="cuda:0", taps=None, max_depth=0.0):
-        self.device = torch.device(device)
         self.taps = None if taps is None else tuple(int(t) for t in taps)
         self.max_depth = float(max_depth or 0.0)
         self.metric_depth = self.max_depth > 0
-        if self.device.type != "cuda":
-            raise RuntimeError("the Depth-Anything HIP engine needs a ROCm device; there is no CPU fallback")
+        # pos_embed stays on the host: it is resized per input grid (_pos) and handed to every forward
+        super().__init__(device, state_dict, "nunif_hip_depth_anything_create_ex", "nunif_hip_depth_anything_destroy",
+                         None if self.taps is None else (ctypes.c_int32 * 4)(*self.taps), ctypes.c_float(self.max_depth),
+                         label="Depth-Anything", skip=("pretrained.pos_embed",))
         self._state_dict = state_dict             # host tensors; kept so that replica() can build the same engine elsewhere
         self._pos_embed = state_dict["pretrained.pos_embed"].detach().float().cpu()
         self._pos_cache = {}
-        keep, descs = [], []
-        for name, t in state_dict.items():
-            if not torch.is_floating_point(t) or name == "pretrained.pos_embed":
-                continue
-            t = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
-            keep.append(t)
-            d = _hip.TensorDesc()
-            d.name, d.data, d.ndim = name.encode(), t.data_ptr(), min(t.dim(), 4)
-            for i, s in enumerate(t.shape[:4]):
-                d.shape[i] = s
-            descs.append(d)
-        arr = (_hip.TensorDesc * len(descs))(*descs)
-        handle = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            taps_arr = None if self.taps is None else (ctypes.c_int32 * 4)(*self.taps)
-            _hip.check(_hip.lib().nunif_hip_depth_anything_create_ex(arr, len(descs), taps_arr, ctypes.c_float(self.max_depth),
-                                                                    ctypes.byref(handle)))
-        self.handle = handle
-
-    def __del__(self):
-        h, self.handle = getattr(self, "handle", None), None
-        if h:
-            try:
-                _hip.lib().nunif_hip_depth_anything_destroy(h)
-            except Exception:
-                pass
 
     def eval(self):
         return self
@@ -107,9 +83,6 @@ class HipDepthAnythingV2:
             raise ValueError(f"expected [B,3,h,w] with h, w multiples of {PATCH}, got {tuple(x.shape)}")
         pos = self._pos(h // PATCH, w // PATCH)
         out = torch.empty((B, h, w), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().nunif_hip_depth_anything_forward(self.handle, ctypes.c_void_p(x.data_ptr()),
-                                                                   ctypes.c_void_p(pos.data_ptr()),
-                                                                   ctypes.c_void_p(out.data_ptr()), B, h, w,
-                                                                   _hip.current_stream_ptr(self.device)))
+        self.call(_hip.lib().nunif_hip_depth_anything_forward, self.handle, ctypes.c_void_p(x.data_ptr()),
+                  ctypes.c_void_p(pos.data_ptr()), ctypes.c_void_p(out.data_ptr()), B, h, w)
         return out

@@ -13,6 +13,7 @@ import torch
 
 from ...nunif.models import I2IBaseModel, register_model
 from ... import _hip
+from ...engine import FlatWeightsMixin, HipEngine
 from .row_flow_v3 import _score_bias_input
 
 
@@ -41,79 +42,15 @@ def _init_weights():
 
 
 @register_model
-class DepthAA(I2IBaseModel):
+class DepthAA(FlatWeightsMixin, I2IBaseModel):
     name = "iw3.depth_aa"
 
     def __init__(self):
         super().__init__({}, scale=1, offset=0, in_channels=1, blend_size=0)
-        self.register_buffer("_device_probe", torch.empty(0), persistent=False)
-        self._weights = _init_weights()
-        self._handle = None
-        self._handle_device = None
+        self._setup_weights(_init_weights())
 
-    def get_device(self):
-        return self._device_probe.device
-
-    def state_dict(self, *args, **kwargs):
-        return OrderedDict((k, v.clone()) for k, v in self._weights.items())
-
-    def load_state_dict(self, state_dict, strict=True, **kwargs):
-        missing = [k for k in self._weights if k not in state_dict]
-        unexpected = [k for k in state_dict if k not in self._weights]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Error(s) in loading state_dict for DepthAA: missing {missing[:4]}, unexpected {unexpected[:4]}")
-        for k in self._weights:
-            if k in state_dict:
-                v = state_dict[k].detach().to("cpu")
-                if v.shape != self._weights[k].shape:
-                    raise RuntimeError(f"size mismatch for {k}: {tuple(v.shape)} vs {tuple(self._weights[k].shape)}")
-                self._weights[k] = v.clone() if not torch.is_floating_point(v) else v.float().clone()
-        self._release()
-        return torch.nn.modules.module._IncompatibleKeys(missing, unexpected)
-
-    def parameters(self, recurse=True):
-        return iter(v for v in self._weights.values() if torch.is_floating_point(v))
-
-    def half(self):
-        return self
-
-    def float(self):
-        return self
-
-    def _release(self):
-        h, self._handle = self._handle, None
-        if h:
-            try:
-                _hip.lib().nunif_hip_depth_aa_destroy(h)
-            except Exception:
-                pass
-
-    def __del__(self):
-        self._release()
-
-    def _engine(self):
-        dev = self.get_device()
-        if dev.type != "cuda":
-            raise RuntimeError("the depth_aa HIP engine needs a ROCm device (model.to('cuda:N')); no CPU fallback")
-        if self._handle is None or self._handle_device != dev:
-            self._release()
-            keep, descs = [], []
-            for name, t in self._weights.items():
-                if not torch.is_floating_point(t):
-                    continue
-                t = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
-                keep.append(t)
-                d = _hip.TensorDesc()
-                d.name, d.data, d.ndim = name.encode(), t.data_ptr(), t.dim()
-                for i, s in enumerate(t.shape):
-                    d.shape[i] = s
-                descs.append(d)
-            arr = (_hip.TensorDesc * len(descs))(*descs)
-            handle = ctypes.c_void_p()
-            with torch.cuda.device(dev):
-                _hip.check(_hip.lib().nunif_hip_depth_aa_create(arr, len(descs), ctypes.byref(handle)))
-            self._handle, self._handle_device = handle, dev
-        return self._handle
+    def _make_engine(self, device):
+        return HipEngine(device, self._weights, "nunif_hip_depth_aa_create", "nunif_hip_depth_aa_destroy", label="depth_aa")
 
     def _run(self, x, mode):
         if self.training:
@@ -121,16 +58,13 @@ class DepthAA(I2IBaseModel):
         squeeze = x.ndim == 3
         if squeeze:
             x = x.unsqueeze(0)
-        dev = self.get_device()
-        handle = self._engine()
-        xin = x.to(device=dev, dtype=torch.float32).contiguous()
+        eng = self.engine()
+        xin = x.to(device=eng.device, dtype=torch.float32).contiguous()
         B, C, h, w = xin.shape
         assert C == 1
         y = torch.empty_like(xin)
-        with torch.cuda.device(dev):
-            _hip.check(_hip.lib().nunif_hip_depth_aa_forward(handle, ctypes.c_void_p(xin.data_ptr()),
-                                                             ctypes.c_void_p(y.data_ptr()), B, h, w, mode,
-                                                             _hip.current_stream_ptr(dev)))
+        eng.call(_hip.lib().nunif_hip_depth_aa_forward, eng.handle, ctypes.c_void_p(xin.data_ptr()), ctypes.c_void_p(y.data_ptr()),
+                 B, h, w, mode)
         y = y.to(x.dtype)
         return y.squeeze(0) if squeeze else y
 

@@ -14,6 +14,7 @@ import torch
 
 from ...nunif.models import I2IBaseModel, register_model
 from ... import _hip
+from ...engine import FlatWeightsMixin, HipEngine
 
 OFFSET = 16
 
@@ -52,92 +53,32 @@ def _init_weights():
     return sd
 
 
-class HipLightInpaintEngine:
+class HipLightInpaintEngine(HipEngine):
     def __init__(self, state_dict, device):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("the light_inpaint HIP engine needs a ROCm device (model.to('cuda:N')); no CPU fallback")
-        keep, descs = [], []
-        for name, t in state_dict.items():
-            t = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
-            keep.append(t)
-            d = _hip.TensorDesc()
-            d.name, d.data, d.ndim = name.encode(), t.data_ptr(), t.dim()
-            for i, s in enumerate(t.shape):
-                d.shape[i] = s
-            descs.append(d)
-        arr = (_hip.TensorDesc * len(descs))(*descs)
-        handle = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().nunif_hip_light_inpaint_create(arr, len(descs), ctypes.byref(handle)))
-        self.handle = handle
-
-    def __del__(self):
-        h, self.handle = getattr(self, "handle", None), None
-        if h:
-            try:
-                _hip.lib().nunif_hip_light_inpaint_destroy(h)
-            except Exception:
-                pass
+        super().__init__(device, state_dict, "nunif_hip_light_inpaint_create", "nunif_hip_light_inpaint_destroy",
+                         label="light_inpaint")
 
     def infer(self, x, mask, closing, inner_iter, outer_iter, mirror_x=False):
         B, C, H, W = x.shape
         assert C == 3 and tuple(mask.shape) == (B, 1, H, W)
         out = torch.empty_like(x)
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().nunif_hip_light_inpaint_infer_ex(
-                self.handle, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(mask.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                B, H, W, 1 if closing else 0, int(inner_iter), int(outer_iter), 1 if mirror_x else 0,
-                _hip.current_stream_ptr(self.device)))
+        self.call(_hip.lib().nunif_hip_light_inpaint_infer_ex, self.handle, ctypes.c_void_p(x.data_ptr()),
+                  ctypes.c_void_p(mask.data_ptr()), ctypes.c_void_p(out.data_ptr()), B, H, W, 1 if closing else 0, int(inner_iter),
+                  int(outer_iter), 1 if mirror_x else 0)
         return out
 
 
 @register_model
-class LightInpaintV1(I2IBaseModel):
+class LightInpaintV1(FlatWeightsMixin, I2IBaseModel):
     name = "inpaint.light_inpaint_v1"
 
     def __init__(self):
         super().__init__({}, scale=1, offset=OFFSET, in_channels=3, blend_size=8)
-        self.register_buffer("_device_probe", torch.empty(0), persistent=False)
         self.downscaling_factor, self.mod = 4, 16
-        self._weights = _init_weights()
-        self._engine = None
+        self._setup_weights(_init_weights())
 
-    def get_device(self):
-        return self._device_probe.device
-
-    def state_dict(self, *args, **kwargs):
-        return OrderedDict((k, v.clone()) for k, v in self._weights.items())
-
-    def load_state_dict(self, state_dict, strict=True, **kwargs):
-        missing = [k for k in self._weights if k not in state_dict]
-        unexpected = [k for k in state_dict if k not in self._weights]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Error(s) in loading state_dict for LightInpaintV1: missing {missing[:4]}, "
-                               f"unexpected {unexpected[:4]}")
-        for k in self._weights:
-            if k in state_dict:
-                v = state_dict[k].detach().to("cpu")
-                if v.shape != self._weights[k].shape:
-                    raise RuntimeError(f"size mismatch for {k}: {tuple(v.shape)} vs {tuple(self._weights[k].shape)}")
-                self._weights[k] = v.float().clone()
-        self._engine = None
-        return torch.nn.modules.module._IncompatibleKeys(missing, unexpected)
-
-    def parameters(self, recurse=True):
-        return iter(self._weights.values())
-
-    def half(self):
-        return self
-
-    def float(self):
-        return self
-
-    def engine(self):
-        dev = self.get_device()
-        if self._engine is None or self._engine.device != dev:
-            self._engine = HipLightInpaintEngine(self._weights, dev)
-        return self._engine
+    def _make_engine(self, device):
+        return HipLightInpaintEngine(self._weights, device)
 
     supports_mirror_x = True
 

@@ -13,6 +13,7 @@ from collections import OrderedDict
 import torch
 
 from ...nunif.models import I2IBaseModel, register_model
+from ...engine import FlatWeightsMixin
 from .light_inpaint_v1 import HipLightInpaintEngine
 
 SEQ_LEN = 12
@@ -54,7 +55,7 @@ def _init_weights(base_dim=96, lv2_mlp_ratio=1):
 
 
 @register_model
-class LightVideoInpaintV1(I2IBaseModel):
+class LightVideoInpaintV1(FlatWeightsMixin, I2IBaseModel):
     name = "inpaint.light_video_inpaint_v1"
     name_alias = ("inpaint.light_video_inpaint_v1_small",)
 
@@ -64,46 +65,11 @@ class LightVideoInpaintV1(I2IBaseModel):
         if (base_dim, lv2_mlp_ratio) not in ((96, 1), (128, 2), (192, 2)):
             raise ValueError("the HIP engine implements the registered variants: (base_dim, lv2_mlp_ratio) = (96, 1) small, "
                              "(128, 2) medium, (192, 2) large")
-        self.register_buffer("_device_probe", torch.empty(0), persistent=False)
         self.sequence_offset, self.downscaling_factor, self.mod = 0, 4, 16
-        self._weights = _init_weights(base_dim, lv2_mlp_ratio)
-        self._engine = None
+        self._setup_weights(_init_weights(base_dim, lv2_mlp_ratio))
 
-    def get_device(self):
-        return self._device_probe.device
-
-    def state_dict(self, *args, **kwargs):
-        return OrderedDict((k, v.clone()) for k, v in self._weights.items())
-
-    def load_state_dict(self, state_dict, strict=True, **kwargs):
-        missing = [k for k in self._weights if k not in state_dict]
-        unexpected = [k for k in state_dict if k not in self._weights]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Error(s) in loading state_dict for LightVideoInpaintV1: missing {missing[:4]}, "
-                               f"unexpected {unexpected[:4]}")
-        for k in self._weights:
-            if k in state_dict:
-                v = state_dict[k].detach().to("cpu")
-                if v.shape != self._weights[k].shape:
-                    raise RuntimeError(f"size mismatch for {k}: {tuple(v.shape)} vs {tuple(self._weights[k].shape)}")
-                self._weights[k] = v.float().clone()
-        self._engine = None
-        return torch.nn.modules.module._IncompatibleKeys(missing, unexpected)
-
-    def parameters(self, recurse=True):
-        return iter(self._weights.values())
-
-    def half(self):
-        return self
-
-    def float(self):
-        return self
-
-    def engine(self):
-        dev = self.get_device()
-        if self._engine is None or self._engine.device != dev:
-            self._engine = HipLightInpaintEngine(self._weights, dev)
-        return self._engine
+    def _make_engine(self, device):
+        return HipLightInpaintEngine(self._weights, device)
 
     supports_mirror_x = True
 

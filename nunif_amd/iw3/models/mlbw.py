@@ -16,6 +16,7 @@ import torch
 
 from ...nunif.models import I2IBaseModel, register_model, register_model_factory
 from ... import _hip
+from ...engine import FlatWeightsMixin, HipEngine
 from .row_flow_v3 import _score_bias_input
 
 OFFSET = 32
@@ -46,37 +47,11 @@ def _init_weights(num_layers, small, hole_mask=False):
     return sd
 
 
-class HipMLBWEngine:
+class HipMLBWEngine(HipEngine):
     def __init__(self, state_dict, device):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("the mlbw HIP engine needs a ROCm device (model.to('cuda:N')); no CPU fallback")
-        keep, descs = [], []
-        for name, t in state_dict.items():
-            if not torch.is_floating_point(t):
-                continue
-            t = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
-            keep.append(t)
-            d = _hip.TensorDesc()
-            d.name, d.data, d.ndim = name.encode(), t.data_ptr(), t.dim()
-            for i, s in enumerate(t.shape):
-                d.shape[i] = s
-            descs.append(d)
-        arr = (_hip.TensorDesc * len(descs))(*descs)
-        handle = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().nunif_hip_mlbw_create(arr, len(descs), ctypes.byref(handle)))
-        self.handle = handle
-        self.num_layers = _hip.lib().nunif_hip_mlbw_num_layers(handle)
-        self.hole_mask = bool(_hip.lib().nunif_hip_mlbw_has_hole_mask(handle))
-
-    def __del__(self):
-        h, self.handle = getattr(self, "handle", None), None
-        if h:
-            try:
-                _hip.lib().nunif_hip_mlbw_destroy(h)
-            except Exception:
-                pass
+        super().__init__(device, state_dict, "nunif_hip_mlbw_create", "nunif_hip_mlbw_destroy", label="mlbw")
+        self.num_layers = _hip.lib().nunif_hip_mlbw_num_layers(self.handle)
+        self.hole_mask = bool(_hip.lib().nunif_hip_mlbw_has_hole_mask(self.handle))
 
     def delta(self, x, flip=False):
         B, C, h, w = x.shape
@@ -84,18 +59,16 @@ class HipMLBWEngine:
         delta = torch.empty((B, self.num_layers, h, w), dtype=torch.float32, device=self.device)
         weight = torch.empty_like(delta)
         mask = torch.empty((B, 1, h, w), dtype=torch.float32, device=self.device) if self.hole_mask else None
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().nunif_hip_mlbw_delta_mask(
-                self.handle, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(delta.data_ptr()),
-                ctypes.c_void_p(weight.data_ptr()), ctypes.c_void_p(mask.data_ptr() if mask is not None else None),
-                B, h, w, 1 if flip else 0, _hip.current_stream_ptr(self.device)))
+        self.call(_hip.lib().nunif_hip_mlbw_delta_mask, self.handle, ctypes.c_void_p(x.data_ptr()),
+                  ctypes.c_void_p(delta.data_ptr()), ctypes.c_void_p(weight.data_ptr()),
+                  ctypes.c_void_p(mask.data_ptr() if mask is not None else None), B, h, w, 1 if flip else 0)
         if self.hole_mask:
             return delta, weight, mask          # mask logits are already flipped back to image coordinates
         return delta, weight
 
 
 @register_model
-class MLBW(I2IBaseModel):
+class MLBW(FlatWeightsMixin, I2IBaseModel):
     name = "sbs.mlbw"
 
     def __init__(self, num_layers=2, base_dim=32, small=False, cycle=False, hole_mask=False, **kwargs):
@@ -107,48 +80,14 @@ class MLBW(I2IBaseModel):
             raise NotImplementedError("the cycle (training) MLBW variant is not on the HIP engine")
         if hole_mask and num_layers != 2:
             raise ValueError("the hole-mask variant is registered for 2 layers only (sbs.mask_mlbw_l2)")
-        self.register_buffer("_device_probe", torch.empty(0), persistent=False)
         self.num_layers = num_layers
         self.cycle, self.hole_mask = cycle, hole_mask
         self.delta_output = False
         self.symmetric = False
-        self._weights = _init_weights(num_layers, small, hole_mask)
-        self._engine = None
+        self._setup_weights(_init_weights(num_layers, small, hole_mask))
 
-    def get_device(self):
-        return self._device_probe.device
-
-    def state_dict(self, *args, **kwargs):
-        return OrderedDict((k, v.clone()) for k, v in self._weights.items())
-
-    def load_state_dict(self, state_dict, strict=True, **kwargs):
-        missing = [k for k in self._weights if k not in state_dict]
-        unexpected = [k for k in state_dict if k not in self._weights]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Error(s) in loading state_dict for MLBW: missing {missing[:4]}, unexpected {unexpected[:4]}")
-        for k in self._weights:
-            if k in state_dict:
-                v = state_dict[k].detach().to("cpu")
-                if v.shape != self._weights[k].shape:
-                    raise RuntimeError(f"size mismatch for {k}: {tuple(v.shape)} vs {tuple(self._weights[k].shape)}")
-                self._weights[k] = v.clone() if not torch.is_floating_point(v) else v.float().clone()
-        self._engine = None
-        return torch.nn.modules.module._IncompatibleKeys(missing, unexpected)
-
-    def parameters(self, recurse=True):
-        return iter(v for v in self._weights.values() if torch.is_floating_point(v))
-
-    def half(self):
-        return self
-
-    def float(self):
-        return self
-
-    def engine(self):
-        dev = self.get_device()
-        if self._engine is None or self._engine.device != dev:
-            self._engine = HipMLBWEngine(self._weights, dev)
-        return self._engine
+    def _make_engine(self, device):
+        return HipMLBWEngine(self._weights, device)
 
     def infer_delta(self, x, flip=False):
         if self.training:

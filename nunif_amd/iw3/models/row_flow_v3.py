@@ -15,6 +15,7 @@ import torch
 
 from ...nunif.models import I2IBaseModel, register_model
 from ... import _hip
+from ...engine import FlatWeightsMixin, HipEngine
 
 OFFSET = 32
 
@@ -55,56 +56,27 @@ def _init_weights():
     return sd
 
 
-class HipRowFlowEngine:
+class HipRowFlowEngine(HipEngine):
     def __init__(self, state_dict, device):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("the row_flow_v3 HIP engine needs a ROCm device (model.to('cuda:N')); no CPU fallback")
-        keep, descs = [], []
-        for name, t in state_dict.items():
-            if not torch.is_floating_point(t):
-                continue                                   # bias.index (int64) is rebuilt from the window size
-            t = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
-            keep.append(t)
-            d = _hip.TensorDesc()
-            d.name, d.data, d.ndim = name.encode(), t.data_ptr(), t.dim()
-            for i, s in enumerate(t.shape):
-                d.shape[i] = s
-            descs.append(d)
-        arr = (_hip.TensorDesc * len(descs))(*descs)
-        handle = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().nunif_hip_row_flow_create(arr, len(descs), ctypes.byref(handle)))
-        self.handle = handle
-
-    def __del__(self):
-        h, self.handle = getattr(self, "handle", None), None
-        if h:
-            try:
-                _hip.lib().nunif_hip_row_flow_destroy(h)
-            except Exception:
-                pass
+        # (bias.index, int64, is left out: it is rebuilt from the window size)
+        super().__init__(device, state_dict, "nunif_hip_row_flow_create", "nunif_hip_row_flow_destroy", label="row_flow_v3")
 
     def delta(self, x, flip=False):
         B, C, h, w = x.shape
         assert C == 3
         out = torch.empty((B, 1, h, w), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().nunif_hip_row_flow_delta(self.handle, ctypes.c_void_p(x.data_ptr()),
-                                                           ctypes.c_void_p(out.data_ptr()), B, h, w, 1 if flip else 0,
-                                                           _hip.current_stream_ptr(self.device)))
+        self.call(_hip.lib().nunif_hip_row_flow_delta, self.handle, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                  B, h, w, 1 if flip else 0)
         return out
 
 
 @register_model
-class RowFlowV3(I2IBaseModel):
+class RowFlowV3(FlatWeightsMixin, I2IBaseModel):
     name = "sbs.row_flow_v3"
 
     def __init__(self):
         super().__init__({}, scale=1, offset=OFFSET, in_channels=8, blend_size=4)
-        self.register_buffer("_device_probe", torch.empty(0), persistent=False)
-        self._weights = _init_weights()
-        self._engine = None
+        self._setup_weights(_init_weights())
         self.delta_output = False
         self.symmetric = False
 
@@ -112,41 +84,8 @@ class RowFlowV3(I2IBaseModel):
     def delta_scale(self):
         return self._weights["delta_scale"]
 
-    def get_device(self):
-        return self._device_probe.device
-
-    def state_dict(self, *args, **kwargs):
-        return OrderedDict((k, v.clone()) for k, v in self._weights.items())
-
-    def load_state_dict(self, state_dict, strict=True, **kwargs):
-        missing = [k for k in self._weights if k not in state_dict]
-        unexpected = [k for k in state_dict if k not in self._weights]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Error(s) in loading state_dict for RowFlowV3: missing {missing[:4]}, "
-                               f"unexpected {unexpected[:4]}")
-        for k in self._weights:
-            if k in state_dict:
-                v = state_dict[k].detach().to("cpu")
-                if v.shape != self._weights[k].shape:
-                    raise RuntimeError(f"size mismatch for {k}: {tuple(v.shape)} vs {tuple(self._weights[k].shape)}")
-                self._weights[k] = v.clone() if not torch.is_floating_point(v) else v.float().clone()
-        self._engine = None
-        return torch.nn.modules.module._IncompatibleKeys(missing, unexpected)
-
-    def parameters(self, recurse=True):
-        return iter(v for v in self._weights.values() if torch.is_floating_point(v))
-
-    def half(self):
-        return self
-
-    def float(self):
-        return self
-
-    def engine(self):
-        dev = self.get_device()
-        if self._engine is None or self._engine.device != dev:
-            self._engine = HipRowFlowEngine(self._weights, dev)
-        return self._engine
+    def _make_engine(self, device):
+        return HipRowFlowEngine(self._weights, device)
 
     def infer_delta(self, x, flip=False):
         """[B,3,h,w] feature planes -> horizontal flow [B,1,h,w]; ``flip`` mirrors the planes inside the first kernel."""

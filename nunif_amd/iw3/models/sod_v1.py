@@ -14,6 +14,7 @@ import torch
 
 from ...nunif.models import I2IBaseModel, register_model
 from ... import _hip
+from ...engine import FlatWeightsMixin, HipEngine
 
 NET_SIZE = 192
 BN_EPS = 1e-5
@@ -98,40 +99,21 @@ TAP_NAMES = ("hx1", "hx2", "hx3", "hx4", "hx5", "hx6", "hx1d")
 
 
 @register_model
-class SODV1(I2IBaseModel):
+class SODV1(FlatWeightsMixin, I2IBaseModel):
     name = "iw3.sod_v1"
     name_alias = ("iw3.dsod_v1",)
 
     def __init__(self):
         super().__init__({}, scale=1, offset=0, in_channels=4, blend_size=0, in_size=NET_SIZE)
-        self.register_buffer("_device_probe", torch.empty(0), persistent=False)
-        self._weights = _init_weights()
-        self._handle = None
-        self._handle_device = None
+        self._setup_weights(_init_weights())
         self.eval()
 
-    def get_device(self):
-        return self._device_probe.device
+    def _param_filter(self, name, tensor):
+        return tensor.is_floating_point() and "running_" not in name
 
-    def state_dict(self, *args, **kwargs):
-        return OrderedDict((k, v.clone()) for k, v in self._weights.items())
-
-    def load_state_dict(self, state_dict, strict=True, **kwargs):
-        missing = [k for k in self._weights if k not in state_dict]
-        unexpected = [k for k in state_dict if k not in self._weights]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Error(s) in loading state_dict for SODV1: missing {missing[:4]}, unexpected {unexpected[:4]}")
-        for k in self._weights:
-            if k in state_dict:
-                v = state_dict[k].detach().to("cpu")
-                if v.shape != self._weights[k].shape:
-                    raise RuntimeError(f"size mismatch for {k}: {tuple(v.shape)} vs {tuple(self._weights[k].shape)}")
-                self._weights[k] = v.float().clone() if torch.is_floating_point(v) else v.clone()
-        self._release()
-        return torch.nn.modules.module._IncompatibleKeys(missing, unexpected)
-
-    def parameters(self, recurse=True):
-        return iter(v for k, v in self._weights.items() if torch.is_floating_point(v) and "running_" not in k)
+    def _make_engine(self, device):
+        return HipEngine(device, pack_weights(self._weights), "nunif_hip_sod_v1_create", "nunif_hip_sod_v1_destroy",
+                         self.i2i_in_size, label="sod_v1")
 
     def fuse(self, mode=True):          # BatchNorm is folded when the weights are packed
         return self
@@ -139,55 +121,16 @@ class SODV1(I2IBaseModel):
     def compile(self, mode=True):
         return self
 
-    def half(self):
-        return self
-
-    def float(self):
-        return self
-
     @staticmethod
     def to_feature(depth):
         return torch.cat([depth, depth ** 0.5, depth ** 2], dim=1)
-
-    def _release(self):
-        h = self.__dict__.get("_handle")
-        self.__dict__["_handle"] = None
-        if h:
-            try:
-                _hip.lib().nunif_hip_sod_v1_destroy(h)
-            except Exception:
-                pass
-
-    def __del__(self):
-        self._release()
-
-    def _engine(self):
-        dev = self.get_device()
-        if dev.type != "cuda":
-            raise RuntimeError("the sod_v1 HIP engine needs a ROCm device (model.to('cuda:N')); no CPU fallback")
-        if self._handle is None or self._handle_device != dev:
-            self._release()
-            packed = pack_weights(self._weights)
-            descs = []
-            for name, t in packed.items():
-                d = _hip.TensorDesc()
-                d.name, d.data, d.ndim = name.encode(), t.data_ptr(), t.dim()
-                for i, s in enumerate(t.shape):
-                    d.shape[i] = s
-                descs.append(d)
-            arr = (_hip.TensorDesc * len(descs))(*descs)
-            handle = ctypes.c_void_p()
-            with torch.cuda.device(dev):
-                _hip.check(_hip.lib().nunif_hip_sod_v1_create(arr, len(descs), self.i2i_in_size, ctypes.byref(handle)))
-            self._handle, self._handle_device = handle, dev
-        return self._handle
 
     def _infer(self, rgb, depth):
         """-> (saliency, depth resized, workspace of this run)."""
         if self.training:
             raise RuntimeError("the HIP engine is inference-only; call .eval()")
-        dev = self.get_device()
-        handle = self._engine()
+        eng = self.engine()
+        dev = eng.device
         rgb = rgb.to(device=dev, dtype=torch.float32).contiguous()
         depth = depth.to(device=dev, dtype=torch.float32).contiguous()
         assert rgb.ndim == 4 and rgb.shape[1] == 3 and depth.ndim == 4 and depth.shape[1] == 1 and depth.shape[0] == rgb.shape[0]
@@ -195,11 +138,9 @@ class SODV1(I2IBaseModel):
         sal = torch.empty((B, 1, s, s), dtype=torch.float32, device=dev)
         depth_scaled = torch.empty((B, 1, s, s), dtype=torch.float32, device=dev)
         ws = torch.empty((_hip.lib().nunif_hip_sod_v1_workspace_floats(B),), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _hip.check(_hip.lib().nunif_hip_sod_v1_forward(
-                handle, ctypes.c_void_p(rgb.data_ptr()), rgb.shape[2], rgb.shape[3], ctypes.c_void_p(depth.data_ptr()),
-                depth.shape[2], depth.shape[3], B, ctypes.c_void_p(ws.data_ptr()), ctypes.c_void_p(sal.data_ptr()),
-                ctypes.c_void_p(depth_scaled.data_ptr()), _hip.current_stream_ptr(dev)))
+        eng.call(_hip.lib().nunif_hip_sod_v1_forward, eng.handle, ctypes.c_void_p(rgb.data_ptr()), rgb.shape[2], rgb.shape[3],
+                 ctypes.c_void_p(depth.data_ptr()), depth.shape[2], depth.shape[3], B, ctypes.c_void_p(ws.data_ptr()),
+                 ctypes.c_void_p(sal.data_ptr()), ctypes.c_void_p(depth_scaled.data_ptr()))
         return sal, depth_scaled, ws
 
     @torch.inference_mode()
@@ -217,16 +158,14 @@ class SODV1(I2IBaseModel):
         with torch.inference_mode():
             sal, depth_scaled, ws = self._infer(rgb, depth)
         B = sal.shape[0]
-        dev = self.get_device()
+        eng = self.engine()
         taps = {}
         for i, name in enumerate(TAP_NAMES):
             S = NET_SIZE >> (0 if name == "hx1d" else i)
-            out = torch.empty((B, 64, S, S), dtype=torch.float32, device=dev)
+            out = torch.empty((B, 64, S, S), dtype=torch.float32, device=eng.device)
             shape = (ctypes.c_int64 * 4)()
-            with torch.cuda.device(dev):
-                _hip.check(_hip.lib().nunif_hip_sod_v1_debug_taps(
-                    self._handle, ctypes.c_void_p(ws.data_ptr()), B, name.encode(), ctypes.c_void_p(out.data_ptr()), out.numel(),
-                    shape, _hip.current_stream_ptr(dev)))
+            eng.call(_hip.lib().nunif_hip_sod_v1_debug_taps, eng.handle, ctypes.c_void_p(ws.data_ptr()), B, name.encode(),
+                     ctypes.c_void_p(out.data_ptr()), out.numel(), shape)
             assert tuple(shape) == tuple(out.shape)
             taps[name] = out
         return sal, depth_scaled, taps

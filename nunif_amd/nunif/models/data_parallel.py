@@ -29,7 +29,7 @@ def _as_devices(device_ids):
 
 def replicate(module, devices):
     """One copy of ``module`` per device (the first device keeps the module itself, like torch's replicate keeps cuda:0's
-    parameters).  Engine models copy their host weights and rebuild the device engine lazily (Model.__deepcopy__)."""
+    parameters).  Engine models copy their host weights and rebuild the device engine lazily (FlatWeightsMixin.__deepcopy__)."""
     replicas = []
     for k, dev in enumerate(devices):
         if hasattr(module, "replica"):               # device-bound engines (HipDepthAnythingV2): rebuilt from their host weights

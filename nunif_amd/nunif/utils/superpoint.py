@@ -19,6 +19,7 @@ from types import SimpleNamespace
 import torch
 
 from ... import _hip
+from ...engine import FlatWeightsMixin, HipEngine
 
 WEIGHTS_URL = "https://github.com/nagadomi/nunif/releases/download/0.0.0/superpoint_v6_from_tf.pth"
 BN_EPS = 1e-3
@@ -183,7 +184,7 @@ def sample_descriptors(keypoints, descriptors, s: int = 8):
     return out.transpose(1, 2).to(descriptors.dtype)
 
 
-class SuperPoint(torch.nn.Module):
+class SuperPoint(FlatWeightsMixin, torch.nn.Module):
     default_conf = {
         "nms_radius": 4,
         "max_num_keypoints": None,
@@ -202,72 +203,17 @@ class SuperPoint(torch.nn.Module):
                 "the HIP engine builds SuperPoint only in the geometry of SuperPoint(): channels [64, 64, 128, 128, 256], "
                 "descriptor_dim 256")
         self.stride = 2 ** (len(self.conf.channels) - 2)
-        self.register_buffer("_device_probe", torch.empty(0), persistent=False)
-        self._weights = _init_weights()
-        self._handle = None
-        self._handle_device = None
+        self._setup_weights(_init_weights())
         self._last_numel = 0
         self.eval()
 
-    def get_device(self):
-        return self._device_probe.device
-
-    def state_dict(self, *args, **kwargs):
-        return OrderedDict((k, v.clone()) for k, v in self._weights.items())
-
-    def load_state_dict(self, state_dict, strict=True, **kwargs):
-        missing = [k for k in self._weights if k not in state_dict]
-        unexpected = [k for k in state_dict if k not in self._weights]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Error(s) in loading state_dict for SuperPoint: missing {missing[:4]}, unexpected {unexpected[:4]}")
-        for k in self._weights:
-            if k in state_dict:
-                v = state_dict[k].detach().to("cpu")
-                if v.shape != self._weights[k].shape:
-                    raise RuntimeError(f"size mismatch for {k}: {tuple(v.shape)} vs {tuple(self._weights[k].shape)}")
-                self._weights[k] = v.float().clone() if torch.is_floating_point(v) else v.clone()
-        self._release()
-        return torch.nn.modules.module._IncompatibleKeys(missing, unexpected)
-
-    def parameters(self, recurse=True):
-        return iter(v for v in self._weights.values() if torch.is_floating_point(v))
+    def _make_engine(self, device):
+        return HipEngine(device, pack_weights(self._weights), "nunif_hip_superpoint_create", "nunif_hip_superpoint_destroy",
+                         label="SuperPoint")
 
     def load(self, map_location="cpu"):
         self.load_state_dict(torch.hub.load_state_dict_from_url(WEIGHTS_URL, weights_only=True, map_location=map_location))
         return self
-
-    def _release(self):
-        h = self.__dict__.get("_handle")
-        self.__dict__["_handle"] = None
-        if h:
-            try:
-                _hip.lib().nunif_hip_superpoint_destroy(h)
-            except Exception:
-                pass
-
-    def __del__(self):
-        self._release()
-
-    def _engine(self):
-        dev = self.get_device()
-        if dev.type != "cuda":
-            raise RuntimeError("the SuperPoint HIP engine needs a ROCm device (model.to('cuda:N')); no CPU fallback")
-        if self._handle is None or self._handle_device != dev:
-            self._release()
-            packed = pack_weights(self._weights)
-            descs = []
-            for name, t in packed.items():
-                d = _hip.TensorDesc()
-                d.name, d.data, d.ndim = name.encode(), t.data_ptr(), t.dim()
-                for i, s in enumerate(t.shape):
-                    d.shape[i] = s
-                descs.append(d)
-            arr = (_hip.TensorDesc * len(descs))(*descs)
-            handle = ctypes.c_void_p()
-            with torch.cuda.device(dev):
-                _hip.check(_hip.lib().nunif_hip_superpoint_create(arr, len(descs), ctypes.byref(handle)))
-            self._handle, self._handle_device = handle, dev
-        return self._handle
 
     def _net(self, image, keypoints=True):
         """Run the engine on ``[B, C, H, W]``: (keypoints [B, cap, 2], scores [B, cap], counts [B]) on the device, or nothing with
@@ -275,8 +221,8 @@ class SuperPoint(torch.nn.Module):
         if self.training:
             raise RuntimeError("the HIP engine is inference-only; call .eval()")
         assert torch.is_tensor(image) and image.ndim == 4 and image.shape[1] in (1, 3), "image must be [B, 1 or 3, H, W]"
-        dev = self.get_device()
-        handle = self._engine()
+        eng = self.engine()
+        dev = eng.device
         x = image.to(device=dev, dtype=torch.float32).contiguous()
         B, C, H, W = x.shape
         self._last_numel = B * H * W
@@ -286,22 +232,18 @@ class SuperPoint(torch.nn.Module):
             kp = torch.empty((B, cap, 2), dtype=torch.float32, device=dev)
             kps = torch.empty((B, cap), dtype=torch.float32, device=dev)
             counts = torch.empty((B,), dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            _hip.check(_hip.lib().nunif_hip_superpoint_forward(
-                handle, _ptr(x), B, C, H, W, int(self.conf.nms_radius), int(self.conf.remove_borders or 0),
-                float(self.conf.detection_threshold), _ptr(kp), _ptr(kps), _ptr(counts), _hip.current_stream_ptr(dev)))
+        eng.call(_hip.lib().nunif_hip_superpoint_forward, eng.handle, _ptr(x), B, C, H, W, int(self.conf.nms_radius),
+                 int(self.conf.remove_borders or 0), float(self.conf.detection_threshold), _ptr(kp), _ptr(kps), _ptr(counts))
         return kp, kps, counts
 
     def debug_tap(self, name):
         """A buffer of the last forward (tests): "backbone.0" .. "backbone.3", "heads", "descriptors" as ``[B, C, h, w]``,
         "scores" / "nms" as ``[B, H, W]``."""
-        dev = self.get_device()
+        eng = self.engine()
         shape = (ctypes.c_int64 * 4)()
         cap = 16 * self._last_numel                               # the largest tap, backbone.0, is [B, H/2, W/2, 64]
-        out = torch.empty(cap, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _hip.check(_hip.lib().nunif_hip_superpoint_debug_taps(self._engine(), name.encode(), _ptr(out), cap, shape,
-                                                                  _hip.current_stream_ptr(dev)))
+        out = torch.empty(cap, dtype=torch.float32, device=eng.device)
+        eng.call(_hip.lib().nunif_hip_superpoint_debug_taps, eng.handle, name.encode(), _ptr(out), cap, shape)
         s = list(shape)
         t = out[: s[0] * s[1] * s[2] * s[3]].reshape(s)
         if name in ("scores", "nms"):
@@ -314,15 +256,14 @@ class SuperPoint(torch.nn.Module):
         counts = counts.tolist()                                  # the one host read per batch: the output is ragged
         b = len(counts)
         keypoints, scores, descriptors = [], [], []
-        lib, handle = _hip.lib(), self._engine()
+        lib, eng = _hip.lib(), self.engine()
         for i in range(b):
             k, s = kp[i, :counts[i]], kps[i, :counts[i]]
             if self.conf.max_num_keypoints is not None:
                 k, s = select_top_k_keypoints(k, s, self.conf.max_num_keypoints)
             k, s = k.contiguous().clone(), s.clone()              # not views: the capacity buffers are not kept alive
             d = torch.empty((k.shape[0], DESCRIPTOR_DIM), dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev):
-                _hip.check(lib.nunif_hip_superpoint_sample(handle, i, _ptr(k), k.shape[0], _ptr(d), _hip.current_stream_ptr(dev)))
+            eng.call(lib.nunif_hip_superpoint_sample, eng.handle, i, _ptr(k), k.shape[0], _ptr(d))
             keypoints.append(k)
             scores.append(s)
             descriptors.append(d)

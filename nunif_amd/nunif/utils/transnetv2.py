@@ -17,6 +17,7 @@ from collections import OrderedDict
 import torch
 
 from ... import _hip
+from ...engine import FlatWeightsMixin, HipEngine
 
 WEIGHTS_FILE = "transnetv2-pytorch-weights.pth"
 DILATIONS = (1, 2, 4, 8)
@@ -121,7 +122,7 @@ def weights_path(model_dir=None):
     return os.path.join(model_dir or default_model_dir(), "checkpoints", WEIGHTS_FILE)
 
 
-class TransNetV2(torch.nn.Module):
+class TransNetV2(FlatWeightsMixin, torch.nn.Module):
     def __init__(self,
                  F=16, L=3, S=2, D=1024,
                  use_many_hot_targets=True,
@@ -141,34 +142,12 @@ class TransNetV2(torch.nn.Module):
             raise NotImplementedError(
                 "the HIP engine builds TransNetV2 only in the geometry of TransNetV2(): F=16, L=3, S=2, D=1024, frame similarity, "
                 "colour histograms and the many-hot head on, no mean pooling")
-        self.register_buffer("_device_probe", torch.empty(0), persistent=False)
-        self._weights = _init_weights()
-        self._handle = None
-        self._handle_device = None
+        self._setup_weights(_init_weights())
         self.eval()
 
-    def get_device(self):
-        return self._device_probe.device
-
-    def state_dict(self, *args, **kwargs):
-        return OrderedDict((k, v.clone()) for k, v in self._weights.items())
-
-    def load_state_dict(self, state_dict, strict=True, **kwargs):
-        missing = [k for k in self._weights if k not in state_dict]
-        unexpected = [k for k in state_dict if k not in self._weights]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Error(s) in loading state_dict for TransNetV2: missing {missing[:4]}, unexpected {unexpected[:4]}")
-        for k in self._weights:
-            if k in state_dict:
-                v = state_dict[k].detach().to("cpu")
-                if v.shape != self._weights[k].shape:
-                    raise RuntimeError(f"size mismatch for {k}: {tuple(v.shape)} vs {tuple(self._weights[k].shape)}")
-                self._weights[k] = v.float().clone() if torch.is_floating_point(v) else v.clone()
-        self._release()
-        return torch.nn.modules.module._IncompatibleKeys(missing, unexpected)
-
-    def parameters(self, recurse=True):
-        return iter(v for v in self._weights.values() if torch.is_floating_point(v))
+    def _make_engine(self, device):
+        return HipEngine(device, pack_weights(self._weights), "nunif_hip_transnetv2_create", "nunif_hip_transnetv2_destroy", 16,
+                         label="TransNetV2")
 
     def load(self, map_location="cpu", model_dir=None):
         path = weights_path(model_dir)
@@ -178,39 +157,6 @@ class TransNetV2(torch.nn.Module):
         self.load_state_dict(torch.load(path, map_location=map_location, weights_only=True))
         return self
 
-    def _release(self):
-        h = self.__dict__.get("_handle")             # absent when the constructor refused its options
-        self.__dict__["_handle"] = None
-        if h:
-            try:
-                _hip.lib().nunif_hip_transnetv2_destroy(h)
-            except Exception:
-                pass
-
-    def __del__(self):
-        self._release()
-
-    def _engine(self):
-        dev = self.get_device()
-        if dev.type != "cuda":
-            raise RuntimeError("the TransNetV2 HIP engine needs a ROCm device (model.to('cuda:N')); no CPU fallback")
-        if self._handle is None or self._handle_device != dev:
-            self._release()
-            packed = pack_weights(self._weights)
-            descs = []
-            for name, t in packed.items():
-                d = _hip.TensorDesc()
-                d.name, d.data, d.ndim = name.encode(), t.data_ptr(), t.dim()
-                for i, s in enumerate(t.shape):
-                    d.shape[i] = s
-                descs.append(d)
-            arr = (_hip.TensorDesc * len(descs))(*descs)
-            handle = ctypes.c_void_p()
-            with torch.cuda.device(dev):
-                _hip.check(_hip.lib().nunif_hip_transnetv2_create(arr, len(descs), 16, ctypes.byref(handle)))
-            self._handle, self._handle_device = handle, dev
-        return self._handle
-
     def _run(self, inputs, sigmoid):
         if self.training:
             raise RuntimeError("the HIP engine is inference-only; call .eval()")
@@ -219,18 +165,16 @@ class TransNetV2(torch.nn.Module):
             inputs = inputs.unsqueeze(0)
         else:
             assert inputs.ndim == 5 and inputs.shape[2:] == (3, 27, 48), "incorrect input type and/or shape"
-        dev = self.get_device()
-        handle = self._engine()
+        eng = self.engine()
+        dev = eng.device
         x = inputs.to(device=dev, dtype=torch.float32).contiguous()
         B, T = x.shape[:2]
         if T < 1 or B < 1:
             raise ValueError("TransNetV2 needs at least one frame")
         out = torch.empty((3 if sigmoid else 2, B, T), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _hip.check(_hip.lib().nunif_hip_transnetv2_forward(
-                handle, ctypes.c_void_p(x.data_ptr()), B, T, ctypes.c_void_p(out[0].data_ptr()),
-                ctypes.c_void_p(out[1].data_ptr()), ctypes.c_void_p(out[2].data_ptr()) if sigmoid else None,
-                _hip.current_stream_ptr(dev)))
+        eng.call(_hip.lib().nunif_hip_transnetv2_forward, eng.handle, ctypes.c_void_p(x.data_ptr()), B, T,
+                 ctypes.c_void_p(out[0].data_ptr()), ctypes.c_void_p(out[1].data_ptr()),
+                 ctypes.c_void_p(out[2].data_ptr()) if sigmoid else None)
         return out
 
     def forward(self, inputs):

@@ -14,6 +14,7 @@ import torch
 
 from ...nunif.models import I2IBaseModel, register_model
 from ... import _hip
+from ...engine import FlatWeightsMixin, HipEngine
 
 
 def tile_size_validator(size):
@@ -59,50 +60,24 @@ def _init_weights(in_channels, out_channels, up=False):
     return sd
 
 
-class HipCUNetEngine:
+class HipCUNetEngine(HipEngine):
     """One ``nunif_cunet`` handle: CUNet / UpCUNet, or the plain conv stacks vgg_7 / upconv_7 (the C side tells them apart
     by the state-dict keys); ``scale`` / ``offset`` are the model's i2i geometry (output side = T * scale - 2 * offset)."""
 
     def __init__(self, state_dict, no_clip, device, scale=None, offset=None):
-        self.device = torch.device(device)
         if scale is None:
             up = state_dict["unet1.conv_bottom.weight"].shape[2] == 4
             scale, offset = (2, 36) if up else (1, 28)
         self.scale, self.offset = scale, offset
-        if self.device.type != "cuda":
-            raise RuntimeError("the cunet HIP engine needs a ROCm device (model.to('cuda:N')); no CPU fallback")
-        keep, descs = [], []
-        for name, t in state_dict.items():
-            t = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
-            keep.append(t)
-            d = _hip.TensorDesc()
-            d.name, d.data, d.ndim = name.encode(), t.data_ptr(), t.dim()
-            for i, s in enumerate(t.shape):
-                d.shape[i] = s
-            descs.append(d)
-        arr = (_hip.TensorDesc * len(descs))(*descs)
-        handle = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().nunif_hip_cunet_create(arr, len(descs), 1 if no_clip else 0, ctypes.byref(handle)))
-        self.handle = handle
-
-    def __del__(self):
-        h, self.handle = getattr(self, "handle", None), None
-        if h:
-            try:
-                _hip.lib().nunif_hip_cunet_destroy(h)
-            except Exception:
-                pass
+        super().__init__(device, state_dict, "nunif_hip_cunet_create", "nunif_hip_cunet_destroy", 1 if no_clip else 0,
+                         label="cunet")
 
     def forward(self, x):
         B, C, T, T2 = x.shape
         assert C == 3 and T == T2
         To = T * self.scale - 2 * self.offset
         z = torch.empty((B, 3, To, To), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().nunif_hip_cunet_forward(self.handle, ctypes.c_void_p(x.data_ptr()),
-                                                          ctypes.c_void_p(z.data_ptr()), B, T,
-                                                          _hip.current_stream_ptr(self.device)))
+        self.call(_hip.lib().nunif_hip_cunet_forward, self.handle, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(z.data_ptr()), B, T)
         return z
 
     def render(self, x, tile_size, batch_size):
@@ -110,14 +85,12 @@ class HipCUNetEngine:
         assert C == 3
         sc = self.scale
         y = torch.empty((3, H * sc, W * sc), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().nunif_hip_cunet_render(self.handle, ctypes.c_void_p(x.data_ptr()),
-                                                         ctypes.c_void_p(y.data_ptr()), H, W, tile_size, batch_size,
-                                                         _hip.current_stream_ptr(self.device)))
+        self.call(_hip.lib().nunif_hip_cunet_render, self.handle, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(y.data_ptr()),
+                  H, W, tile_size, batch_size)
         return y
 
 
-class _CUNetBase(I2IBaseModel):
+class _CUNetBase(FlatWeightsMixin, I2IBaseModel):
     _up = False
 
     def __init__(self, in_channels=3, out_channels=3, no_clip=False):
@@ -126,46 +99,11 @@ class _CUNetBase(I2IBaseModel):
         if in_channels != 3 or out_channels != 3:
             raise ValueError("the HIP cunet engine supports in_channels = out_channels = 3")
         self.register_tile_size_validator(tile_size_validator)
-        self.register_buffer("_device_probe", torch.empty(0), persistent=False)
         self.no_clip = no_clip
-        self._weights = _init_weights(in_channels, out_channels, self._up)
-        self._engine = None
+        self._setup_weights(_init_weights(in_channels, out_channels, self._up))
 
-    def get_device(self):
-        return self._device_probe.device
-
-    def state_dict(self, *args, **kwargs):
-        return OrderedDict((k, v.clone()) for k, v in self._weights.items())
-
-    def load_state_dict(self, state_dict, strict=True, **kwargs):
-        missing = [k for k in self._weights if k not in state_dict]
-        unexpected = [k for k in state_dict if k not in self._weights]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Error(s) in loading state_dict for {type(self).__name__}: missing {missing[:4]}, "
-                               f"unexpected {unexpected[:4]}")
-        for k in self._weights:
-            if k in state_dict:
-                v = state_dict[k].detach().to("cpu")
-                if v.shape != self._weights[k].shape:
-                    raise RuntimeError(f"size mismatch for {k}: {tuple(v.shape)} vs {tuple(self._weights[k].shape)}")
-                self._weights[k] = v.float().clone()
-        self._engine = None
-        return torch.nn.modules.module._IncompatibleKeys(missing, unexpected)
-
-    def parameters(self, recurse=True):
-        return iter(self._weights.values())
-
-    def half(self):
-        return self
-
-    def float(self):
-        return self
-
-    def engine(self):
-        dev = self.get_device()
-        if self._engine is None or self._engine.device != dev:
-            self._engine = HipCUNetEngine(self._weights, self.no_clip, dev)
-        return self._engine
+    def _make_engine(self, device):
+        return HipCUNetEngine(self._weights, self.no_clip, device)
 
     def forward(self, x):
         if self.training:

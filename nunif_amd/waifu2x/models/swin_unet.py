@@ -16,6 +16,7 @@ import torch
 
 from ...nunif.models import I2IBaseModel, register_model, register_model_factory
 from ... import _hip
+from ...engine import FlatWeightsMixin, HipEngine
 
 WINDOW = 6
 
@@ -86,51 +87,22 @@ def _init_weights(scale_factor, base_dim, in_channels, out_channels, layer_norm=
     return sd
 
 
-class HipSwinUNetEngine:
+class HipSwinUNetEngine(HipEngine):
     """Owns one ``nunif_swin_unet*`` handle (device weights + workspace) for one device."""
 
     def __init__(self, state_dict, scale_factor, device):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("the swin_unet HIP engine needs a ROCm device (model.to('cuda:N')); no CPU fallback")
+        # (the int64 relative_position_index is left out: the C side recomputes it from the window geometry)
+        super().__init__(device, state_dict, "nunif_hip_swin_unet_create", "nunif_hip_swin_unet_destroy", scale_factor,
+                         label="swin_unet")
         self.scale_factor = scale_factor
-        keep = []
-        descs = []
-        for name, t in state_dict.items():
-            if not t.is_floating_point():
-                continue   # relative_position_index is recomputed from the window geometry
-            t = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
-            keep.append(t)
-            d = _hip.TensorDesc()
-            d.name = name.encode()
-            d.data = t.data_ptr()
-            d.ndim = t.dim()
-            for i, s in enumerate(t.shape):
-                d.shape[i] = s
-            descs.append(d)
-        arr = (_hip.TensorDesc * len(descs))(*descs)
-        handle = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().nunif_hip_swin_unet_create(arr, len(descs), scale_factor, ctypes.byref(handle)))
-        self.handle = handle
-
-    def __del__(self):
-        h, self.handle = getattr(self, "handle", None), None
-        if h:
-            try:
-                _hip.lib().nunif_hip_swin_unet_destroy(h)
-            except Exception:
-                pass
 
     def forward(self, x):
         B, C, T, T2 = x.shape
         assert C == 3 and T == T2
         s = self.scale_factor
         z = torch.empty((B, 3, (T - 16) * s, (T - 16) * s), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().nunif_hip_swin_unet_forward(
-                self.handle, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(z.data_ptr()), B, T,
-                _hip.current_stream_ptr(self.device)))
+        self.call(_hip.lib().nunif_hip_swin_unet_forward, self.handle, ctypes.c_void_p(x.data_ptr()),
+                  ctypes.c_void_p(z.data_ptr()), B, T)
         return z
 
     def render(self, x, tile_size, batch_size):
@@ -138,10 +110,8 @@ class HipSwinUNetEngine:
         assert C == 3
         s = self.scale_factor
         y = torch.empty((3, H * s, W * s), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().nunif_hip_swin_unet_render(
-                self.handle, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(y.data_ptr()), H, W, tile_size,
-                batch_size, _hip.current_stream_ptr(self.device)))
+        self.call(_hip.lib().nunif_hip_swin_unet_render, self.handle, ctypes.c_void_p(x.data_ptr()),
+                  ctypes.c_void_p(y.data_ptr()), H, W, tile_size, batch_size)
         return y
 
 
@@ -158,84 +128,36 @@ class SwinRowEngine:
         self.y_h, self.y_w = self.grid.y_h, self.grid.y_w
         self.device = engine.device
 
-    def _call(self, fn, *args):
-        with torch.cuda.device(self.device):
-            _hip.check(fn(*args, _hip.current_stream_ptr(self.device)))
-
     def render_tile_rows(self, x, r0, r1):
-        self._call(_hip.lib().nunif_hip_swin_unet_render_tile_rows, self.e.handle, ctypes.c_void_p(x.data_ptr()), self.H, self.W,
-                   self.tile_size, self.batch_size, r0, r1)
+        self.e.call(_hip.lib().nunif_hip_swin_unet_render_tile_rows, self.e.handle, ctypes.c_void_p(x.data_ptr()), self.H, self.W,
+                     self.tile_size, self.batch_size, r0, r1)
 
     def export_band(self, tile_row, row0, n_rows):
         band = torch.empty((self.w_blocks, 3, n_rows, self.out_tile_size), dtype=torch.float32, device=self.device)
-        self._call(_hip.lib().nunif_hip_swin_unet_tile_row_band, self.e.handle, self.H, self.W, self.tile_size, tile_row, row0,
-                   n_rows, ctypes.c_void_p(band.data_ptr()), 0)
+        self.e.call(_hip.lib().nunif_hip_swin_unet_tile_row_band, self.e.handle, self.H, self.W, self.tile_size, tile_row, row0,
+                     n_rows, ctypes.c_void_p(band.data_ptr()), 0)
         return band
 
     def import_band(self, tile_row, row0, band):
         band = band.to(device=self.device, dtype=torch.float32).contiguous()
-        self._call(_hip.lib().nunif_hip_swin_unet_tile_row_band, self.e.handle, self.H, self.W, self.tile_size, tile_row, row0,
-                   band.shape[2], ctypes.c_void_p(band.data_ptr()), 1)
+        self.e.call(_hip.lib().nunif_hip_swin_unet_tile_row_band, self.e.handle, self.H, self.W, self.tile_size, tile_row, row0,
+                     band.shape[2], ctypes.c_void_p(band.data_ptr()), 1)
 
     def stitch_rows(self, y0, y1):
         out = torch.empty((3, y1 - y0, self.y_w), dtype=torch.float32, device=self.device)
         if y1 > y0:
-            self._call(_hip.lib().nunif_hip_swin_unet_stitch_rows, self.e.handle, ctypes.c_void_p(out.data_ptr()), self.H, self.W,
-                       self.tile_size, y0, y1)
+            self.e.call(_hip.lib().nunif_hip_swin_unet_stitch_rows, self.e.handle, ctypes.c_void_p(out.data_ptr()), self.H, self.W,
+                         self.tile_size, y0, y1)
         return out
 
 
-class _FlatWeightsModel(I2IBaseModel):
-    """Common machinery: flat fp32 master weights under the reference's keys + a lazily built HIP engine
-    (``_make_engine(device)``, one handle per device)."""
+class _FlatWeightsModel(FlatWeightsMixin, I2IBaseModel):
+    """The swin_unet families: ``FlatWeightsMixin`` + their tile-size rule and the per-tile ``forward``."""
     unet_scale_factor = 1
 
     def _setup_weights(self, weights):
         self.register_tile_size_validator(tile_size_validator)
-        self.register_buffer("_device_probe", torch.empty(0), persistent=False)
-        self._weights = weights
-        self._engine = None
-
-    def _make_engine(self, device):
-        raise NotImplementedError
-
-    # -- nn.Module surface ------------------------------------------------------------------------------------
-    def get_device(self):
-        return self._device_probe.device
-
-    def state_dict(self, *args, **kwargs):
-        return OrderedDict((k, v.clone()) for k, v in self._weights.items())
-
-    def load_state_dict(self, state_dict, strict=True, **kwargs):
-        missing = [k for k in self._weights if k not in state_dict]
-        unexpected = [k for k in state_dict if k not in self._weights]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Error(s) in loading state_dict for {type(self).__name__}: "
-                               f"missing {missing[:4]}{'...' if len(missing) > 4 else ''}, "
-                               f"unexpected {unexpected[:4]}{'...' if len(unexpected) > 4 else ''}")
-        for k in self._weights:
-            if k in state_dict:
-                v = state_dict[k].detach().to("cpu")
-                if v.shape != self._weights[k].shape:
-                    raise RuntimeError(f"size mismatch for {k}: {tuple(v.shape)} vs {tuple(self._weights[k].shape)}")
-                self._weights[k] = v.to(self._weights[k].dtype).clone()
-        self._engine = None
-        return torch.nn.modules.module._IncompatibleKeys(missing, unexpected)
-
-    def parameters(self, recurse=True):
-        return iter(v for v in self._weights.values() if v.is_floating_point())
-
-    def half(self):      # storage precision is the engine's business (fp16 maps, fp32 accumulate)
-        return self
-
-    def float(self):
-        return self
-
-    def engine(self):
-        dev = self.get_device()
-        if self._engine is None or self._engine.device != dev:
-            self._engine = self._make_engine(dev)
-        return self._engine
+        super()._setup_weights(weights)
 
     def _prepare(self, x):
         return x.to(device=self.get_device(), dtype=torch.float32).contiguous()

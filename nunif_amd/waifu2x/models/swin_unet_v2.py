@@ -17,6 +17,7 @@ import torch
 
 from ...nunif.models import register_model_factory, I2IBaseModel, register_model
 from ... import _hip
+from ...engine import HipEngine
 from ...synthetic import window_score_bias_input
 from .swin_unet import _FlatWeightsModel, tile_size_validator
 
@@ -78,40 +79,14 @@ def _init_weights(scale_factor, base_dim, lv1_mlp_ratio, lv2_mlp_ratio, lv2_rati
     return sd
 
 
-class HipSwinUNetV2Engine:
+class HipSwinUNetV2Engine(HipEngine):
     """Owns one ``nunif_swin_unet_v2*`` handle (device weights + workspace) for one device."""
 
     def __init__(self, state_dict, scale_factor, device):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("the swin_unet_v2 HIP engine needs a ROCm device (model.to('cuda:N')); no CPU fallback")
+        # the score-bias index (int64) / offsets are recomputed from the window geometry
+        super().__init__(device, state_dict, "nunif_hip_swin_unet_v2_create", "nunif_hip_swin_unet_v2_destroy", scale_factor,
+                         label="swin_unet_v2", skip=[k for k in state_dict if k.endswith("relative_bias.delta")])
         self.scale_factor = scale_factor
-        keep, descs = [], []
-        for name, t in state_dict.items():
-            if not t.is_floating_point() or name.endswith("relative_bias.delta"):
-                continue        # the score-bias index / offsets are recomputed from the window geometry
-            t = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
-            keep.append(t)
-            d = _hip.TensorDesc()
-            d.name = name.encode()
-            d.data = t.data_ptr()
-            d.ndim = t.dim()
-            for i, s in enumerate(t.shape):
-                d.shape[i] = s
-            descs.append(d)
-        arr = (_hip.TensorDesc * len(descs))(*descs)
-        handle = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().nunif_hip_swin_unet_v2_create(arr, len(descs), scale_factor, ctypes.byref(handle)))
-        self.handle = handle
-
-    def __del__(self):
-        h, self.handle = getattr(self, "handle", None), None
-        if h:
-            try:
-                _hip.lib().nunif_hip_swin_unet_v2_destroy(h)
-            except Exception:
-                pass
 
     def forward(self, x, clamp=True):
         B, C, T, T2 = x.shape
@@ -119,10 +94,8 @@ class HipSwinUNetV2Engine:
         s = self.scale_factor
         o = (T - 18) * s
         z = torch.empty((B, 3, o, o), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().nunif_hip_swin_unet_v2_forward(
-                self.handle, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(z.data_ptr()), B, T, 1 if clamp else 0,
-                _hip.current_stream_ptr(self.device)))
+        self.call(_hip.lib().nunif_hip_swin_unet_v2_forward, self.handle, ctypes.c_void_p(x.data_ptr()),
+                  ctypes.c_void_p(z.data_ptr()), B, T, 1 if clamp else 0)
         return z
 
 

@@ -13,10 +13,11 @@ from collections import OrderedDict
 import torch
 
 from ...nunif.models import I2IBaseModel, register_model
+from ...engine import FlatWeightsMixin
 from .cunet import HipCUNetEngine
 
 
-class _ConvStack(I2IBaseModel):
+class _ConvStack(FlatWeightsMixin, I2IBaseModel):
     _channels = ()
     _deconv = False
     _kaiming = False
@@ -26,9 +27,7 @@ class _ConvStack(I2IBaseModel):
                          in_channels=in_channels)
         if in_channels != 3 or out_channels != 3:
             raise ValueError("the HIP conv-stack engine supports in_channels = out_channels = 3")
-        self.register_buffer("_device_probe", torch.empty(0), persistent=False)
-        self._weights = self._init_weights()
-        self._engine = None
+        self._setup_weights(self._init_weights())
 
     def _init_weights(self):
         sd = OrderedDict()
@@ -50,41 +49,8 @@ class _ConvStack(I2IBaseModel):
             sd[f"net.{2 * i}.weight"], sd[f"net.{2 * i}.bias"] = w, b
         return sd
 
-    def get_device(self):
-        return self._device_probe.device
-
-    def state_dict(self, *args, **kwargs):
-        return OrderedDict((k, v.clone()) for k, v in self._weights.items())
-
-    def load_state_dict(self, state_dict, strict=True, **kwargs):
-        missing = [k for k in self._weights if k not in state_dict]
-        unexpected = [k for k in state_dict if k not in self._weights]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Error(s) in loading state_dict for {type(self).__name__}: missing {missing[:4]}, "
-                               f"unexpected {unexpected[:4]}")
-        for k in self._weights:
-            if k in state_dict:
-                v = state_dict[k].detach().to("cpu")
-                if v.shape != self._weights[k].shape:
-                    raise RuntimeError(f"size mismatch for {k}: {tuple(v.shape)} vs {tuple(self._weights[k].shape)}")
-                self._weights[k] = v.float().clone()
-        self._engine = None
-        return torch.nn.modules.module._IncompatibleKeys(missing, unexpected)
-
-    def parameters(self, recurse=True):
-        return iter(self._weights.values())
-
-    def half(self):
-        return self
-
-    def float(self):
-        return self
-
-    def engine(self):
-        dev = self.get_device()
-        if self._engine is None or self._engine.device != dev:
-            self._engine = HipCUNetEngine(self._weights, False, dev, scale=self.i2i_scale, offset=self.i2i_offset)
-        return self._engine
+    def _make_engine(self, device):
+        return HipCUNetEngine(self._weights, False, device, scale=self.i2i_scale, offset=self.i2i_offset)
 
     def forward(self, x):
         if self.training:
