@@ -1,4 +1,5 @@
-"""Localised error bounds for the swin and cunet nets and the iw3 side nets: worst-REGION error against a float64 oracle (helper module, not a conftest).
+"""Localised error bounds for the swin and cunet nets, the iw3 side nets and the iw3 depth path: worst-REGION error against a float64
+oracle (helper module, not a conftest).
 
 PSNR is a whole-image average: one 6 x 6 window of a 256 tile off by 0.1 (70x the fp16 noise floor) still reads 51 dB.  The
 kernels go wrong per window (lanes, masks, tables and index arithmetic are per window / per head / per edge row), so this module
@@ -19,6 +20,12 @@ cells 8 / 16 / 32 / 64 of the level-1 map in output pixels (twice that for the 2
 The iw3 side nets (``sbs.row_flow_v3``, ``sbs.mlbw_*``, csrc/rowflow.hip) run one window of 4 x 4 or 3 x 3 tokens per wave and a token
 is 1 row x 8 depth pixels: their regions are rectangular cells (cell_h, cell_w) with offsets (off_y, off_x), and since flows,
 softmax weights and logits are not clamped the floor is relative, tau = TAP_TAU_REL x the map's rms (``tests/sidenet_cases.py``).
+
+The iw3 depth path (``iw3.depth_anything``: csrc/depth_anything.hip, depth_mlp.hip, conv3_lds.hip; ``iw3.depth_aa``: csrc/depth_aa.hip)
+is pinned on its final outputs only, [B,1,h,w], with the side nets' constants and relative floor.  The depth engine goes wrong per
+token (14 x 14 pixels of the map), per 4 x 4 token block (the footprint of one ``layer4_rn`` pixel pair) and per 8 x 32 conv patch of
+``output_conv2.0``; DepthAA per 8 x 8 window = 16 x 16 pixels behind its centred pad, shifted by 8 pixels in blocks 0 and 2
+(``tests/depth_cases.py``).
 """
 import math
 
@@ -26,6 +33,8 @@ import torch
 import torch.nn.functional as F
 
 from oracle import cunet as OC
+from oracle import depth_aa as ODAA
+from oracle import depth_anything_v2 as ODA
 from oracle import mlbw as OM
 from oracle import row_flow_v3 as ORF
 from oracle import swin_unet as O
@@ -50,6 +59,13 @@ ROW_FLOW_CELLS = ((4, 32), (3, 24), (12, 96))   # the 4 x 4 and the 3 x 3 window
 MLBW = {"sbs.mlbw_l2": (2, False, False), "sbs.mlbw_l4": (4, False, False), "sbs.mlbw_l2s": (2, True, False),
         "sbs.mask_mlbw_l2": (2, False, True)}
 MLBW_CELL = (4, 32)
+
+# the iw3 depth path, final outputs only.  The depth engine: one token of the final map, a 4 x 4 token block (one layer4_rn pixel
+# pair) and the 8 x 32 patch of output_conv2.0, each aligned and shifted by half a cell.  DepthAA: one 8 x 8 window after the pixel
+# shuffle, starting at the centred pad's (-ph1, -pw1), and the 4-token zero-pad shift of blocks 0 and 2 (8 pixels)
+DEPTH_ANYTHING, DEPTH_AA = "iw3.depth_anything", "iw3.depth_aa"
+DEPTH_ANYTHING_CELLS = ((14, 14), (56, 56), (8, 32))
+DEPTH_AA_CELL, DEPTH_AA_SHIFT = (16, 16), (8, 8)
 
 # Thresholds: about twice the worst ratios measured on an MI355X over every case of tests/test_gpu_swin_errloc.py (its docstring)
 A_OUT, B_OUT, TAU_OUT = 2.5, 3.75, 5e-4          # clamped [0,1] outputs (worst 1.16 / 1.82); tau = one fp16 ulp in [0.5, 1)
@@ -76,7 +92,15 @@ def warp_floor(c):
     return WARP_FLOOR_ULPS * 2.0 ** -23 * (0.5 * (w - 1) * sx + 0.5 * (h - 1) * sy)
 
 
-def _forward(sd, x, name, taps=None, no_clip=False):
+def _forward(sd, x, name, taps=None, no_clip=False, max_depth=0.0, infer=False):
+    if name == DEPTH_ANYTHING:
+        assert not no_clip and not infer, "the depth engine has no no_clip / infer"
+        # x: [B,3,h,w] ImageNet-normalised; taps = the four encoder blocks that feed the head (None: the checkpoint's default)
+        return ODA.model_forward(sd, x, taps=taps, max_depth=max_depth).unsqueeze(1)
+    if name == DEPTH_AA:
+        assert taps is None and not no_clip, "DepthAA has no taps / no_clip"
+        return ODAA.infer(sd, x) if infer else ODAA.forward(sd, x, clamp=False)
+    assert max_depth == 0.0 and not infer, "max_depth / infer are options of the depth path"
     if name == ROW_FLOW or name in MLBW:
         assert taps is None and not no_clip, "the side nets have no taps / no_clip"
         # x: the [B,3,h,w] feature planes (depth | divergence | convergence); unclamped flows, softmax weights, mask logits
@@ -92,16 +116,24 @@ def _forward(sd, x, name, taps=None, no_clip=False):
     return torch.clamp(O.unet_forward(sd, x, O.GEOMETRY.get(name, (0, 0, 0, SCALE[name]))[3], taps=taps), 0.0, 1.0)
 
 
-def oracle64(sd, x, name, taps=None, no_clip=False):
-    """The oracle forward with the state dict and the input cast to float64 (float64 output, clamped like the wrapper)."""
+def oracle64(sd, x, name, taps=None, no_clip=False, **kwargs):
+    """The oracle forward with the state dict and the input cast to float64 (float64 output, clamped like the wrapper).
+    ``kwargs``: ``max_depth`` (the depth engine's metric head), ``infer`` (DepthAA.infer instead of forward(clamp=False))."""
     sd64 = {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
-    return _forward(sd64, x.double(), name, taps, no_clip)
+    return _forward(sd64, x.double(), name, taps, no_clip, **kwargs)
 
 
-def emulated(sd, x, name, taps=None, no_clip=False):
-    """The reference's own GPU arithmetic: fp16 parameters, every op result rounded to fp16 (oracle/fp16_emulation.py)."""
+def emulated(sd, x, name, taps=None, no_clip=False, **kwargs):
+    """The reference's own GPU arithmetic: fp16 parameters, every op result rounded to fp16 (oracle/fp16_emulation.py).
+    ``half_weights`` keeps every key containing ``norm`` in fp32: that is right for the ViT LayerNorms of the depth engine
+    (``pretrained.blocks.*.norm1 / norm2``, ``pretrained.norm``), which autocast runs in fp32 with fp32 parameters."""
     with fp16_autocast_emulation():
-        return _forward(half_weights(sd), x.float(), name, taps, no_clip)
+        return _forward(half_weights(sd), x.float(), name, taps, no_clip, **kwargs)
+
+
+def depth_aa_pad(h, w):
+    """(ph1, pw1): the top / left part of DepthAA's centred replicate pad to multiples of 16 (oracle/depth_aa.py forward)."""
+    return (16 - h % 16) // 2, (16 - w % 16) // 2
 
 
 def mlbw_pad(h, w):
@@ -115,9 +147,16 @@ def cells_for(name, origin=0, shape=None):
     The side nets have rectangular cells: entries ((cell_h, cell_w), (off_y, off_x)[, (shift_y, shift_x)]); the shift is the second
     partition ``localised_stats`` looks at (default: half a cell both ways).  row_flow_v3 pads bottom / right only (origin 0); MLBW pads
     centred, so its windows start at (-ph1, -pw1) of the ``shape`` = (h, w) output, and its shifted blocks sit 2 tokens further
-    (sy / sx of nunif_hip_mlbw_create: (2, 2) tokens = (2, 16) pixels for the full nets, (0, 2) = (0, 16) for the small ones)."""
+    (sy / sx of nunif_hip_mlbw_create: (2, 2) tokens = (2, 16) pixels for the full nets, (0, 2) = (0, 16) for the small ones).
+    The depth engine: cells (14, 14) / (56, 56) / (8, 32) from pixel 0, shifted by half a cell.  DepthAA: (16, 16) cells from
+    (-ph1, -pw1) of the ``shape`` = (h, w) map (``depth_aa_pad``), the second partition 8 pixels further."""
     if name == ROW_FLOW:
         return [(c, (0, 0)) for c in ROW_FLOW_CELLS]
+    if name == DEPTH_ANYTHING:                      # no pad: tokens, token blocks and conv patches all start at pixel 0
+        return [(c, (0, 0)) for c in DEPTH_ANYTHING_CELLS]
+    if name == DEPTH_AA:
+        ph1, pw1 = depth_aa_pad(*shape)
+        return [(DEPTH_AA_CELL, ((-ph1) % DEPTH_AA_CELL[0], (-pw1) % DEPTH_AA_CELL[1]), DEPTH_AA_SHIFT)]
     if name in MLBW:
         ph1, pw1 = mlbw_pad(*shape)
         return [(MLBW_CELL, ((-ph1) % MLBW_CELL[0], (-pw1) % MLBW_CELL[1]), (0, 16) if MLBW[name][1] else (2, 16))]

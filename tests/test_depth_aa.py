@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import depth_cases as D
 from conftest import GOLDEN, psnr, sd_checksum
 from oracle import depth_aa as ODA
 from oracle.forward_warp import synth_depth
@@ -41,6 +42,8 @@ def test_hip_depth_aa(hiplib, g):
     rel = (edit - edit_ref).pow(2).mean().sqrt() / edit_ref.pow(2).mean().sqrt()
     assert rel.item() < 2e-2, rel.item()
     assert psnr(y.cpu(), g["y"]) >= 50.0 and psnr(m(x, clamp=False).cpu(), g["y_noclamp"]) >= 50.0
+    # the fixture's input window by window against float64, the reference's fp16 arithmetic as the yardstick (tests/errloc.py)
+    D.check_fresh(m(x, clamp=False).cpu(), sd, g["x"], D.AA, "depth_aa fixture")
     yi = m.infer(g["xi"].to("cuda:0")).cpu()
     span = float(g["xi"].max() - g["xi"].min())
     assert psnr(yi / span, g["y_infer"] / span) >= 50.0

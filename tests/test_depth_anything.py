@@ -8,6 +8,7 @@ import os
 import pytest
 import torch
 
+import depth_cases as D
 from conftest import psnr, synth_image
 from oracle import depth_anything_v2 as ODA
 
@@ -59,6 +60,8 @@ def test_hip_backbone_vs_restatement(hiplib):
         p = psnr(y / span, ref / span)
         rel = ((y - ref).pow(2).mean().sqrt() / ref.std()).item()
         assert p >= 50.0 and rel < 1e-2, (shape, p, rel)
+        # the same output cell by cell against float64, the reference's fp16 arithmetic as the yardstick (tests/errloc.py)
+        D.check_fresh(y, sd, x, D.NET, f"restatement {shape[0]}x{shape[2]}x{shape[3]}")
     assert torch.equal(net(x.to("cuda:0")).cpu(), y)                        # deterministic
     with pytest.raises(ValueError):
         net(torch.zeros(1, 3, 50, 56))
@@ -114,6 +117,7 @@ def test_hip_backbone_variants_vs_restatement(hiplib, encoder, taps, max_depth):
     p = psnr(y / span, ref / span)
     rel = ((y - ref).pow(2).mean().sqrt() / ref.std()).item()
     assert float(ref.std()) > 1e-3 and p >= 50.0 and rel < 1.5e-2, (encoder, taps, max_depth, p, rel)
+    D.check_fresh(y, sd, x, D.NET, f"variant {encoder} taps {taps} max_depth {max_depth}", taps=taps, max_depth=max_depth)
 
 
 @pytest.mark.gpu
