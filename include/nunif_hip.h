@@ -517,6 +517,29 @@ int nunif_hip_superpoint_match(const float *d1, int32_t n1, const float *d2, int
 int nunif_hip_affine_warp(const float *x, const float *params, float *out, int32_t B, int32_t C, int32_t H, int32_t W,
                           int32_t padding_mode, void *stream);
 
+/* iw3 --autocrop (nunif/utils/autocrop.py): the letterbox detector and the crop / uncrop copy.
+ * stats replaces AutoCropDetector.detect_tb :140-154 and detect_lr :156-170 (with rgb_to_y :117-138) and the accumulation of
+ *   update :24-48 for a batch: x [B,3,H,W] f32 device; flat = 0 the black modes (Y clamped to the TV range, mean <= 32/255 and
+ *   max |y - mean| < 16/255), 1 the flat modes (lower median as torch.median, fraction of |y - median| < 16/255 above 0.99);
+ *   passes bit 0 = rows (tb), bit 1 = columns (lr); only what is asked for is computed.  Every decision is ADDED to the device
+ *   counters border_count_tb [H] / border_count_lr [W] (i32; one thread owns a counter: no atomics, bit-identical on every call
+ *   and stream).  A fixed number of launches whatever B, no host sync.  work: caller-owned device scratch of the black lr pass,
+ *   B * ceil(H / 32) * W * 16 bytes, 16-byte aligned (unused otherwise, may be NULL).  H <= 4608, W <= 8192 (the LDS tiling of the
+ *   flat modes: 8 column lines of H floats, 4 row lines of W floats); larger frames are refused.  Inputs must be finite.
+ * debug_stats (tests) is stats that also writes the statistic vectors: row_a / col_a the mean (black) or median (flat), row_b /
+ *   col_b the max deviation (black) or the fraction (flat), [B][H] and [B][W] f32; the counters may then be NULL.
+ * crop_pad replaces AutoCrop.crop :346-354 (as a contiguous copy) and AutoCrop.uncrop :356-360 (F.pad, constant): src [N][sH][sW]
+ *   and dst [N][dH][dW] f32 (N = batch x channels, distinct buffers); the window of win_h x win_w at (y0, x0) of src lands at
+ *   (pad_top, pad_left) of dst, everything else of dst is pad_value.  The window must lie inside both. */
+int nunif_hip_autocrop_stats(const float *x, int32_t B, int32_t H, int32_t W, int32_t flat, int32_t passes,
+                             int32_t *border_count_tb, int32_t *border_count_lr, void *work, int64_t work_bytes, void *stream);
+int nunif_hip_autocrop_debug_stats(const float *x, int32_t B, int32_t H, int32_t W, int32_t flat, int32_t passes,
+                                   int32_t *border_count_tb, int32_t *border_count_lr, void *work, int64_t work_bytes,
+                                   float *row_a, float *row_b, float *col_a, float *col_b, void *stream);
+int nunif_hip_autocrop_crop_pad(const float *src, float *dst, int64_t N, int32_t sH, int32_t sW, int32_t dH, int32_t dW,
+                                int32_t y0, int32_t x0, int32_t pad_top, int32_t pad_left, int32_t win_h, int32_t win_w,
+                                float pad_value, void *stream);
+
 /* Test hooks (tests/ only): snapshot every stage's NHWC fp16 output during the next forward calls, then read
  * them back one by one (returns 1 past the last tap).  Names match oracle.swin_unet.unet_forward(taps=...). */
 int nunif_hip_swin_unet_debug_taps(nunif_swin_unet *handle, int32_t enable);

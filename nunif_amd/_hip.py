@@ -154,6 +154,10 @@ SIGNATURES = {
     "nunif_hip_superpoint_match": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                             c_void_p]),
     "nunif_hip_affine_warp": (c_int32, [c_void_p, c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p]),
+    "nunif_hip_autocrop_stats": (c_int32, [c_void_p] + [c_int32] * 5 + [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "nunif_hip_autocrop_debug_stats": (c_int32, [c_void_p] + [c_int32] * 5 + [c_void_p, c_void_p, c_void_p, c_int64] +
+                                       [c_void_p] * 5),
+    "nunif_hip_autocrop_crop_pad": (c_int32, [c_void_p, c_void_p, c_int64] + [c_int32] * 10 + [c_float, c_void_p]),
     "nunif_hip_swin_unet_debug_taps":(c_int32, [c_void_p, c_int32]),
     "nunif_hip_swin_unet_get_tap": (c_int32, [c_void_p, c_int32, c_char_p, c_int32, c_void_p, c_int64,
                                               ctypes.POINTER(c_int64)]),

@@ -18,12 +18,13 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-x", "hip", "-
          "-fno-gpu-rdc"]
 
 
-# the stitcher replays the reference's fp32 recurrence bit-exactly: no FMA contraction in that file
+# the stitcher replays the reference's fp32 recurrence bit-exactly: no FMA contraction in that file (autocrop.hip: the luma
+# whose medians are compared bit for bit)
 # the swin kernels are VALU-issue bound: hipcc's SLP vectoriser packs adjacent fp32 ops into v_pk_*_f32, which issue at
 # half rate and drag an s_nop behind each dependent use on gfx950 (tools/ubench_valu.hip) — keep them scalar
 NO_SLP = ["-fno-slp-vectorize"]
 EXTRA_FLAGS = {"stitch.hip": ["-ffp-contract=off"], "iw3_warp.hip": ["-ffp-contract=off"],
-               "iw3_depth.hip": ["-ffp-contract=off"], "image_ops.hip": ["-ffp-contract=off"], "grain.hip": ["-ffp-contract=off"], "swin_block_tail.hip": NO_SLP, "swin_block_tail_ws.hip": NO_SLP, "swin_qkv_attn_r.hip": NO_SLP + ["-fno-honor-nans"], "swin_block96.hip": NO_SLP + ["-fno-honor-nans"],
+               "iw3_depth.hip": ["-ffp-contract=off"], "image_ops.hip": ["-ffp-contract=off"], "grain.hip": ["-ffp-contract=off"], "autocrop.hip": ["-ffp-contract=off"], "swin_block_tail.hip": NO_SLP, "swin_block_tail_ws.hip": NO_SLP, "swin_qkv_attn_r.hip": NO_SLP + ["-fno-honor-nans"], "swin_block96.hip": NO_SLP + ["-fno-honor-nans"],
                "swin_kernels.hip": NO_SLP, "swin_patchup.hip": NO_SLP, "swin_patchdown.hip": NO_SLP, "cunet_up.hip": NO_SLP, "cunet_head.hip": NO_SLP,
                "cunet_kernels.hip": NO_SLP, "rowflow.hip": NO_SLP, "depth_aa.hip": NO_SLP, "depth_anything.hip": NO_SLP + ["-fno-honor-nans"], "depth_temporal.hip": NO_SLP, "conv3_lds.hip": NO_SLP,
                "transnetv2.hip": NO_SLP, "sod_v1.hip": NO_SLP, "superpoint.hip": NO_SLP}

@@ -79,6 +79,14 @@ PATCHES = [
     ("nunif.utils.superpoint", "SuperPoint"),
     ("nunif.utils.superpoint", "find_match_index"),
     ("nunif.utils.superpoint", "apply_transform"),
+    # --autocrop (nunif/utils/autocrop.py:6-207 the detector, :210-249 the video sampling loop, :252-360 crop / uncrop).
+    # iw3/utils.py:26 binds AutoCrop (and AutoCropDummy, which computes nothing and stays) by name and picks the engine's class up
+    # as a consumer, as iw3/desktop/utils.py does; AutoCrop.from_image and from_video_file reach the engine's detector and loop
+    # through the engine's own module.  The reference module imports nunif.utils.video (PyAV), as iw3.utils already does: under
+    # strict=False an import failure skips the three entries like any other.
+    ("nunif.utils.autocrop", "AutoCropDetector"),
+    ("nunif.utils.autocrop", "AutoCrop"),
+    ("nunif.utils.autocrop", "autocrop_analyze_video"),
 ]
 
 # reference packages whose modules may hold ``from ... import`` copies of a patched name

@@ -15,6 +15,7 @@ from .backward_warp import apply_divergence_grid_sample, apply_divergence_nn_LR
 from .equirectangular import equirectangular_projection
 from .forward_warp import apply_divergence_forward_warp
 from .mapper import get_mapper
+from ..nunif.utils.autocrop import AutoCrop, AutoCropDummy
 
 
 # iw3/utils.py:48-51
@@ -249,14 +250,34 @@ def debug_depth_image(depth, args):
 
 def process_image(x, args, depth_model, side_model=None, skip_autocrop=None, autocrop_uncrop=False):
     """The image-mode entry (iw3/utils.py:505-548): ``preprocess_image`` -> depth -> per-image min-max -> stereo method ->
-    ``postprocess_image``; CHW float in, CHW float SBS (or the chosen format) out.  ``--autocrop`` (border detection,
-    ``nunif/utils/autocrop.py``) is not on the engine and is refused rather than ignored."""
+    ``postprocess_image``; CHW float in, CHW float SBS (or the chosen format) out.  ``--autocrop`` is refused here rather than
+    ignored: :func:`process_image_autocrop` is this entry with the border detection, and after ``nunif_amd.install()`` the
+    reference's own ``process_image`` runs it on the engine's ``AutoCrop``."""
     assert depth_model.get_ema_buffer_size() == 1
     g = lambda k, d=None: getattr(args, k, d)     # noqa: E731
     if g("autocrop") is not None and not skip_autocrop:
-        raise NotImplementedError("--autocrop is outside the HIP engine's scope; crop the frame before process_image")
+        raise NotImplementedError("process_image does not crop: use process_image_autocrop(x, args, depth_model, ...) for "
+                                  "--autocrop, or nunif_amd.install() under the reference's iw3.utils.process_image")
+    return _process_image(x, args, depth_model, side_model, AutoCropDummy())
+
+
+def process_image_autocrop(x, args, depth_model, side_model=None, autocrop_uncrop=False):
+    """``process_image`` with ``--autocrop`` (iw3/utils.py:505-545): the borders are detected on the raw frame
+    (``AutoCrop.from_image`` with ``args.autocrop`` as the mode), cropped after ``preprocess_image`` and, with
+    ``autocrop_uncrop``, padded back onto both eyes before ``postprocess_image``.  Without ``args.autocrop`` nothing is cropped."""
+    if getattr(args, "autocrop", None) is None:
+        autocrop = AutoCropDummy()
+    else:
+        autocrop = AutoCrop.from_image(x, mode=args.autocrop, uncrop_enabled=autocrop_uncrop)
+    return _process_image(x, args, depth_model, side_model, autocrop)
+
+
+def _process_image(x, args, depth_model, side_model, autocrop):
+    assert depth_model.get_ema_buffer_size() == 1
+    g = lambda k, d=None: getattr(args, k, d)     # noqa: E731
     with torch.inference_mode():
         x = preprocess_image(x, args)
+        x = autocrop.crop(x)
         depth = depth_model.infer(x, tta=g("tta", False), low_vram=g("low_vram", False), enable_amp=not g("disable_amp", False),
                                   edge_dilation=g("edge_dilation", 0), depth_aa=g("depth_aa", False))
         depth = depth_model.minmax_normalize_chw(depth)
@@ -264,14 +285,14 @@ def process_image(x, args, depth_model, side_model=None, skip_autocrop=None, aut
             return debug_depth_image(depth, args)
         if g("rgbd") or g("half_rgbd"):
             left_eye, right_eye = apply_rgbd(x, depth, mapper=args.mapper)
-            return postprocess_image(left_eye, right_eye, args)
+            return postprocess_image(autocrop.uncrop(left_eye), autocrop.uncrop(right_eye), args)
         while True:                                   # a video inpaint side model answers None until its queue is full
             left_eye, right_eye = apply_divergence(depth, x, args, side_model)
             if left_eye is not None:
                 break
         if left_eye.ndim == 4:
             left_eye, right_eye = left_eye[0], right_eye[0]
-        return postprocess_image(left_eye, right_eye, args)
+        return postprocess_image(autocrop.uncrop(left_eye), autocrop.uncrop(right_eye), args)
 
 
 def to_tensor(frame_hwc, device=None):
