@@ -517,6 +517,49 @@ int nunif_hip_superpoint_match(const float *d1, int32_t n1, const float *d2, int
 int nunif_hip_affine_warp(const float *x, const float *params, float *out, int32_t B, int32_t C, int32_t H, int32_t W,
                           int32_t padding_mode, void *stream);
 
+/* stlizer --border outpaint / expand_outpaint: LightOutpaintV1 (stlizer/models/light_outpaint_v1.py) and the EMA frame buffer of
+ * pass 4 (stlizer/multipass_pipeline.py:447-474), fp32 operands and accumulation throughout.  Inputs must be finite (the buffer
+ * step's frames excepted: their NaN are the mask).
+ *
+ * create() takes the weights packed on the host (nunif_amd/stlizer/models/light_outpaint_v1.py pack_weights), all f32:
+ *   dct.{0,1,2}.w [9*Cin][Cout] (row = (kh*3+kw)*Cin + c), .b [Cout]        Downsampling :54-71, channels 4 -> 8 -> 16 -> 64
+ *   <blk>.mha.qkv.w [C][3C], .b [3C]    MHA.qkv_proj (nunif/modules/attention.py:106) input-major, the columns of head h at
+ *                                       96 h + (q | k | v) * 32;  <blk> = enc (C 64), mid0, mid1 (C 32), dec (C 64)
+ *   <blk>.mha.table [64][64]            WindowScoreBias.forward() (attention.py:408-415), one table for all heads
+ *   <blk>.mha.proj.w [C][C], .b         MHA.head_proj, input-major;  <blk>.mha.mlp1.w [C][2C], .b and .mlp2.w [C][C], .b  MHABlock.mlp
+ *   <blk>.pool.pw1.w [C][2C], .b        PoolBlock.mlp.0 :17, the columns of chunk j at 64 j: channels 32 j .. 32 j + 31, then C + the same
+ *   <blk>.pool.dw.w [9][2C], .b [2C]    the depthwise conv :20 tap-major;  <blk>.pool.pw2.w [C][C], .b  mlp.5 :23
+ *   proj_mid.w [64][32], .b; proj_out.w [32][64], .b  :95-96;  to_image.w [3][64], .b [3]  ToImageBilinaer.proj :77
+ * infer: x [B,3,H,W] f32, mask [B,1,H,W] u8 (non-zero = to be painted), out [B,3,H,W] f32 (not x).  mode 0 `composite` is
+ *   LightOutpaintV1.infer(composite=True) :175-204, 1 `raw` is infer(composite=False) :205-206, 2 `forward` is the eval-mode forward
+ *   :164-173 on what infer's net call returns (pass max_size >= max(H, W) for the reference's forward, which never resizes).
+ *   All of :175-206 and OutpaintBase.forward / _forward :115-153 run inside: the resize to max_size (new side =
+ *   round-half-even(side * (max_size / long side)) in double, as Python), the 3x3 mask dilation and > 0.5 threshold, the zeroing,
+ *   the replicate pad to a multiple of 64 with its mask of ones, x * (1 - mask) ONLY when a pad was needed, the net, the x8
+ *   bilinear upsample, the crop, the resize back and the composite.  work: nunif_hip_outpaint_work_bytes(B, H, W, max_size) bytes
+ *   of caller-owned device memory, 16-byte aligned; the handle keeps no per-call state, so calls on different streams with
+ *   different work buffers may overlap.  work_bytes returns -1 for a shape infer refuses.
+ * debug_taps copies one channels-last map [B,h,w,C] (h = padded height / 8) of the infer call that last wrote `work` (same B, H, W,
+ *   max_size): "dct" (after the three convs :117), "enc" (:118), "mid" (after the skip add :119), "dec" (:120), all C = 64, and
+ *   "proj", the 3-channel map before the upsample (:82).
+ * buffer_step replaces multipass_pipeline.py:452-453 and :461-471 for a batch, one launch each: with coarse == NULL it writes
+ *   out = frames with NaN -> 0 and mask0 [B,1,H,W] u8 = isnan(frames[:, 0]) (what infer takes in); with coarse [B,3,H,W] (the
+ *   raw net output) it visits the frames in order per element: reset[j] != 0 sets buffer = coarse_j (:464-466; the caller sets it
+ *   for the first frame ever and for scene_weight < 0.01), buffer = buffer * d + coarse_j * (1 - d) (:468-469), out_j = clamp(
+ *   isnan(frames_j) ? buffer : frames_j, 0, 1) (:470-471, the mask per element).  buffer [3,H,W] f32 and reset [B] u8 are device
+ *   memory; d = buffer_decay is the blend weight AFTER :456-458.  One thread owns an element across the batch: no atomics. */
+typedef struct nunif_outpaint nunif_outpaint;
+int nunif_hip_outpaint_create(const nunif_tensor_desc *tensors, int32_t n_tensors, nunif_outpaint **handle);
+void nunif_hip_outpaint_destroy(nunif_outpaint *handle);
+int64_t nunif_hip_outpaint_work_bytes(int32_t B, int32_t H, int32_t W, int32_t max_size);
+int nunif_hip_outpaint_infer(nunif_outpaint *handle, const float *x, const uint8_t *mask, int32_t B, int32_t H, int32_t W,
+                             int32_t max_size, int32_t mode, float *out, void *work, void *stream);
+int nunif_hip_outpaint_debug_taps(nunif_outpaint *handle, const void *work, int32_t B, int32_t H, int32_t W, int32_t max_size,
+                                  const char *name, float *out, int64_t capacity, int64_t *shape4, void *stream);
+int nunif_hip_outpaint_buffer_step(const float *frames, const float *coarse, float *buffer, const uint8_t *reset,
+                                   double buffer_decay, int32_t B, int32_t H, int32_t W, float *out, uint8_t *mask0,
+                                   void *stream);
+
 /* iw3 --autocrop (nunif/utils/autocrop.py): the letterbox detector and the crop / uncrop copy.
  * stats replaces AutoCropDetector.detect_tb :140-154 and detect_lr :156-170 (with rgb_to_y :117-138) and the accumulation of
  *   update :24-48 for a batch: x [B,3,H,W] f32 device; flat = 0 the black modes (Y clamped to the TV range, mean <= 32/255 and

@@ -154,6 +154,13 @@ SIGNATURES = {
     "nunif_hip_superpoint_match": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                             c_void_p]),
     "nunif_hip_affine_warp": (c_int32, [c_void_p, c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p]),
+    "nunif_hip_outpaint_create": (c_int32, [ctypes.POINTER(TensorDesc), c_int32, ctypes.POINTER(c_void_p)]),
+    "nunif_hip_outpaint_destroy": (None, [c_void_p]),
+    "nunif_hip_outpaint_work_bytes": (c_int64, [c_int32] * 4),
+    "nunif_hip_outpaint_infer": (c_int32, [c_void_p, c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p, c_void_p, c_void_p]),
+    "nunif_hip_outpaint_debug_taps": (c_int32, [c_void_p, c_void_p] + [c_int32] * 4 + [c_char_p, c_void_p, c_int64,
+                                                ctypes.POINTER(c_int64), c_void_p]),
+    "nunif_hip_outpaint_buffer_step": (c_int32, [c_void_p] * 4 + [c_double] + [c_int32] * 3 + [c_void_p] * 3),
     "nunif_hip_autocrop_stats": (c_int32, [c_void_p] + [c_int32] * 5 + [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "nunif_hip_autocrop_debug_stats": (c_int32, [c_void_p] + [c_int32] * 5 + [c_void_p, c_void_p, c_void_p, c_int64] +
                                        [c_void_p] * 5),

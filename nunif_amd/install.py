@@ -96,7 +96,14 @@ _CONSUMER_ROOTS = ("nunif", "waifu2x", "iw3", "stlizer", "cliqa")
 _MODEL_MODULES = [("waifu2x.models", ["nunif_amd.waifu2x.models.swin_unet", "nunif_amd.waifu2x.models.cunet",
                                       "nunif_amd.waifu2x.models.vgg_7", "nunif_amd.waifu2x.models.upconv_7",
                                       "nunif_amd.waifu2x.models.swin_unet_v2"]),
-                  ("iw3.models", ["nunif_amd.iw3.models"])]
+                  ("iw3.models", ["nunif_amd.iw3.models"]),
+                  # stlizer.light_outpaint_v1 (pass 4 of stlizer/multipass_pipeline.py:380 loads it through load_model); the
+                  # reference package imports only torch and nunif.*: strict=True stays independent of PyAV
+                  ("stlizer.models", ["nunif_amd.stlizer.models"])]
+# Reference model packages that install() merges only when the process has already loaded them (the CLI layer is loaded before
+# install(), nunif_amd/launch.py, and stlizer/multipass_pipeline.py:13 imports its models).  Importing them here would register
+# their names in the reference's registry for every process: install() is a drop-in, it adds no name the process did not have.
+_ONLY_IF_LOADED = ("stlizer.models",)
 
 _state = None      # {"bindings": [(module, attr, original)], "registry": {name: original factory or _MISSING}}
 _MISSING = object()
@@ -148,6 +155,8 @@ def install(registry=True, strict=True):
             report["patched"][f"{ref_name}.{attr}"] = n
         if registry:
             for ref_models, our_modules in _MODEL_MODULES:
+                if ref_models in _ONLY_IF_LOADED and ref_models not in sys.modules:
+                    continue
                 try:
                     importlib.import_module(ref_models)
                 except Exception as e:
