@@ -583,6 +583,37 @@ int nunif_hip_autocrop_crop_pad(const float *src, float *dst, int64_t N, int32_t
                                 int32_t y0, int32_t x0, int32_t pad_top, int32_t pad_left, int32_t win_h, int32_t win_w,
                                 float pad_value, void *stream);
 
+/* iw3 desktop streaming (iw3/desktop/utils.py:99-123 to_uint8 + to_jpeg_data, called per frame at :383-389): a baseline JPEG
+ * encoder on the device, so that a frame crosses to the host as its JPEG stream and not as a uint8 image.  The encoder holds no
+ * weights: plain functions and a caller-owned workspace.  DESIGN.md ("JPEG frame encoder") states it step by step.
+ * quant_tables, header, max_bytes and workspace_bytes are host-only arithmetic (nunif_amd/csrc/jpeg_host.h), no GPU needed.
+ * quant_tables: the IJG scaling of the ITU T.81 Annex K tables for quality 1..100, baseline-clamped to 1..255 (libjpeg's
+ *   jpeg_set_quality(q, TRUE)), natural (row-major) order, into luma[64] and chroma[64] (host).
+ * header: SOI, APP0 (JFIF 1.01, units 0, 1:1), DQT x 2 (8 bit, zigzag), SOF0, DHT x 4 (Annex K), DRI, SOS into out (host,
+ *   capacity >= 629); returns the length (629) or a negative status.
+ * max_bytes: an upper bound of the stream of one frame: the header, per block its worst case of 1 660 bits, per interval the fill
+ *   of its last byte, every byte counted twice (a stuffed 0xFF), and the 2-byte RSTn / EOI marker.  -1 for a refused shape.
+ * workspace_bytes: the size of `workspace` for encode: coefficients [B][blocks][64] i16, two i32 per interval, and per interval
+ *   a staging slot of its worst case.  -1 for a refused shape.
+ * encode: rgb [B,3,H,W] f32 contiguous device memory in [0,1] (clamped; values are quantised as to_uint8 does, round half even)
+ *   -> B baseline JFIF streams, stream b at out + b * capacity (device), its length in out_len[b] (device i32).  subsampling 420
+ *   or 444; a restart interval of restart_mcus MCUs (1..65535; it may span MCU rows; intervals are the unit of parallelism).
+ *   Four launches on `stream`, no host synchronisation, no atomics on global memory: the bytes depend on the input alone.  If
+ *   capacity is smaller than the stream, out_len[b] = -1 and nothing of slot b is written; max_bytes is always enough.  workspace:
+ *   workspace_bytes() bytes of device memory, 256-byte aligned; calls that overlap need their own.  1 <= H, W <= 8192, B <= 16,
+ *   quality 1..100; anything else is refused.
+ * debug_coefficients (tests) runs the first launch alone: the quantised coefficients in scan order, [B][mcus * blocks_per_mcu][64]
+ *   i16 device memory: MCU by MCU in raster order, Y00 Y01 Y10 Y11 Cb Cr (420) or Y Cb Cr (444), each block in zigzag order. */
+int nunif_hip_jpeg_quant_tables(int32_t quality, uint8_t *luma, uint8_t *chroma);
+int64_t nunif_hip_jpeg_header(int32_t H, int32_t W, int32_t quality, int32_t subsampling, int32_t restart_mcus, uint8_t *out,
+                              int64_t capacity);
+int64_t nunif_hip_jpeg_max_bytes(int32_t H, int32_t W, int32_t subsampling, int32_t restart_mcus);
+int64_t nunif_hip_jpeg_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t subsampling, int32_t restart_mcus);
+int nunif_hip_jpeg_encode(const float *rgb, int32_t B, int32_t H, int32_t W, int32_t quality, int32_t subsampling,
+                          int32_t restart_mcus, uint8_t *out, int64_t capacity, int32_t *out_len, void *workspace, void *stream);
+int nunif_hip_jpeg_debug_coefficients(const float *rgb, int32_t B, int32_t H, int32_t W, int32_t quality, int32_t subsampling,
+                                      int16_t *coef, void *stream);
+
 /* Test hooks (tests/ only): snapshot every stage's NHWC fp16 output during the next forward calls, then read
  * them back one by one (returns 1 past the last tap).  Names match oracle.swin_unet.unet_forward(taps=...). */
 int nunif_hip_swin_unet_debug_taps(nunif_swin_unet *handle, int32_t enable);

@@ -165,6 +165,12 @@ SIGNATURES = {
     "nunif_hip_autocrop_debug_stats": (c_int32, [c_void_p] + [c_int32] * 5 + [c_void_p, c_void_p, c_void_p, c_int64] +
                                        [c_void_p] * 5),
     "nunif_hip_autocrop_crop_pad": (c_int32, [c_void_p, c_void_p, c_int64] + [c_int32] * 10 + [c_float, c_void_p]),
+    "nunif_hip_jpeg_quant_tables": (c_int32, [c_int32, c_void_p, c_void_p]),
+    "nunif_hip_jpeg_header": (c_int64, [c_int32] * 5 + [c_void_p, c_int64]),
+    "nunif_hip_jpeg_max_bytes": (c_int64, [c_int32] * 4),
+    "nunif_hip_jpeg_workspace_bytes": (c_int64, [c_int32] * 5),
+    "nunif_hip_jpeg_encode": (c_int32, [c_void_p] + [c_int32] * 6 + [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "nunif_hip_jpeg_debug_coefficients": (c_int32, [c_void_p] + [c_int32] * 5 + [c_void_p, c_void_p]),
     "nunif_hip_swin_unet_debug_taps":(c_int32, [c_void_p, c_int32]),
     "nunif_hip_swin_unet_get_tap": (c_int32, [c_void_p, c_int32, c_char_p, c_int32, c_void_p, c_int64,
                                               ctypes.POINTER(c_int64)]),

@@ -87,7 +87,14 @@ PATCHES = [
     ("nunif.utils.autocrop", "AutoCropDetector"),
     ("nunif.utils.autocrop", "AutoCrop"),
     ("nunif.utils.autocrop", "autocrop_analyze_video"),
+    # iw3.desktop's frame encoder (iw3/desktop/utils.py:110-123, called per streamed frame at :383-389).  The reference module
+    # imports wx and torchvision.io at its top: it is patched only in a process that has loaded it (_PATCH_ONLY_IF_LOADED).
+    ("iw3.desktop.utils", "to_jpeg_data"),
 ]
+
+# PATCHES entries of reference modules that install() never imports itself: the desktop streamer loads iw3.desktop.utils before it
+# calls install(), every other process neither has nor needs it, and strict=True must not depend on wx or torchvision
+_PATCH_ONLY_IF_LOADED = ("iw3.desktop.utils",)
 
 # reference packages whose modules may hold ``from ... import`` copies of a patched name
 _CONSUMER_ROOTS = ("nunif", "waifu2x", "iw3", "stlizer", "cliqa")
@@ -133,6 +140,8 @@ def install(registry=True, strict=True):
     try:
         jobs = []
         for ref_name, attr in PATCHES:
+            if ref_name in _PATCH_ONLY_IF_LOADED and ref_name not in sys.modules:
+                continue
             try:
                 ref_mod = importlib.import_module(ref_name)
                 ours = getattr(importlib.import_module("nunif_amd." + ref_name), attr)
