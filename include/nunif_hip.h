@@ -614,6 +614,27 @@ int nunif_hip_jpeg_encode(const float *rgb, int32_t B, int32_t H, int32_t W, int
 int nunif_hip_jpeg_debug_coefficients(const float *rgb, int32_t B, int32_t H, int32_t W, int32_t quality, int32_t subsampling,
                                       int16_t *coef, void *stream);
 
+/* HDR -> SDR tone mapping of one decoded frame (nunif/utils/video.py:309-416 hdr2sdr, called per frame by process_video's
+ * input_reformatter :1025-1036): x / 65535 (:325), inverse EOTF (PQ :330-333, HLG :338-344), exposure (:354), Hable map over the
+ * Hable map of the white point (:356-369), the HLG luma mix (:363-367), the BT.2020 -> bt709 / bt601 matrix (:372-387), clamp,
+ * OETF with its linear toe (:391-395), clamp, in ONE launch.  DESIGN.md ("HDR to SDR") states how the powers are evaluated.
+ * src: rgb48 HWC [H][W][3], uint16, in device memory or pinned host memory (read zero-copy).  trc: 16 (SMPTE 2084, PQ) or 18
+ * (ARIB STD-B67, HLG); colorspace: 709 or 601; H, W <= 8192; anything else is refused with NUNIF_HIP_EINVAL.
+ * params: exposure and white_point of the curve in use (pq_* for trc 16, hlg_* for trc 18); saturation_gain is read for HLG only.
+ * form 0 (u16): dst HWC uint16 = trunc(v * 65535), what the reference's function returns (:398); device or pinned host memory.
+ * form 1 (chw): dst [3][H][W] fp32 = float(trunc(v * 65535)) / 65535 by IEEE division: what VU.to_tensor (:218-223) makes of the
+ *   reference's frame.
+ * form 2 (debug, tests): dst HWC fp32 = v itself, the value before `* 65535`.
+ * hdr2sdr_constants is host-only: the matrix (row major, 9 floats) and hable_map(white_point) in the reference's fp32 expressions,
+ *   exactly the kernel's arguments. */
+typedef struct nunif_hdr2sdr_params {
+    double exposure, white_point, saturation_gain;
+} nunif_hdr2sdr_params;
+int nunif_hip_hdr2sdr(const void *src, void *dst, int32_t H, int32_t W, int32_t trc, int32_t colorspace,
+                      const nunif_hdr2sdr_params *params, int32_t form, void *stream);
+int nunif_hip_hdr2sdr_constants(int32_t trc, int32_t colorspace, const nunif_hdr2sdr_params *params, float *matrix,
+                                float *hable_white);
+
 /* Test hooks (tests/ only): snapshot every stage's NHWC fp16 output during the next forward calls, then read
  * them back one by one (returns 1 past the last tap).  Names match oracle.swin_unet.unet_forward(taps=...). */
 int nunif_hip_swin_unet_debug_taps(nunif_swin_unet *handle, int32_t enable);

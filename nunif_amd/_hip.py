@@ -44,6 +44,11 @@ class ForwardWarpParams(ctypes.Structure):
                 ("fill", c_int32), ("synthetic_view", c_int32), ("width_base", c_int32), ("convergence_dev", c_void_p)]
 
 
+class Hdr2SdrParams(ctypes.Structure):
+    """``nunif_hdr2sdr_params``: exposure and white point of the curve in use, and hlg_saturation_gain (video.py:311-312)."""
+    _fields_ = [("exposure", c_double), ("white_point", c_double), ("saturation_gain", c_double)]
+
+
 class ProfRecord(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 48), ("total_ms", c_double), ("launches", c_int64),
                 ("flops", c_double), ("bytes", c_double)]
@@ -171,6 +176,10 @@ SIGNATURES = {
     "nunif_hip_jpeg_workspace_bytes": (c_int64, [c_int32] * 5),
     "nunif_hip_jpeg_encode": (c_int32, [c_void_p] + [c_int32] * 6 + [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "nunif_hip_jpeg_debug_coefficients": (c_int32, [c_void_p] + [c_int32] * 5 + [c_void_p, c_void_p]),
+    "nunif_hip_hdr2sdr": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, ctypes.POINTER(Hdr2SdrParams), c_int32,
+                                    c_void_p]),
+    "nunif_hip_hdr2sdr_constants": (c_int32, [c_int32, c_int32, ctypes.POINTER(Hdr2SdrParams), ctypes.POINTER(c_float),
+                                              ctypes.POINTER(c_float)]),
     "nunif_hip_swin_unet_debug_taps":(c_int32, [c_void_p, c_int32]),
     "nunif_hip_swin_unet_get_tap": (c_int32, [c_void_p, c_int32, c_char_p, c_int32, c_void_p, c_int64,
                                               ctypes.POINTER(c_int64)]),

@@ -87,6 +87,11 @@ PATCHES = [
     ("nunif.utils.autocrop", "AutoCropDetector"),
     ("nunif.utils.autocrop", "AutoCrop"),
     ("nunif.utils.autocrop", "autocrop_analyze_video"),
+    # HDR -> SDR tone mapping of a decoded frame (nunif/utils/video.py:309-416); process_video's input_reformatter (:1025-1036)
+    # finds it as a global of its own module, so re-binding it there is enough.  Every process that gets this far has loaded
+    # nunif.utils.video already (nunif.utils.autocrop above imports it), so the entry needs no _PATCH_ONLY_IF_LOADED: where PyAV
+    # is missing, strict=False skips it together with the autocrop entries.
+    ("nunif.utils.video", "hdr2sdr"),
     # iw3.desktop's frame encoder (iw3/desktop/utils.py:110-123, called per streamed frame at :383-389).  The reference module
     # imports wx and torchvision.io at its top: it is patched only in a process that has loaded it (_PATCH_ONLY_IF_LOADED).
     ("iw3.desktop.utils", "to_jpeg_data"),

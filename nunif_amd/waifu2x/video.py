@@ -28,13 +28,15 @@ def _frame_pixels(frame):
 
 
 class Waifu2xVideoStream:
-    def __init__(self, ctx, args, device=None, depth=3, seed=None, use_16bit=None):
+    def __init__(self, ctx, args, device=None, depth=3, seed=None, use_16bit=None, hdr=None):
         """``ctx``: a loaded ``Waifu2x`` context; ``args``: the reference's argparse namespace (``method``, ``noise_level``,
         ``tile_size``, ``batch_size``, ``tta``, ``disable_amp``, ``rotate_left`` / ``rotate_right``, ``grain``,
         ``grain_strength``, ``grain_speed``, ``pix_fmt``).  ``seed``: the grain seed; by default torch's
         ``torch.initial_seed()`` at construction, so ``torch.manual_seed`` makes a run repeatable.  ``use_16bit``: the output
         depth when the caller has already asked ``VU.pix_fmt_requires_16bit(args.pix_fmt)``; by default the engine's own copy of
-        that rule.  The depth of the frames going in is each frame's own (uint8 or uint16), as in ``VU.to_tensor``."""
+        that rule.  The depth of the frames going in is each frame's own (uint8 or uint16), as in ``VU.to_tensor``.  ``hdr``: an
+        entry from ``nunif_amd.nunif.utils.hdr.hdr_entry`` — the frames going in are then the rgb48 frames of a BT.2020 PQ / HLG
+        source as decoded, and the tone mapping of ``VU.hdr2sdr`` is the ring's entry step (not together with a quarter turn)."""
         self.ctx, self.args = ctx, args
         self.device = torch.device(device if device is not None else ctx.device)
         if self.device.type != "cuda":
@@ -44,6 +46,10 @@ class Waifu2xVideoStream:
             use_16bit = pix_fmt_requires_16bit(getattr(args, "pix_fmt", None))
         self.bits = 16 if use_16bit else 8
         self.turns = 1 if getattr(args, "rotate_left", False) else 3 if getattr(args, "rotate_right", False) else 0
+        self.hdr = hdr
+        if hdr is not None and self.turns:
+            raise ValueError("Waifu2xVideoStream: hdr= cannot be combined with --rotate-left / --rotate-right: the tone-mapping "
+                             "entry has no quarter turn; tone-map with VU.hdr2sdr first and pass the SDR frames")
         self.grain = bool(getattr(args, "grain", False))
         self.grain_strength = float(getattr(args, "grain_strength", 0.2))
         self.grain_speed = float(getattr(args, "grain_speed", 0.8))
@@ -69,6 +75,8 @@ class Waifu2xVideoStream:
 
     # ---- the three steps the ring runs ----------------------------------------------------------------------------------
     def _enter(self, hwc, device=None):
+        if self.hdr is not None:
+            return self.hdr(hwc, device=device)
         return _ops.frame_to_tensor(hwc, device=device, turns=self.turns)
 
     def _convert(self, rgb):
@@ -112,6 +120,8 @@ class Waifu2xVideoStream:
         if frame.dtype not in (np.uint8, np.uint16):
             raise ValueError(f"unsupported frame dtype {frame.dtype}")
         in_bits = 16 if frame.dtype == np.uint16 else 8      # a 10-bit source keeps its depth whatever the output pixel format is
+        if self.hdr is not None and in_bits != 16:
+            raise ValueError("Waifu2xVideoStream: hdr= needs rgb48 (uint16) frames")
         flushed = []
         if self._ring is None or tuple(frame.shape) != self._in_shape or in_bits != self._in_bits:
             flushed = self.drain()                      # a new frame size or depth: everything in flight leaves first
