@@ -635,6 +635,32 @@ int nunif_hip_hdr2sdr(const void *src, void *dst, int32_t H, int32_t W, int32_t 
 int nunif_hip_hdr2sdr_constants(int32_t trc, int32_t colorspace, const nunif_hdr2sdr_params *params, float *matrix,
                                 float *hable_white);
 
+/* Planar YUV <-> the CHW fp32 tensor: the two pixel-format conversions of process_video (nunif/utils/video.py), one launch each,
+ * no host synchronisation, no atomics.  DESIGN.md ("Pixel formats") and csrc/pixfmt.hip state the arithmetic: ITU coefficients in
+ * fp32 and linear chroma resampling for the MPEG-2 / H.264 default chroma position — deliberately not swscale's fixed point.
+ * format: 0 yuv420p, 1 yuv444p (uint8), 2 yuv420p10le (uint16, 10 significant bits); matrix: 601, 709 or 2020 (non-constant
+ * luminance); full_range: 0 limited, 1 full (the yuvj* formats); 1 <= H, W <= 8192; anything else is refused with NUNIF_HIP_EINVAL.
+ * planes: data[i] in device memory or pinned host memory (zero-copy), pitch[i] the BYTE pitch of plane i (>= its row; PyAV's
+ *   plane.line_size); chroma planes hold ceil(W / 2) x ceil(H / 2) samples at 4:2:0.  Padding bytes are never written.
+ * yuv_to_tensor: frame.reformat(**rgb24_options) (:1038-1039, options of guess_rgb24_options :621-640, matrix / range of
+ *   guess_colorspace :610-618 / guess_color_range :596-607) followed by to_tensor (:218-223).  dst [3][H][W] fp32 in [0, 1];
+ *   form 1 (debug, tests) does not clamp.  frame (optional, form 0 only): the HWC rgb24 (8-bit formats) / rgb48 (10-bit) frame,
+ *   written in the same launch; device or pinned memory.
+ * tensor_to_yuv: to_frame (:259-269) followed by reformatter(new_frame) (:1084, built by configure_colorspace :763-854).  src
+ *   [3][H][W] fp32, clamped to [0, 1]; codes are rounded half up and clamped to [0, 2^bits - 1].
+ * pixfmt_constants is host-only: the 3 x 3 coefficients (row major) and the 3 code offsets the kernels use for (matrix,
+ *   full_range, bits 8 or 10, direction 0 = yuv -> rgb: rgb = M (yuv - off); 1 = rgb -> yuv: yuv = M rgb + off). */
+typedef struct nunif_pixfmt_planes {
+    void *data[3];
+    int64_t pitch[3];
+} nunif_pixfmt_planes;
+int nunif_hip_yuv_to_tensor(const nunif_pixfmt_planes *src, int32_t format, int32_t H, int32_t W, int32_t matrix,
+                            int32_t full_range, int32_t form, float *dst, void *frame, void *stream);
+int nunif_hip_tensor_to_yuv(const float *src, int32_t H, int32_t W, int32_t format, int32_t matrix, int32_t full_range,
+                            const nunif_pixfmt_planes *dst, void *stream);
+int nunif_hip_pixfmt_constants(int32_t matrix, int32_t full_range, int32_t bits, int32_t direction, float *coefficients,
+                               float *offsets);
+
 /* Test hooks (tests/ only): snapshot every stage's NHWC fp16 output during the next forward calls, then read
  * them back one by one (returns 1 past the last tap).  Names match oracle.swin_unet.unet_forward(taps=...). */
 int nunif_hip_swin_unet_debug_taps(nunif_swin_unet *handle, int32_t enable);

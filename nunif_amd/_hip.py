@@ -49,6 +49,11 @@ class Hdr2SdrParams(ctypes.Structure):
     _fields_ = [("exposure", c_double), ("white_point", c_double), ("saturation_gain", c_double)]
 
 
+class PixfmtPlanes(ctypes.Structure):
+    """``nunif_pixfmt_planes``: the three plane pointers of a planar YUV frame and their byte pitches (PyAV's ``line_size``)."""
+    _fields_ = [("data", c_void_p * 3), ("pitch", c_int64 * 3)]
+
+
 class ProfRecord(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 48), ("total_ms", c_double), ("launches", c_int64),
                 ("flops", c_double), ("bytes", c_double)]
@@ -180,6 +185,9 @@ SIGNATURES = {
                                     c_void_p]),
     "nunif_hip_hdr2sdr_constants": (c_int32, [c_int32, c_int32, ctypes.POINTER(Hdr2SdrParams), ctypes.POINTER(c_float),
                                               ctypes.POINTER(c_float)]),
+    "nunif_hip_yuv_to_tensor": (c_int32, [ctypes.POINTER(PixfmtPlanes)] + [c_int32] * 6 + [c_void_p, c_void_p, c_void_p]),
+    "nunif_hip_tensor_to_yuv": (c_int32, [c_void_p] + [c_int32] * 5 + [ctypes.POINTER(PixfmtPlanes), c_void_p]),
+    "nunif_hip_pixfmt_constants": (c_int32, [c_int32] * 4 + [ctypes.POINTER(c_float), ctypes.POINTER(c_float)]),
     "nunif_hip_swin_unet_debug_taps":(c_int32, [c_void_p, c_int32]),
     "nunif_hip_swin_unet_get_tap": (c_int32, [c_void_p, c_int32, c_char_p, c_int32, c_void_p, c_int64,
                                               ctypes.POINTER(c_int64)]),

@@ -30,7 +30,9 @@ EXTRA_FLAGS = {"stitch.hip": ["-ffp-contract=off"], "iw3_warp.hip": ["-ffp-contr
                "transnetv2.hip": NO_SLP, "sod_v1.hip": NO_SLP, "superpoint.hip": NO_SLP, "outpaint.hip": NO_SLP,
                "jpeg.hip": NO_SLP,
                # hdr.hip: the reference's fp32 expressions operation by operation (its error is the tests' yardstick)
-               "hdr.hip": ["-ffp-contract=off"] + NO_SLP}
+               "hdr.hip": ["-ffp-contract=off"] + NO_SLP,
+               # pixfmt.hip: every multiply and add is one rounding, in the order tests/pixfmt_ref.py states them
+               "pixfmt.hip": ["-ffp-contract=off"] + NO_SLP}
 
 
 def sources():

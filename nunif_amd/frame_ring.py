@@ -21,7 +21,7 @@ from .iw3 import _ops
 
 class FrameRing:
     def __init__(self, process_fn, in_shape, out_shape, device="cuda:0", depth=3, bits=8, zero_copy=True, out_mode="copy",
-                 edge_streams=True, enter_fn=None, leave_fn=None, in_bits=None):
+                 edge_streams=True, enter_fn=None, leave_fn=None, in_bits=None, in_bytes=None, out_bytes=None):
         """``process_fn(chw_float_tensor) -> chw_float_tensor in [0,1]`` runs on the ring's stream.
         in_shape / out_shape: (H, W, 3) of the uint8 (or uint16 when bits=16) HWC frames.
 
@@ -31,6 +31,9 @@ class FrameRing:
         stream or on their own, blocked the submitting thread for a whole frame time (5-7 ms inside ``copy_``) and
         the pipeline ran at 19-20 ms per 1080p 2x frame against 9.5 ms of GPU work."""
         assert bits in (8, 16) and out_mode in ("copy", "view")
+        if (in_bytes is not None or out_bytes is not None) and not zero_copy:
+            # the staged route would copy whole slots, pitch padding included, and the leave step would allocate per frame
+            raise ValueError("FrameRing: planar slots (in_bytes / out_bytes) need zero_copy=True")
         # in_bits: the bit depth of the frames going IN when it is not the output's (a 10-bit source written to an 8-bit pixel
         # format, or the reverse): the entry kernel divides by the source's own maximum, as VU.to_tensor does
         self.in_bits = in_bits = bits if in_bits is None else in_bits
@@ -53,7 +56,20 @@ class FrameRing:
         if self.device.type != "cuda":
             raise RuntimeError("FrameRing needs a ROCm device; there is no CPU path")
         self.process_fn, self.bits, self.depth, self.zero_copy = process_fn, bits, depth, zero_copy
-        t_dtype = torch.uint8 if bits == 8 else torch.int16          # int16 carries the uint16 bit pattern
+        # in_bytes / out_bytes: that side's slot is a FLAT BYTE buffer holding the planes of a planar frame (yuv420p ...), not an
+        # HWC frame, and in_shape / out_shape of that side are ignored; the caller's enter_fn / leave_fn
+        # (nunif_amd.nunif.utils.pixfmt.yuv_entry / yuv_leave) know the layout.  Either an int (the byte size) or an object with
+        # ``nbytes`` and ``views(flat uint8 array)`` (a pixfmt.PlaneLayout): input_buffer() then hands out the planes as views.
+        self.in_planes, self.out_planes = in_bytes, out_bytes
+        if in_bytes is not None:
+            in_shape, in_bits, self.in_bits = (int(getattr(in_bytes, "nbytes", in_bytes)),), 8, 8
+            if enter_fn is None:
+                raise ValueError("FrameRing: in_bytes needs an enter_fn that reads the planes")
+        if out_bytes is not None:
+            out_shape = (int(getattr(out_bytes, "nbytes", out_bytes)),)
+            if leave_fn is None:
+                raise ValueError("FrameRing: out_bytes needs a leave_fn that writes the planes")
+        t_dtype = torch.uint8 if bits == 8 or out_bytes is not None else torch.int16   # int16 carries the uint16 bit pattern
         i_dtype = torch.uint8 if in_bits == 8 else torch.int16
         self.slots = []
         for _ in range(depth):
@@ -86,7 +102,7 @@ class FrameRing:
             # host memcpy into the pinned buffer — with numpy, NOT ``Tensor.copy_``: torch's copy into a pinned tensor took
             # 0.14 ms at the median but 70-90 ms every 3rd-4th frame (tools/ring_trace.py: 13 of round 1's 21 ms per frame;
             # the "platform stall" of DESIGN.md round 1 was this call), np.copyto is a flat 0.13 ms
-            np.copyto(slot["h_in"].numpy(), frame.view(np.int16) if self.in_bits == 16 else frame)
+            np.copyto(slot["h_in"].numpy(), frame.view(np.int16) if self.in_bits == 16 and self.in_planes is None else frame)
         if self.zero_copy and self.edge_streams:
             # three streams: the PCIe-bound edge kernels of neighbouring frames (0.12 ms in, 0.45 ms out for 1080p -> 2x) run
             # beside the render of the frame in the middle instead of in front of / behind it on one stream
@@ -128,7 +144,7 @@ class FrameRing:
         buf = slot["h_out"]
         slot["h_out"], self._spare = self._spare, buf      # the consumer's buffer leaves the rotation until the next collect
         arr = buf.numpy()
-        out = arr.view(np.uint16) if self.bits == 16 else arr
+        out = arr.view(np.uint16) if self.bits == 16 and self.out_planes is None else arr
         if self.out_mode == "copy":
             out = out.copy()
         slot["busy"] = False
@@ -142,6 +158,8 @@ class FrameRing:
         if slot["busy"]:
             self._held = self._collect()
         arr = self.slots[self._next]["h_in"].numpy()
+        if self.in_planes is not None:                       # a planar slot: the planes as views, or the flat bytes
+            return self.in_planes.views(arr) if hasattr(self.in_planes, "views") else arr
         return arr.view(np.uint16) if self.in_bits == 16 else arr
 
     def drain(self):

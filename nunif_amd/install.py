@@ -92,6 +92,10 @@ PATCHES = [
     # nunif.utils.video already (nunif.utils.autocrop above imports it), so the entry needs no _PATCH_ONLY_IF_LOADED: where PyAV
     # is missing, strict=False skips it together with the autocrop entries.
     ("nunif.utils.video", "hdr2sdr"),
+    # the two pixel-format conversions of process_video's loop (nunif/utils/video.py:763-854 builds them, :1038-1039 and :1084 run
+    # them): process_video (:1016) finds configure_colorspace as a global of its own module.  The engine's function runs the
+    # reference's and then takes both conversions over only for an engine frame callback and planar formats on both ends.
+    ("nunif.utils.video", "configure_colorspace"),
     # iw3.desktop's frame encoder (iw3/desktop/utils.py:110-123, called per streamed frame at :383-389).  The reference module
     # imports wx and torchvision.io at its top: it is patched only in a process that has loaded it (_PATCH_ONLY_IF_LOADED).
     ("iw3.desktop.utils", "to_jpeg_data"),

@@ -61,9 +61,33 @@ class PipelineOps:
     """Device functions used by the scheduler.  Defaults: the HIP engine (``nunif_amd.iw3.utils``)."""
 
     def __init__(self, to_tensor=None, preprocess_image=None, apply_divergence=None, apply_rgbd=None,
-                 postprocess_image=None, to_frame=None):
+                 postprocess_image=None, to_frame=None,
+                 in_format=None, in_matrix="bt709", in_full_range=False,
+                 out_format=None, out_matrix="bt709", out_full_range=False):
+        """``in_format`` / ``in_matrix`` / ``in_full_range``: the frames going in are the decoder's planes (``frame.data`` is a
+        pair ``(flat uint8 array or tensor, pixfmt.PlaneLayout)`` of that format) and ``to_tensor`` is the engine's planar entry;
+        ``out_format`` / ``out_matrix`` / ``out_full_range``: a stereo pair leaves as the encoder's planes (a flat uint8 tensor in
+        ``out_layout(h, w)``) instead of an HWC frame.  By default both ends are rgb, as before."""
         from . import utils as U
-        self.to_tensor = to_tensor or (lambda frame, device=None: U.to_tensor(_frame_pixels(frame), device=device))
+        from ..nunif.utils import pixfmt
+        for name, fmt, matrix in (("in", in_format, in_matrix), ("out", out_format, out_matrix)):
+            if fmt is not None and pixfmt._ALIASES.get(fmt, fmt) not in pixfmt.FORMATS:
+                raise ValueError(f"PipelineOps: {name}_format must be one of {sorted(pixfmt.FORMATS)}, got {fmt!r}")
+            if fmt is not None and matrix not in pixfmt.MATRICES:
+                raise ValueError(f"PipelineOps: {name}_matrix must be one of {sorted(pixfmt.MATRICES)}, got {matrix!r}")
+        if in_format is not None and to_tensor is not None:
+            raise ValueError("PipelineOps: in_format= replaces to_tensor; pass one of them")
+        if out_format is not None and to_frame is not None:
+            raise ValueError("PipelineOps: out_format= replaces to_frame; pass one of them")
+        self.in_format, self.in_matrix = pixfmt._ALIASES.get(in_format, in_format), in_matrix
+        self.in_full_range = bool(in_full_range) or (in_format or "").startswith("yuvj")
+        self.out_format, self.out_matrix = pixfmt._ALIASES.get(out_format, out_format), out_matrix
+        self.out_pix_fmt = out_format      # the name as given (a yuvj* alias stays): what an av.VideoFrame of the planes is called
+        self.out_full_range = bool(out_full_range) or (out_format or "").startswith("yuvj")
+        self._config = None                # a VideoOutputConfig whose state may name the formats at the first frame: bind_config
+        self._own_edges = to_tensor is None and to_frame is None
+        self._staging, self._staged = [], 0
+        self.to_tensor = to_tensor or self._to_tensor
         self.preprocess_image = preprocess_image or U.preprocess_image
         self.apply_divergence = apply_divergence or U.apply_divergence
         self.apply_rgbd = apply_rgbd or U.apply_rgbd
@@ -73,8 +97,99 @@ class PipelineOps:
         # format allows); a caller's own postprocess_image / to_frame keep the two-step route
         self._fused_out = U.postprocess_to_frame if (postprocess_image is None and to_frame is None) else None
 
+    def bind_config(self, config, vf=""):
+        """For the owner of a ``VU.process_video`` run whose frame callback comes from one of the binders below, on the
+        ``VideoOutputConfig`` its ``config_callback`` returns: declares the callback as the engine's (not with a software ``--vf``,
+        nor with a caller's own ``to_tensor`` / ``to_frame`` or formats given up front).  Where the engine's
+        ``configure_colorspace`` then records ``config.state["engine_pixfmt"]``, the six format options are taken from there at
+        the first frame: the scheduler is handed the decoder's frames and returns the encoder's planes."""
+        from ..nunif.utils.video import declare_engine_callback
+        fixed = not self._own_edges or self.in_format is not None or self.out_format is not None
+        self._config = config if declare_engine_callback(config, vf=vf, turns=fixed) else None
+
+    def _settle(self):
+        if self._config is not None:
+            from ..nunif.utils.video import ENGINE_PIXFMT
+            config, self._config = self._config, None
+            plan = config.state.get(ENGINE_PIXFMT)
+            if plan:                    # names as configure_colorspace records them: already checked
+                from ..nunif.utils import pixfmt
+                self.in_format, self.in_matrix, self.in_full_range = plan["in_format"], plan["in_matrix"], plan["in_full_range"]
+                self.out_pix_fmt, self.out_matrix, self.out_full_range = \
+                    plan["out_format"], plan["out_matrix"], plan["out_full_range"]
+                self.out_format = pixfmt._ALIASES.get(self.out_pix_fmt, self.out_pix_fmt)
+
+    def _to_tensor(self, frame, device=None):
+        from . import utils as U
+        self._settle()
+        if self.in_format is not None:
+            return self._planes_to_tensor(frame, device=device)
+        return U.to_tensor(_frame_pixels(frame), device=device)
+
+    def _pinned_slot(self, nbytes):
+        """One of four pinned staging buffers, handed out in turn; the kernel that read a buffer zero-copy on its last turn has
+        finished before it is written again (its event)."""
+        i, self._staged = self._staged % 4, self._staged + 1
+        if len(self._staging) <= i:
+            self._staging.append([torch.empty(nbytes, dtype=torch.uint8).pin_memory(), None])
+        slot = self._staging[i]
+        if slot[1] is not None:                      # before the buffer is written OR dropped: the host allocator knows nothing of
+            slot[1].synchronize()                    # a kernel's zero-copy read
+            slot[1] = None
+        if slot[0].numel() < nbytes:
+            slot[0] = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+        return slot
+
+    def _planes_to_tensor(self, frame, device=None):
+        """The planes always reach the kernel in device or PINNED memory, read zero-copy: a pinned or device tensor as it is; a
+        numpy array, an unpinned tensor or a decoded ``av.VideoFrame`` through one host copy into a pinned staging buffer."""
+        import numpy as np
+        from ..nunif.utils import pixfmt
+        slot = None
+        if hasattr(frame, "planes") and hasattr(frame, "format") and not isinstance(getattr(frame, "data", None), tuple):
+            name = pixfmt._ALIASES.get(frame.format.name, frame.format.name)
+            layout = pixfmt.PlaneLayout(name, frame.width, frame.height) if name in pixfmt.FORMATS else name
+            if layout != name and name == self.in_format:
+                slot = self._pinned_slot(layout.nbytes)
+                pixfmt.copy_av_planes(frame, layout, layout.views(slot[0].numpy()))
+                buf = slot[0]
+        else:
+            try:
+                buf, layout = frame.data
+            except (AttributeError, TypeError, ValueError):
+                raise ValueError("PipelineOps: with in_format= a frame's data is a pair (flat uint8 buffer, PlaneLayout)") from None
+        if not isinstance(layout, pixfmt.PlaneLayout) or layout.format != self.in_format:
+            raise ValueError(f"PipelineOps: the frame's layout is {layout!r}, the scheduler was opened for {self.in_format}")
+        if slot is None and not (torch.is_tensor(buf) and (buf.is_cuda or buf.is_pinned())):
+            if device is None or torch.device(device).type != "cuda":
+                raise RuntimeError("PipelineOps: the planar entry needs a ROCm device; there is no CPU fallback")
+            host = buf.numpy() if torch.is_tensor(buf) else np.asarray(buf)
+            if host.dtype != np.uint8 or host.ndim != 1 or host.size < layout.nbytes:
+                raise ValueError(f"PipelineOps: the planes must be a flat uint8 buffer of {layout.nbytes} bytes")
+            slot = self._pinned_slot(layout.nbytes)
+            np.copyto(slot[0].numpy()[:layout.nbytes], host[:layout.nbytes])
+            buf = slot[0]
+        x = pixfmt.yuv_to_tensor(buf, layout, self.in_matrix, self.in_full_range, device=device)
+        if slot is not None:
+            slot[1] = torch.cuda.Event()
+            slot[1].record(torch.cuda.current_stream(x.device))
+        return x
+
+    def out_layout(self, height, width):
+        """The layout of the planes ``stereo_out`` writes for an output image of ``height`` x ``width``."""
+        from ..nunif.utils import pixfmt
+        return pixfmt.PlaneLayout(self.out_format, width, height)
+
     def stereo_out(self, left_eye, right_eye, args, use_16bit=False):
         """One stereo pair -> the output frame: ``to_frame(postprocess_image(left, right, args))``."""
+        self._settle()
+        if self.out_format is not None:
+            from ..nunif.utils import pixfmt
+            sbs = self.postprocess_image(left_eye, right_eye, args)
+            layout = self.out_layout(sbs.shape[-2], sbs.shape[-1])
+            planes = pixfmt.tensor_to_yuv(sbs, layout, self.out_matrix, self.out_full_range)
+            planes.plane_layout = layout             # for whoever wraps the planes into a frame: bind_av_frame_callback
+            return planes
         if self._fused_out is not None:
             return self._fused_out(left_eye, right_eye, args, use_16bit=use_16bit)
         return self.to_frame(self.postprocess_image(left_eye, right_eye, args), use_16bit=use_16bit)
@@ -344,6 +459,34 @@ def bind_vda_frame_callback(depth_model, side_model, segment_pts, args, ops=None
         return _batch_infer() if len(batch_queue) == args.batch_size else None
 
     depth_model.reset()
+    return frame_callback
+
+
+def bind_av_frame_callback(depth_model, side_model, segment_pts, args, config, to_frame, vf="", to_planar_frame=None):
+    """``bind_single_frame_callback`` as the ``frame_callback`` of a ``VU.process_video`` run: decoded ``av.VideoFrame`` s in, a list
+    of ``av.VideoFrame`` s out.  ``config``: the ``VideoOutputConfig`` the run's ``config_callback`` returns — call this from
+    inside that callback: the op table declares itself on it (``PipelineOps.bind_config``), and where the engine's
+    ``configure_colorspace`` answers with ``config.state["engine_pixfmt"]`` the frames enter as the decoder's planes and leave as
+    the encoder's, under the pixel-format name the encoder was opened with.  Otherwise they are the rgb frames they were:
+    ``to_frame`` is the reference's ``VU.to_frame``.  ``to_planar_frame(planes, layout, format=name)``: by default
+    ``pixfmt.to_av_frame``."""
+    import numpy as np
+    from ..nunif.utils import pixfmt
+    ops = PipelineOps()
+    ops.bind_config(config, vf=vf)
+    inner = bind_single_frame_callback(depth_model, side_model, segment_pts, args, ops=ops)
+
+    def wrap(out):
+        layout = getattr(out, "plane_layout", None)
+        if layout is not None:
+            return (to_planar_frame or pixfmt.to_av_frame)(out.cpu().numpy(), layout, format=ops.out_pix_fmt)
+        arr = out.cpu().numpy()                      # a quantised HWC frame; int16 carries the uint16 bit pattern (_ops.to_frame)
+        return to_frame(arr.view(np.uint16) if arr.dtype == np.int16 else arr)
+
+    def frame_callback(frame):
+        return [wrap(out) for out in inner(frame)]
+
+    frame_callback.ops = ops
     return frame_callback
 
 
