@@ -661,6 +661,41 @@ int nunif_hip_tensor_to_yuv(const float *src, int32_t H, int32_t W, int32_t form
 int nunif_hip_pixfmt_constants(int32_t matrix, int32_t full_range, int32_t bits, int32_t direction, float *coefficients,
                                float *offsets);
 
+/* cliqa's image-quality nets and patch selection (nunif_amd/csrc/cliqa.hip), eval mode, fp16 operands with fp32 accumulation
+ * (the reference runs them under fp16 autocast, cliqa/utils.py:65,78,91), NHWC fp16 maps.
+ * create replaces the constructors and eval-mode BatchNorm of cliqa/models/jpeg_quality.py JPEGQuality :8-41 (kind 0),
+ *   grain_noise_level.py GrainNoiseLevel :8-34 (kind 1) and scale_factor.py ScaleFactor :10-36 (kind 2).  It takes the weights
+ *   with BatchNorm folded on the host (nunif_amd/cliqa/models/_net.py pack_weights), all fp32:
+ *   conv1.w [64][Cin][3][3] (Cin 6 for kind 0, 3 otherwise), conv1.b [64]; conv2.w [128][64][3][3], conv2.b [128];
+ *   rb1a / rb1b / rb2a / rb2b .w [128][128][3][3], .b [128] (the two convs of each ResBlock, nunif/modules/res_block.py:55-63);
+ *   head<i>.w [256][128][3][3], head<i>.b [256], head<i>.ow [256], head<i>.ob [1] (i = 0; kind 0 also i = 1, the subsampling head).
+ * forward replaces JPEGQuality.forward :70-75 (with preprocess :57-68), GrainNoiseLevel.forward :52-58 and ScaleFactor.forward
+ *   :53-63 (eval: clamped to [1, 2]): x [B,3,H,W] f32 device in [0, 1], any B, any H, W >= 8 -> out0 [B] f32 (quality, noise level
+ *   or scale factor), out1 [B] f32 (kind 0: subsampling logit; NULL otherwise).  The batch is walked in groups of at most `group` images
+ *   (0, or more than 2^23 input pixels hold: as many as those hold; H W <= 2^26).  workspace: caller-owned device bytes,
+ *   nunif_hip_cliqa_workspace_bytes(handle, B, H, W, group) of them (0 for a shape forward refuses), so that calls on different
+ *   streams never share scratch; forward is told how many it got (workspace_bytes) and refuses fewer than it needs
+ *   (NUNIF_HIP_EINVAL).  The layout is csrc/cliqa_host.h.  No host synchronisation, no atomics.
+ * debug_taps (tests only) is forward plus the maps behind the three pools (features[6], [8], [10]: tap1 [B,H/2,W/2,128], tap2
+ *   [B,H/4,W/4,128], tap3 [B,H/8,W/8,128], NHWC fp16) and the head maps in front of the global pools (after [2] of each head:
+ *   head_maps [B,H/8,W/8,heads*256] f32).
+ * select_patches replaces extract_patches :36-57 with std_score :26-27 for an image already on the device: image [3,H,W] f32,
+ *   cut into non-overlapping patch_size x patch_size patches, row-major, partial ones dropped (n = (H / P) (W / P) <= 4096);
+ *   scores [n] f32 = mean over channels of the unbiased std; indices [K] int64 and patches [K,3,P,P] f32, K = min(num_patches, n),
+ *   in descending score order (equal scores: the lower index first).  An image smaller than a patch is NUNIF_HIP_EINVAL
+ *   (safe_pad :19-23 is a host step).  tv_score :30-33 is not carried: it reads an undefined name in the reference. */
+typedef struct nunif_cliqa nunif_cliqa;
+int nunif_hip_cliqa_create(const nunif_tensor_desc *tensors, int32_t n_tensors, int32_t kind, nunif_cliqa **handle);
+void nunif_hip_cliqa_destroy(nunif_cliqa *handle);
+int64_t nunif_hip_cliqa_workspace_bytes(nunif_cliqa *handle, int32_t B, int32_t H, int32_t W, int32_t group);
+int nunif_hip_cliqa_forward(nunif_cliqa *handle, const float *x, int32_t B, int32_t H, int32_t W, int32_t group, void *workspace,
+                            int64_t workspace_bytes, float *out0, float *out1, void *stream);
+int nunif_hip_cliqa_debug_taps(nunif_cliqa *handle, const float *x, int32_t B, int32_t H, int32_t W, int32_t group,
+                               void *workspace, int64_t workspace_bytes, float *out0, float *out1, void *tap1, void *tap2,
+                               void *tap3, float *head_maps, void *stream);
+int nunif_hip_cliqa_select_patches(const float *image, int32_t H, int32_t W, int32_t patch_size, int32_t num_patches,
+                                   float *scores, int64_t *indices, float *patches, void *stream);
+
 /* Test hooks (tests/ only): snapshot every stage's NHWC fp16 output during the next forward calls, then read
  * them back one by one (returns 1 past the last tap).  Names match oracle.swin_unet.unet_forward(taps=...). */
 int nunif_hip_swin_unet_debug_taps(nunif_swin_unet *handle, int32_t enable);

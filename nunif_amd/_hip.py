@@ -188,6 +188,12 @@ SIGNATURES = {
     "nunif_hip_yuv_to_tensor": (c_int32, [ctypes.POINTER(PixfmtPlanes)] + [c_int32] * 6 + [c_void_p, c_void_p, c_void_p]),
     "nunif_hip_tensor_to_yuv": (c_int32, [c_void_p] + [c_int32] * 5 + [ctypes.POINTER(PixfmtPlanes), c_void_p]),
     "nunif_hip_pixfmt_constants": (c_int32, [c_int32] * 4 + [ctypes.POINTER(c_float), ctypes.POINTER(c_float)]),
+    "nunif_hip_cliqa_create": (c_int32, [ctypes.POINTER(TensorDesc), c_int32, c_int32, ctypes.POINTER(c_void_p)]),
+    "nunif_hip_cliqa_destroy": (None, [c_void_p]),
+    "nunif_hip_cliqa_workspace_bytes": (c_int64, [c_void_p] + [c_int32] * 4),
+    "nunif_hip_cliqa_forward": (c_int32, [c_void_p, c_void_p] + [c_int32] * 4 + [c_void_p, c_int64] + [c_void_p] * 3),
+    "nunif_hip_cliqa_debug_taps": (c_int32, [c_void_p, c_void_p] + [c_int32] * 4 + [c_void_p, c_int64] + [c_void_p] * 7),
+    "nunif_hip_cliqa_select_patches": (c_int32, [c_void_p] + [c_int32] * 4 + [c_void_p] * 4),
     "nunif_hip_swin_unet_debug_taps":(c_int32, [c_void_p, c_int32]),
     "nunif_hip_swin_unet_get_tap": (c_int32, [c_void_p, c_int32, c_char_p, c_int32, c_void_p, c_int64,
                                               ctypes.POINTER(c_int64)]),

@@ -214,7 +214,7 @@ struct ConvArgs {
     const f16 *wstream;       // fragments in [k-step][n-tile] order, k = tap*Cin + ci, zero-padded by 16 KiB
     const float *bias;        // [N]
     int N, n_real;
-    int act; float slope;     // 0 none, 2 LeakyReLU
+    int act; float slope;     // 0 none, 2 LeakyReLU(slope), 3 ReLU
     f16 *out;                 // NHWC [B,Ho,Wo,n_real] (when out32 == NULL)
     float *out32;             // image head: planar fp32 [B,n_real,Ho,Wo]
     const float *add32; int addH, addW, add_crop;   // optional + add32[b][n][y+add_crop][x+add_crop]

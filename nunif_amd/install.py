@@ -115,11 +115,14 @@ _MODEL_MODULES = [("waifu2x.models", ["nunif_amd.waifu2x.models.swin_unet", "nun
                   ("iw3.models", ["nunif_amd.iw3.models"]),
                   # stlizer.light_outpaint_v1 (pass 4 of stlizer/multipass_pipeline.py:380 loads it through load_model); the
                   # reference package imports only torch and nunif.*: strict=True stays independent of PyAV
-                  ("stlizer.models", ["nunif_amd.stlizer.models"])]
+                  ("stlizer.models", ["nunif_amd.stlizer.models"]),
+                  # cliqa.jpeg_quality / grain_noise_level / scale_factor (python -m cliqa.filter_* build them through load_model and
+                  # reach them through forward and get_model_device only); cliqa.utils imports torchvision and has no PATCHES entry
+                  ("cliqa.models", ["nunif_amd.cliqa.models"])]
 # Reference model packages that install() merges only when the process has already loaded them (the CLI layer is loaded before
 # install(), nunif_amd/launch.py, and stlizer/multipass_pipeline.py:13 imports its models).  Importing them here would register
 # their names in the reference's registry for every process: install() is a drop-in, it adds no name the process did not have.
-_ONLY_IF_LOADED = ("stlizer.models",)
+_ONLY_IF_LOADED = ("stlizer.models", "cliqa.models")
 
 _state = None      # {"bindings": [(module, attr, original)], "registry": {name: original factory or _MISSING}}
 _MISSING = object()

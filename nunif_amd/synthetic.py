@@ -741,3 +741,40 @@ def light_outpaint_state_dict(seed):
         else:
             sd[key] = 0.1 * torch.randn(shape, generator=g)
     return sd
+
+
+def cliqa_state_dict(seed, kind):
+    """Seeded weights of a cliqa net (``kind``: ``jpeg_quality`` / ``grain_noise_level`` / ``scale_factor``) in the reference's key
+    layout (``cliqa/models``).  Convolutions get He gain so that activations stay O(1) through the seven convolutions in series;
+    BatchNorm gets non-trivial statistics (scale 0.6-1.4, shift, mean, variance 0.5-1.5) so that a wrong fold shows (with the
+    constructor's 1 / 0 / 0 / 1 the fold is the identity); every bias is non-zero.  The final 1 x 1 convs are scaled so that the
+    outputs land inside the ranges the ``predict_*`` functions clamp to (0-100, 0-50, 1-2), the subsampling logit around 0."""
+    from .cliqa.models._net import state_dict_shapes
+    g = torch.Generator().manual_seed(seed)
+    out_gain = {"quality_output": (2.0, 50.0), "subsampling_output": (0.3, 0.0), "noise_level_output": (1.0, 25.0),
+                "scale_factor_output": (0.04, 1.5)}
+    sd = {}
+    for key, shape in state_dict_shapes(kind).items():
+        mod, leaf = key.rsplit(".", 1)
+        head = key.split(".")[0]
+        is_bn = mod in ("features.1", "features.4") or mod.endswith((".conv.1", ".conv.4", "_output.1"))
+        if leaf == "num_batches_tracked":
+            sd[key] = torch.tensor(100, dtype=torch.long)
+        elif head in out_gain and mod.endswith(".4"):               # the final 1 x 1 conv
+            if leaf == "weight":
+                sd[key] = out_gain[head][0] * torch.randn(shape, generator=g) / math.sqrt(256.0)
+            else:
+                sd[key] = torch.tensor([out_gain[head][1]]) + 0.01 * torch.randn(shape, generator=g)
+        elif len(shape) == 4:
+            sd[key] = torch.randn(shape, generator=g) * math.sqrt(2.0 / (shape[1] * shape[2] * shape[3]))
+        elif leaf == "running_var":
+            sd[key] = 0.5 + torch.rand(shape, generator=g)
+        elif leaf == "running_mean":
+            sd[key] = 0.2 * torch.randn(shape, generator=g)
+        elif is_bn and leaf == "weight":
+            sd[key] = 0.6 + 0.8 * torch.rand(shape, generator=g)
+        elif is_bn:
+            sd[key] = 0.2 * torch.randn(shape, generator=g)
+        else:                                                       # a conv bias (ScaleFactor)
+            sd[key] = 0.05 * torch.randn(shape, generator=g)
+    return sd
