@@ -696,6 +696,39 @@ int nunif_hip_cliqa_debug_taps(nunif_cliqa *handle, const float *x, int32_t B, i
 int nunif_hip_cliqa_select_patches(const float *image, int32_t H, int32_t W, int32_t patch_size, int32_t num_patches,
                                    float *scores, int64_t *indices, float *patches, void *stream);
 
+/* iw3 --export / --export-disparity (iw3/utils.py:1366-1505 bind_export_single_frame_callback / bind_export_vda_frame_callback:
+ * per frame save_image :224-244 of the 8-bit RGB source and iw3/base_depth_model.py:197-210 save_normalized_depth of the 16-bit
+ * depth, both libpng on a host thread pool): a lossless PNG encoder on the device, so that a frame crosses to the host as its
+ * finished PNG bytes.  No weights: plain functions and a caller-owned workspace.  DESIGN.md ("PNG frame encoder") states the
+ * stream byte for byte.  header, max_bytes and workspace_bytes are host-only (nunif_amd/csrc/png_host.h), no GPU needed.
+ * form: 0 = RGB 8 from [B,3,H,W] f32 (clamp, x 255, round half even, as to_uint8); 1 = RGB 8 from [B,H,W,3] u8; 2 = grey 16 from
+ *   [B,1,H,W] f32 (clamp, fp32 0xffff * d, truncation, big-endian, as save_normalized_depth).
+ * header: the PNG signature, IHDR and one tEXt chunk per (key, value) pair (zero-terminated Latin-1; a key holds 1..79 bytes) into
+ *   out (host); returns the length or a negative status.
+ * max_bytes: an upper bound of the body (the IDAT chunks and IEND) of one frame for any input: per stripe of n filtered bytes
+ *   3 + 14 + 19 x 3 + 316 x 7 header bits, 15 n bits of tokens, 15 for the end of block and 3 for the stored block, filled to a
+ *   byte, 4 bytes LEN / NLEN and 12 of chunk; 2 bytes of zlib header, 4 of Adler-32, 12 of IEND.  -1 for a refused shape.
+ * workspace_bytes: the size of `workspace` for encode and debug_codes.  -1 for a refused shape.
+ * encode: B frames -> B bodies, body b at out + b * capacity (device), its length in out_len[b] (device i32).  One IDAT chunk per
+ *   stripe of stripe_rows rows (1..H; stripes are the unit of parallelism), each a dynamic-Huffman deflate block and an empty
+ *   stored block; adaptive row filter (smallest sum of absolute values, lowest type on a tie); matches at the pixel distance.
+ *   Five launches on `stream`, no host synchronisation, no atomics on global memory: the bytes depend on the input alone.  If
+ *   capacity is smaller than the body, out_len[b] = -1 and nothing of slot b is written; max_bytes is always enough.  workspace:
+ *   workspace_bytes() bytes of device memory, 256-byte aligned; calls that overlap need their own.  1 <= H, W <= 8192, B <= 16;
+ *   anything else is refused.
+ * debug_filtered (tests) runs the first launch alone: the filtered bytes [B][H][1 + W * bpp] u8 (device), the filter type first.
+ * debug_codes (tests) runs the first three launches: per stripe the histogram and the code lengths, [B][stripes][336] i32 each
+ *   (device): 286 literal / length symbols, 30 distance symbols, 19 code-length symbols, one word of padding. */
+int64_t nunif_hip_png_header(int32_t H, int32_t W, int32_t form, const char *const *text_keys, const char *const *text_values,
+                             int32_t n_text, uint8_t *out, int64_t capacity);
+int64_t nunif_hip_png_max_bytes(int32_t H, int32_t W, int32_t form, int32_t stripe_rows);
+int64_t nunif_hip_png_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t form, int32_t stripe_rows);
+int nunif_hip_png_encode(const void *src, int32_t form, int32_t B, int32_t H, int32_t W, int32_t stripe_rows, uint8_t *out,
+                         int64_t capacity, int32_t *out_len, void *workspace, void *stream);
+int nunif_hip_png_debug_filtered(const void *src, int32_t form, int32_t B, int32_t H, int32_t W, uint8_t *filtered, void *stream);
+int nunif_hip_png_debug_codes(const void *src, int32_t form, int32_t B, int32_t H, int32_t W, int32_t stripe_rows, int32_t *hist,
+                              int32_t *lengths, void *workspace, void *stream);
+
 /* Test hooks (tests/ only): snapshot every stage's NHWC fp16 output during the next forward calls, then read
  * them back one by one (returns 1 past the last tap).  Names match oracle.swin_unet.unet_forward(taps=...). */
 int nunif_hip_swin_unet_debug_taps(nunif_swin_unet *handle, int32_t enable);
