@@ -106,7 +106,10 @@ int nunif_hip_swin_unet_render(nunif_swin_unet *handle, const float *x, float *y
  *   tile_row_band     export (import_band = 0) / import (1) of output rows [row0, row0 + n_rows) of every tile of one tile row,
  *                     band = [w_blocks][3][n_rows][out_tile_size] f32 device — what neighbouring ranks exchange,
  *   stitch_rows       the single-pass stitch of output rows [y_row_begin, y_row_end) into a compact [3][rows][y_w] band.
- * Same tile grid, same tile store layout and the same stitch kernel as nunif_hip_swin_unet_render: bit-identical results. */
+ * Same tile grid, same tile store layout and the same stitch kernel as nunif_hip_swin_unet_render: bit-identical results.
+ * The tile store is defined only where a stitch of the frame reads it: of a tile of the last tile row / column, the pixels past the
+ * frame's edge are not written by a frame render (NUNIF_SWIN_SKIP_PAD), and a band exported by tile_row_band
+ * carries whatever the store held there.  No stitch reads those pixels on either side of an exchange. */
 int nunif_hip_swin_unet_render_tile_rows(nunif_swin_unet *handle, const float *x, int32_t x_h, int32_t x_w,
                                          int32_t tile_size, int32_t batch_size, int32_t row_begin, int32_t row_end,
                                          void *stream);
@@ -115,6 +118,19 @@ int nunif_hip_swin_unet_tile_row_band(nunif_swin_unet *handle, int32_t x_h, int3
                                       void *stream);
 int nunif_hip_swin_unet_stitch_rows(nunif_swin_unet *handle, float *y_band, int32_t x_h, int32_t x_w, int32_t tile_size,
                                     int32_t y_row_begin, int32_t y_row_end, void *stream);
+
+/* Which 6 x 6 windows of a tile a frame render has to run (host-only integer math; the frame entry points above use it to leave
+ * out windows that only feed replicate padding the stitch crops away).  Axis 0 = rows, 1 = columns.  Per block and axis the active
+ * windows are [0, n_win) plus, if `wrap`, the last window (a shifted block's wrap window, which holds tokens [0, 3)); a tile runs
+ * the product of its two axes.  grid: a swin_unet grid (offset 8 * scale); blocks_per_stage[5]: blocks of swin1 .. swin5;
+ * shifts / out: one entry per block in forward order (shift 0 or 3, swin_unet.py:30); to_image_fused: whether ToImage runs inside
+ * the last block's tail (1x / 2x nets) — either way one token becomes scale x scale pixels, so it does not change the extents. */
+typedef struct {
+    int32_t n_win[2];
+    int32_t wrap[2];
+} nunif_swin_block_extent;
+int nunif_hip_swin_unet_tile_extents(const nunif_tile_grid *grid, int32_t tile_index, const int32_t *blocks_per_stage,
+                                     const int32_t *shifts, int32_t to_image_fused, nunif_swin_block_extent *out);
 
 /* ------------------------------------------------------------------------------------------------------------
  * waifu2x CUNet.  Replaces waifu2x/models/cunet.py CUNet.forward :183-196 (UNet1 :52-67, UNet2 :99-121, SEBlock

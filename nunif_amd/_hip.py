@@ -35,6 +35,11 @@ class TileGrid(ctypes.Structure):
                 "input_tile_step": self.input_tile_step, "output_tile_step": self.output_tile_step}
 
 
+class SwinBlockExtent(ctypes.Structure):
+    """``nunif_swin_block_extent``: per axis (rows, columns) the leading windows of a block that run and whether its wrap window does."""
+    _fields_ = [("n_win", c_int32 * 2), ("wrap", c_int32 * 2)]
+
+
 class TensorDesc(ctypes.Structure):
     _fields_ = [("name", c_char_p), ("data", c_void_p), ("ndim", c_int32), ("shape", c_int64 * 4)]
 
@@ -74,6 +79,8 @@ SIGNATURES = {
     "nunif_hip_swin_unet_render_tile_rows": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "nunif_hip_swin_unet_tile_row_band": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p]),
     "nunif_hip_swin_unet_stitch_rows": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "nunif_hip_swin_unet_tile_extents": (c_int32, [ctypes.POINTER(TileGrid), c_int32, ctypes.POINTER(c_int32), ctypes.POINTER(c_int32),
+                                                   c_int32, ctypes.POINTER(SwinBlockExtent)]),
     "nunif_hip_swin_unet_v2_create": (c_int32, [ctypes.POINTER(TensorDesc), c_int32, c_int32, ctypes.POINTER(c_void_p)]),
     "nunif_hip_swin_unet_v2_destroy": (None, [c_void_p]),
     "nunif_hip_swin_unet_v2_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
@@ -254,6 +261,19 @@ def tile_grid(x_h, x_w, scale, offset, tile_size, blend_size):
     g = TileGrid()
     check(lib().nunif_hip_tile_grid_init(x_h, x_w, scale, offset, tile_size, blend_size or 0, ctypes.byref(g)))
     return g
+
+
+def swin_tile_extents(grid, tile_index, blocks_per_stage=(2, 2, 6, 2, 2), shifts=None, to_image_fused=True):
+    """Windows of tile ``tile_index`` that a swin_unet frame render runs: one ``(n_win_y, n_win_x, wrap_y, wrap_x)`` per block in
+    forward order (``nunif_hip_swin_unet_tile_extents``; host-only integer math)."""
+    n = sum(blocks_per_stage)
+    if shifts is None:
+        shifts = [3 if i % 2 else 0 for k in blocks_per_stage for i in range(k)]
+    per = (c_int32 * 5)(*blocks_per_stage)
+    sh = (c_int32 * n)(*shifts)
+    out = (SwinBlockExtent * n)()
+    check(lib().nunif_hip_swin_unet_tile_extents(ctypes.byref(grid), tile_index, per, sh, 1 if to_image_fused else 0, out))
+    return [(e.n_win[0], e.n_win[1], e.wrap[0], e.wrap[1]) for e in out]
 
 
 def blend_ramp(blend_size):

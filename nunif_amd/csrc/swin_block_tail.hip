@@ -315,6 +315,26 @@ int launch_winmap_build(int *pixmap, int B, int H, int W, int shift, hipStream_t
     return NUNIF_HIP_OK;
 }
 
+__global__ void winmap_list_build_kernel(int *__restrict__ pixmap, const unsigned *__restrict__ list, int n_list, int H, int W, int shift) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= 36 * n_list) return;
+    const int w = n / 36, t = n - 36 * w;
+    const unsigned e = list[w];
+    const int b = (int)(e >> 16), wy = (int)((e >> 8) & 255u), wx = (int)(e & 255u);
+    const int iy = t / 6, ix = t - 6 * iy;
+    int yy = wy * 6 + iy + shift, xx = wx * 6 + ix + shift;
+    if (yy >= H) yy -= H;
+    if (xx >= W) xx -= W;
+    pixmap[n] = (b * H + yy) * W + xx;
+}
+
+int launch_winmap_list_build(int *pixmap, const unsigned *win_list, int n_list, int H, int W, int shift, hipStream_t s) {
+    NUNIF_REQUIRE(pixmap && win_list && n_list > 0 && H % 6 == 0 && W % 6 == 0 && 36L * n_list < (1L << 31), "winmap: list of %d windows", n_list);
+    winmap_list_build_kernel<<<(unsigned)((36L * n_list + 255) / 256), 256, 0, s>>>(pixmap, win_list, n_list, H, W, shift);
+    NUNIF_LAUNCH_CHECK();
+    return NUNIF_HIP_OK;
+}
+
 constexpr int proj_mlp_stream_frags_c(int C) { return 2 * (C / 32) * (C / 32) + (2 * C / 32) * (2 * (C / 32) + C / 16); }
 
 int proj_mlp_stream_frags(int C) {
@@ -336,7 +356,7 @@ int launch_proj_mlp(const f16 *att, f16 *x, const f16 *wstream, const float *bp,
     WinMap wm;
     memset(&wm, 0, sizeof(wm));
     if (wmap) wm = *wmap;
-    NUNIF_REQUIRE(!wm.on || (wm.pixmap && wm.H % 6 == 0 && wm.W % 6 == 0 && M % ((long)wm.H * wm.W) == 0 && 96L * M < (1L << 31)),
+    NUNIF_REQUIRE(!wm.on || (wm.pixmap && wm.H % 6 == 0 && wm.W % 6 == 0 && M % 36 == 0 && 96L * M < (1L << 31)),
                   "proj_mlp: window map geometry");        // 16 M + 2880 (M / 36) = 96 M att elements are indexed in 32 bits (swin_unet.cpp
                                                            // hands larger launches the pixel-major map)
     constexpr int MF = 2, WAVES = 8;

@@ -162,8 +162,11 @@ struct TailToImage { const f16 *w; const float *bias; float *out; int H, W, ps, 
 // WinMap (C = 96 resident kernel only): tokens are walked in WINDOW order (n = window * 36 + t, the shifted 6x6 windows of
 // launch_qkv_attn_r) and att is the window-major map that kernel writes with window_major = 1; x rows / image pixels are
 // addressed through the same window -> pixel map.  The per-token arithmetic is unchanged (bit-identical results).
-struct WinMap { int on, H, W, shift; const int *pixmap; };     // pixmap: token -> pixel table of launch_winmap_build (B H W ints)
+struct WinMap { int on, H, W, shift; const int *pixmap; };     // pixmap: token -> pixel table of launch_winmap_build (B H W ints),
+                                                               // or of a window list (36 ints per listed window, M = 36 n_list)
 int launch_winmap_build(int *pixmap, int B, int H, int W, int shift, hipStream_t s);
+// the same table for a window LIST (launch_qkv_attn_r's win_list, device memory): pixmap[36 i + t] = pixel of token t of window i
+int launch_winmap_list_build(int *pixmap, const unsigned *win_list, int n_list, int H, int W, int shift, hipStream_t s);
 int launch_proj_mlp(const f16 *att, f16 *x, const f16 *wstream, const float *bp, const float *b0, const float *b3,
                     long M, int C, hipStream_t s, const TailToImage *to_image = nullptr, int rev = 0,
                     const WinMap *wm = nullptr, int gelu32 = 0);      // gelu32: the fp32-polynomial GELU (swin_gelu.h gelu8t)
@@ -193,7 +196,10 @@ int launch_proj_mlp_ws(const f16 *att, f16 *x, const f16 *wws, const float *bp, 
 // 512-byte run; launch_proj_mlp's WinMap reads it back in the same order
 constexpr int kQkvBiasFloatsPerHead = 36 * 52;
 int launch_qkv_attn_r(const f16 *x, f16 *att, const f16 *wres, const float *bqkv, const float *btab32,
-                      int B, int H, int W, int C, int heads, int shift, hipStream_t s, int rev = 0, int window_major = 0);
+                      int B, int H, int W, int C, int heads, int shift, hipStream_t s, int rev = 0, int window_major = 0,
+                      const unsigned *win_list = nullptr, int n_list = 0);
+// win_list (window_major only): run the n_list windows it names, entry = batch << 16 | window row << 8 | window column, instead of
+// all B (H / 6) (W / 6); window i of the list lands at slot i of the window-major att map (a compact map of 36 n_list tokens)
 
 // ---- (shifted) 6x6 window attention on a fused qkv map ----------------------------------------------------------
 // qkv: [B,H,W,3C] fp16 (q | k | v, each heads x hd), out: [B,H,W,C]; bias: [heads][36][48] fp32 with the

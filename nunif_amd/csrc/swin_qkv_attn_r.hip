@@ -40,6 +40,7 @@ struct QkvAttnRArgs {
     const float *btab32;     // [heads][36][52] fp32: log2e * bias, key columns in win_token order (col 32 + 4 g = key 32 + g), 48..51 unused
     int B, H, W, shift, n_windows;
     int rev;                 // 1: walk the windows from the last to the first (snake order, see launch_qkv_attn_r)
+    const unsigned *wlist;   // NULL: all B (H / 6) (W / 6) windows; else n_windows entries (batch << 16 | window row << 8 | window column)
 };
 
 // o * inv -> fp16, the product rounded ONCE: (f16) fma(o, inv, 0) is v_fma_mixlo / mixhi_f16 (fp32 fma, converted on the way out) —
@@ -182,10 +183,23 @@ qkv_attn_r_kernel(QkvAttnRArgs a) {
             for (int ks = 0; ks < KS; ++ks) xf[mt][ks] = *reinterpret_cast<const f16x8 *>(xb + vo[mt] + 64 * ks);
         }
     };
-    auto decode = [&](int &wb, int &wy, int &wx, bool &special) {          // snake order: digit-wise complement of the index
-        wb = a.rev ? a.B - 1 - cb : cb;
-        wy = a.rev ? nwy - 1 - cy : cy;
-        wx = a.rev ? nwx - 1 - cx : cx;
+    // slot of work index wi in a window list (snake order: the list walked backwards); clamped, a wave decodes one index past its last
+    auto list_slot = [&](int wi) {
+        const int i = wi < a.n_windows ? wi : a.n_windows - 1;
+        return a.rev ? a.n_windows - 1 - i : i;
+    };
+    int lslot = 0;           // slot of the decoded window in the list = its index in the compact window-major att map
+    auto decode = [&](int wi, int &wb, int &wy, int &wx, bool &special) {  // snake order: digit-wise complement of the index
+        if (a.wlist) {
+            // listed windows (frame renders that leave out padding-only windows): one wave-uniform table read replaces the counters
+            lslot = list_slot(wi);
+            const unsigned e = a.wlist[lslot];
+            wb = (int)(e >> 16); wy = (int)((e >> 8) & 255u); wx = (int)(e & 255u);
+        } else {
+            wb = a.rev ? a.B - 1 - cb : cb;
+            wy = a.rev ? nwy - 1 - cy : cy;
+            wx = a.rev ? nwx - 1 - cx : cx;
+        }
         special = a.shift > 0 && (wy == nwy - 1 || wx == nwx - 1);
     };
     auto advance = [&]() {
@@ -214,12 +228,14 @@ qkv_attn_r_kernel(QkvAttnRArgs a) {
     // (The window loop and the head loop stay wrapped in lambdas called once: written inline, hipcc allocates registers differently.)
     auto run_windows = [&]() {
     int wi = w0;
-    decode(wb, wy, wx, special);
-    auto step = [&]() { advance(); wi += wstride; decode(wb, wy, wx, special); };      // on to the wave's next window
+    decode(wi, wb, wy, wx, special);
+    auto step = [&]() { if (!a.wlist) advance(); wi += wstride; decode(wi, wb, wy, wx, special); };  // on to the wave's next window
     if (wi < a.n_windows) load_x(wb, wy, wx, special, xf, vo);
 #pragma unroll 1
     while (wi < a.n_windows) {
-        const int wq = (wb * nwy + wy) * nwx + wx;                         // index of this window in the window-major att map
+        // index of this window in the window-major att map (a listed window: its slot in the list, the map is compact)
+        // (read here, at the top of the trip: the early x request inside the last head decodes the NEXT window)
+        const int wq = a.wlist ? lslot : (wb * nwy + wy) * nwx + wx;
         char *ab = reinterpret_cast<char *>(a.att) + (WM ? (long)wq * (HEADS * 36 * HD * 2) : (long)wb * img_bytes);
         // window-major map: a wave-uniform byte offset (the launcher keeps the map below 4 GB) + a lane constant per tile
         // (in unsigned arithmetic: past 2 GB of map the product no longer fits a signed int; the launcher keeps it below 4 GB)
@@ -403,19 +419,23 @@ static int launch_r(const QkvAttnRArgs &a, int grid, hipStream_t s) {
 }
 
 int launch_qkv_attn_r(const f16 *x, f16 *att, const f16 *wres, const float *bqkv, const float *btab32,
-                      int B, int H, int W, int C, int heads, int shift, hipStream_t s, int rev, int window_major) {
+                      int B, int H, int W, int C, int heads, int shift, hipStream_t s, int rev, int window_major,
+                      const unsigned *win_list, int n_list) {
     NUNIF_REQUIRE(H % 6 == 0 && W % 6 == 0, "qkv_attn: %dx%d not a multiple of the 6x6 window", H, W);
     NUNIF_REQUIRE(heads == 6 && (C == 96 || C == 192), "qkv_attn: C=%d heads=%d unsupported", C, heads);
     if (H <= 6) shift = 0;                 // torchvision disables the shift when the window covers the map
     QkvAttnRArgs a;
     a.x = x; a.att = att; a.wres = wres; a.bqkv = bqkv; a.btab32 = btab32;
     a.B = B; a.H = H; a.W = W; a.shift = shift;
-    a.n_windows = B * (H / 6) * (W / 6);
+    NUNIF_REQUIRE(!win_list || (window_major && n_list > 0 && n_list <= B * (H / 6) * (W / 6) && B < 65536 && H / 6 < 256 && W / 6 < 256),
+                  "qkv_attn: a window list needs the window-major map and at most 65535 x 255 x 255 windows");
+    a.n_windows = win_list ? n_list : B * (H / 6) * (W / 6);
+    a.wlist = win_list;
     a.rev = rev;            // snake order between consecutive kernels (swin_unet.cpp next_dir)
     NUNIF_REQUIRE(!window_major || C == 96, "qkv_attn: the window-major att map exists for C = 96 only");
     NUNIF_REQUIRE(!window_major || (long)a.n_windows * (6 * 36 * 16 * 2) < (1L << 32),
                   "qkv_attn: the window-major att map of %d windows does not fit 32-bit byte offsets", a.n_windows);
-    const double tok = (double)B * H * W;
+    const double tok = 36.0 * a.n_windows;           // the work issued: a listed launch counts its own windows
     // C = 96: 16 waves per workgroup (120 registers, no register prefetch: four waves per SIMD hide the x loads; 8 waves with
     // prefetch measured 10 % slower, 12 waves in between); C = 192: 8 waves
     const int kWavesR = C == 96 ? 16 : 8;

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <list>
 #include <string>
 #include <vector>
 
@@ -45,10 +46,92 @@ struct Block {
     float *b96_btab = nullptr;
 };
 
+// Windows of one C = 96 block that a frame render runs (pad skipping), for one tile minibatch: `list` holds one
+// entry per active window, (tile in the minibatch << 16 | window row << 8 | window column), tile-major; the attention kernel
+// writes window i of the list at slot i of the window-major att map and the tail walks `pixmap` (token 36 i + t -> pixel).
+struct SkipBlock {
+    unsigned *list = nullptr;
+    int *pixmap = nullptr;
+    int n_windows = 0;
+};
+
+// One plan per (grid, tile minibatch).  Everything of a plan lives in ONE device allocation: the lists of its blocks (uploaded
+// once, `host` keeps the source alive for the asynchronous copy) and behind them the token tables, which a kernel builds from
+// the lists on the stream that first uses the plan (launch_winmap_list_build) — `ready` orders any other stream behind that.
+struct SkipPlan {
+    nunif_tile_grid grid = {};
+    int tile_begin = 0, B = 0;
+    std::vector<SkipBlock> stage[5];      // empty where the stage runs whole
+    void *dev = nullptr;
+    size_t bytes = 0;
+    std::vector<unsigned> host;
+    hipStream_t built_on = nullptr;
+    hipEvent_t ready = nullptr;
+};
+
+// One axis of one block, walking BACKWARDS: `e` = tokens [0, e) of the block's OUTPUT that a consumer needs (e >= 1).  Fills the
+// windows that must run and returns the prefix of the block's INPUT that those windows read as unmasked keys.
+int block_extent_back(int e, int S, int shift, int32_t *n_win, int32_t *wrap) {
+    const int nw = S / 6;
+    if (S <= 6) shift = 0;                 // torchvision disables the shift when one window covers the map
+    if (shift == 0) {
+        *n_win = std::min(nw, (e + 5) / 6);
+        *wrap = 0;
+        return std::min(S, 6 * *n_win);
+    }
+    // shifted by 3: window w < nw - 1 holds tokens [6 w + 3, 6 w + 9), the wrap window (nw - 1) holds [S - 3, S) and [0, 3) in two
+    // mask regions.  Tokens [0, 3) are always needed, so the wrap window always runs; its far half enters as masked keys only.
+    *n_win = std::min(nw - 1, (std::max(e - 3, 0) + 5) / 6);
+    *wrap = 1;
+    return *n_win == nw - 1 ? S : 3 + 6 * *n_win;
+}
+
 }  // namespace
 }  // namespace nunif
 
 using namespace nunif;
+
+// Pure integer host function (declared in nunif_hip.h): see the header.  Everything is separable per axis — the stitch reads a
+// rectangle of a tile, a token needs the rectangle of its window, PatchDown / PatchUp are 2 x 2 per pixel — so each axis is walked
+// on its own from the stitch back to the stem.
+extern "C" int nunif_hip_swin_unet_tile_extents(const nunif_tile_grid *g, int32_t tile_index, const int32_t *blocks_per_stage,
+                                                const int32_t *shifts, int32_t to_image_fused, nunif_swin_block_extent *out) {
+    (void)to_image_fused;      // fused or not, ToImage maps one token to scale x scale pixels: the extents are the same
+    NUNIF_REQUIRE(g && blocks_per_stage && shifts && out, "tile_extents: NULL argument");
+    NUNIF_REQUIRE(tile_index >= 0 && tile_index < g->h_blocks * g->w_blocks, "tile_extents: tile %d outside the grid", tile_index);
+    const int S = g->tile_size - 16;
+    NUNIF_REQUIRE(S > 0 && S % 24 == 0 && g->scale > 0 && g->out_tile_size == S * g->scale,
+                  "tile_extents: the grid is not a swin_unet grid (tile %d, output tile %d)", g->tile_size, g->out_tile_size);
+    int first[6] = {0};
+    for (int st = 0; st < 5; ++st) {
+        NUNIF_REQUIRE(blocks_per_stage[st] >= 0, "tile_extents: negative block count");
+        first[st + 1] = first[st] + blocks_per_stage[st];
+    }
+    const int size[5] = {S, S / 2, S / 4, S / 2, S};
+    const int ti[2] = {tile_index / g->w_blocks, tile_index % g->w_blocks};
+    const int y_len[2] = {g->y_h, g->y_w};
+    for (int ax = 0; ax < 2; ++ax) {
+        // stitch_kernel (stitch.hip) reads pixel t = Y - output_tile_step * i of tile i for every output row / column Y of the frame
+        // with 0 <= t < out_tile_size, blend margins included: the prefix [0, min(out_tile_size, y_len - output_tile_step * i))
+        const int n_px = std::min(g->out_tile_size, y_len[ax] - g->output_tile_step * ti[ax]);
+        auto stage_back = [&](int st, int e) {         // e: needed prefix of the stage's output -> of its input
+            for (int i = blocks_per_stage[st] - 1; i >= 0; --i) {
+                nunif_swin_block_extent &o = out[first[st] + i];
+                if (e <= 0) { o.n_win[ax] = 0; o.wrap[ax] = 0; continue; }
+                e = block_extent_back(e, size[st], shifts[first[st] + i], &o.n_win[ax], &o.wrap[ax]);
+            }
+            return std::max(e, 0);
+        };
+        const int e5 = n_px <= 0 ? 0 : std::min(S, (n_px + g->scale - 1) / g->scale);    // to_image: one token -> scale x scale pixels
+        const int top_in = stage_back(4, e5);                          // swin5 reads PatchUp(swin4) + the swin1 skip
+        const int e4_in = stage_back(3, (top_in + 1) / 2);             // PatchUp: token i of the fine map reads token i / 2
+        const int e3_in = stage_back(2, (e4_in + 1) / 2);
+        // a skip connection takes the larger of its two consumers; PatchDown: token j reads tokens 2 j and 2 j + 1
+        const int e2_in = stage_back(1, std::min(size[1], std::max(2 * e3_in, e4_in)));
+        (void)stage_back(0, std::min(size[0], std::max(2 * e2_in, top_in)));
+    }
+    return NUNIF_HIP_OK;
+}
 
 struct nunif_swin_unet : DeviceOwner {       // owns every device allocation made at create time
     int scale_factor = 2;
@@ -71,6 +154,22 @@ struct nunif_swin_unet : DeviceOwner {       // owns every device allocation mad
     // token -> pixel tables of the window-major C = 96 tail (launch_winmap_build), one per shift, for the geometry last seen
     DeviceBuf winmap[2];
     int winmap_B = 0, winmap_S = 0;
+    // pad skipping of the frame entry points: one plan (window lists + token tables) per grid and tile
+    // minibatch, of every grid the handle has rendered.  Most recently used first, so a handle that alternates between frame
+    // sizes or minibatches finds its plans again; evicted from the back beyond kMaxPlans / kMaxPlanBytes.
+    std::list<SkipPlan> plans;
+    size_t plan_bytes = 0;
+    const SkipPlan *plan = nullptr;   // the plan of the forward_impl call under way (NULL: whole tiles)
+    void drop_plan(std::list<SkipPlan>::iterator it) {
+        if (it->ready) (void)hipEventDestroy(it->ready);
+        (void)hipFree(it->dev);           // (synchronises the device: no launch that reads the plan is still in flight)
+        plan_bytes -= it->bytes;
+        plans.erase(it);
+    }
+    void clear_plans() {
+        while (!plans.empty()) drop_plan(plans.begin());
+        plan = nullptr;
+    }
     int device = 0;
     // debug taps (tests only): when on, every stage's fp16 output is snapshotted device-side
     struct Tap { std::string name; void *dev; size_t bytes; };
@@ -313,7 +412,7 @@ static int next_dir(nunif_swin_unet *h) {
 }
 
 int run_stage(nunif_swin_unet *h, std::vector<Block> &blocks, f16 *x, int B, int S, int dim, hipStream_t s,
-              const char *name, const TailToImage *to_image = nullptr) {
+              const char *name, const TailToImage *to_image = nullptr, const std::vector<SkipBlock> *skip = nullptr) {
     f16 *qkv = (f16 *)h->qkv.p, *att = (f16 *)h->att.p;
     const size_t tok = (size_t)B * S * S;
     int rc;
@@ -360,8 +459,10 @@ int run_stage(nunif_swin_unet *h, std::vector<Block> &blocks, f16 *x, int B, int
         // window order); debug taps want the pixel-major map the oracle has
         // (the tail indexes the window-major map in 32 bits: 96 tok elements; larger launches take the pixel-major map)
         const bool att_wm = dim == 96 && h->att_wm && !h->taps_on && 96L * (long)tok < (1L << 31);
+        // frame renders: only the windows the stitch depends on (skip_plan); att is then compact, slot i = window i of the list
+        const SkipBlock *sk = skip && att_wm && i < skip->size() && (*skip)[i].list ? &(*skip)[i] : nullptr;
         if ((rc = launch_qkv_attn_r(x, att, bl.qkv_res, bl.qkv_rbias, bl.attn_btab32, B, S, S, dim, h->heads, shift, s, next_dir(h),
-                                    att_wm ? 1 : 0)))
+                                    att_wm ? 1 : 0, sk ? sk->list : nullptr, sk ? sk->n_windows : 0)))
             return rc;
         if ((rc = tap(h, tn + ".attn", att, tok * dim * 2, s))) return rc;
         // x = y + mlp(y), y = x + proj(attn): three GEMMs chained through registers, one read + one write of x
@@ -373,7 +474,9 @@ int run_stage(nunif_swin_unet *h, std::vector<Block> &blocks, f16 *x, int B, int
         } else {
             const int eff_shift = S <= 6 ? 0 : shift;
             WinMap wmap = {att_wm ? 1 : 0, S, S, eff_shift, nullptr};
-            if (att_wm) {
+            if (sk) {
+                wmap.pixmap = sk->pixmap;
+            } else if (att_wm) {
                 if (h->winmap_S != S || B > h->winmap_B) {
                     // (re)build both tables on this stream: every launch that reads them is ordered behind it.  The table of a
                     // larger batch contains the smaller one's as its prefix (token n -> batch n / (36 windows per image))
@@ -385,7 +488,7 @@ int run_stage(nunif_swin_unet *h, std::vector<Block> &blocks, f16 *x, int B, int
                 }
                 wmap.pixmap = (const int *)h->winmap[eff_shift ? 1 : 0].p;
             }
-            if ((rc = launch_proj_mlp(att, x, bl.tail_stream, bl.proj.bias, bl.mlp0.bias, bl.mlp3.bias, (long)tok, dim, s,
+            if ((rc = launch_proj_mlp(att, x, bl.tail_stream, bl.proj.bias, bl.mlp0.bias, bl.mlp3.bias, sk ? 36L * sk->n_windows : (long)tok, dim, s,
                                       last ? to_image : nullptr, next_dir(h), &wmap, h->gelu32)))
                 return rc;
         }
@@ -412,13 +515,108 @@ int ensure_workspace(nunif_swin_unet *h, int B, int T) {
     return NUNIF_HIP_OK;
 }
 
+// The window lists of tile minibatch [t0, t0 + B) of grid g (frame entry points only).  What a tile runs depends on the grid and
+// the tile's index alone — never on the minibatch or the stream — so any split of a frame into minibatches computes the same bits.
+//
+// INVARIANT the skipping rests on: the stem, PatchDown, PatchUp and the un-fused to_image always process WHOLE tiles, so every
+// activation map is fully rewritten from the current frame before a block reads it; a token a block skips keeps that block's
+// input (finite, a function of the current frame).  The far half of a shifted block's wrap window is read as masked keys whose
+// softmax weight is an exact fp16 zero, and 0 x finite = 0 where 0 x a stale Inf / NaN would not be.  Only the C = 96 blocks skip
+// (their tail walks the same compact list through `pixmap`, and the compact att map is written in full before it is read);
+// C = 192 blocks and the generic block path run whole tiles, which is a superset of what their consumers need.
+constexpr size_t kMaxPlans = 1024, kMaxPlanBytes = (size_t)1 << 30;
+
+int skip_plan(nunif_swin_unet *h, const nunif_tile_grid *g, int t0, int B, hipStream_t s, const SkipPlan **out) {
+    *out = nullptr;
+    const int S = g->tile_size - 16, nw = S / 6;
+    if (!h->att_wm || h->taps_on || h->block96 || S <= 6 || nw >= 256 || B >= 65536 || 96L * B * S * S >= (1L << 31) ||
+        g->out_tile_size != S * g->scale)
+        return NUNIF_HIP_OK;
+    for (auto it = h->plans.begin(); it != h->plans.end(); ++it)
+        if (it->tile_begin == t0 && it->B == B && memcmp(g, &it->grid, sizeof(*g)) == 0) {
+            h->plans.splice(h->plans.begin(), h->plans, it);
+            if (it->dev && it->built_on != s) NUNIF_HIP_CHECK(hipStreamWaitEvent(s, it->ready, 0));
+            *out = &*it;
+            return NUNIF_HIP_OK;
+        }
+    int32_t per_stage[5], n_blocks = 0;
+    std::vector<int32_t> shifts;
+    for (int st = 0; st < 5; ++st) {
+        per_stage[st] = (int32_t)h->swin[st].size();
+        for (int i = 0; i < per_stage[st]; ++i) shifts.push_back(i % 2 == 1 ? 3 : 0);      // swin_unet.py:30
+        n_blocks += per_stage[st];
+    }
+    std::vector<std::vector<nunif_swin_block_extent>> ext(B, std::vector<nunif_swin_block_extent>(n_blocks));
+    int rc;
+    for (int b = 0; b < B; ++b)
+        if ((rc = nunif_hip_swin_unet_tile_extents(g, t0 + b, per_stage, shifts.data(), 0, ext[b].data()))) return rc;
+    h->plans.emplace_front();
+    SkipPlan &plan = h->plans.front();
+    plan.grid = *g; plan.tile_begin = t0; plan.B = B; plan.built_on = s;
+    struct Piece { int st, i, shift; size_t first, n; };
+    std::vector<Piece> pieces;
+    int first = 0;
+    for (int st = 0; st < 5; first += per_stage[st], ++st) {
+        const int dim = st == 0 ? h->C : (st == 4 ? h->top_dim : 2 * h->C);
+        bool fast = (st == 0 || st == 4) && dim == 96;      // level 1 of the 1x / 2x nets and swin1 of the 4x net
+        for (const Block &bl : h->swin[st]) fast = fast && bl.fast;
+        if (!fast) continue;
+        plan.stage[st].resize(per_stage[st]);
+        for (int i = 0; i < per_stage[st]; ++i) {
+            const size_t at = plan.host.size();
+            for (int b = 0; b < B; ++b) {
+                const nunif_swin_block_extent &e = ext[b][first + i];
+                auto active = [&](int ax, int w) { return w < e.n_win[ax] || (e.wrap[ax] && w == nw - 1); };
+                for (int wy = 0; wy < nw; ++wy) {
+                    if (!active(0, wy)) continue;
+                    for (int wx = 0; wx < nw; ++wx)
+                        if (active(1, wx)) plan.host.push_back((unsigned)b << 16 | (unsigned)wy << 8 | (unsigned)wx);
+                }
+            }
+            const size_t n = plan.host.size() - at;
+            if (n == (size_t)B * nw * nw || n == 0) { plan.host.resize(at); continue; }   // nothing to leave out: the whole-tile path
+            pieces.push_back({st, i, shifts[first + i], at, n});
+        }
+    }
+    if (pieces.empty()) { *out = &plan; return NUNIF_HIP_OK; }       // (cached all the same: the next frame finds it)
+    // layout: all lists | token tables (36 ints per listed window), the tables 256-byte aligned
+    const size_t list_bytes = (plan.host.size() * 4 + 255) / 256 * 256;
+    plan.bytes = list_bytes + plan.host.size() * 36 * 4;
+    auto fail = [&](int code) { h->drop_plan(h->plans.begin()); return code; };
+    if (hipMalloc(&plan.dev, plan.bytes) != hipSuccess) {
+        set_error("hipMalloc(%zu) of the window lists failed", plan.bytes);
+        plan.bytes = 0;
+        return fail(NUNIF_HIP_ENOMEM);
+    }
+    h->plan_bytes += plan.bytes;
+    if (hipMemcpyAsync(plan.dev, plan.host.data(), plan.host.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipEventCreateWithFlags(&plan.ready, hipEventDisableTiming) != hipSuccess) {
+        set_error("upload of the window lists failed");
+        return fail(NUNIF_HIP_EHIP);
+    }
+    for (const Piece &pc : pieces) {
+        SkipBlock &sb = plan.stage[pc.st][pc.i];
+        sb.list = (unsigned *)plan.dev + pc.first;
+        sb.pixmap = (int *)((char *)plan.dev + list_bytes) + pc.first * 36;
+        sb.n_windows = (int)pc.n;
+        if ((rc = launch_winmap_list_build(sb.pixmap, sb.list, sb.n_windows, S, S, pc.shift, s))) return fail(rc);
+    }
+    if (hipEventRecord(plan.ready, s) != hipSuccess) { set_error("hipEventRecord failed"); return fail(NUNIF_HIP_EHIP); }
+    while (h->plans.size() > kMaxPlans || (h->plan_bytes > kMaxPlanBytes && h->plans.size() > 1)) h->drop_plan(std::prev(h->plans.end()));
+    *out = &plan;
+    return NUNIF_HIP_OK;
+}
+
 // x: tile mode [B,3,T,T] or (frame != NULL) the frame + grid; z: [B,3,S*s,S*s]
 int forward_impl(nunif_swin_unet *h, const float *x, const float *frame, const nunif_tile_grid *grid,
-                 int tile_begin, float *z, int B, int T, hipStream_t s) {
+                 int tile_begin, float *z, int B, int T, hipStream_t s, bool skip_pad = false) {
     const int S = T - 16, C = h->C;
     NUNIF_REQUIRE(T > 16 && S % 12 == 0 && S % 16 == 0, "tile_size %d is not valid for swin_unet", T);
     int rc;
     if ((rc = ensure_workspace(h, B, T))) return rc;
+    h->plan = nullptr;
+    if (frame && skip_pad && (rc = skip_plan(h, grid, tile_begin, B, s, &h->plan))) return rc;
+    auto skip_of = [&](int st) { return h->plan && !h->plan->stage[st].empty() ? &h->plan->stage[st] : nullptr; };
     f16 *s1 = (f16 *)h->s1.p, *f1 = (f16 *)h->f1.p, *f2 = (f16 *)h->f2.p, *f3 = (f16 *)h->f3.p;
 
     if (h->stemf_w2 && stem_fused_supported(h->C1, (int)C)) {
@@ -453,7 +651,7 @@ int forward_impl(nunif_swin_unet *h, const float *x, const float *frame, const n
         return rc;
 stem_done:
     if ((rc = tap(h, "stem", f1, (size_t)B * S * S * C * 2, s))) return rc;
-    if ((rc = run_stage(h, h->swin[0], f1, B, S, C, s, "swin1"))) return rc;                          // swin1 -> x3
+    if ((rc = run_stage(h, h->swin[0], f1, B, S, C, s, "swin1", nullptr, skip_of(0)))) return rc;                          // swin1 -> x3
     if ((rc = run_patchdown(h->down1, f1, B, S / 2, S / 2, C, 0, f2, s, "gemm_down1", next_dir(h)))) return rc;
     if ((rc = tap(h, "down1", f2, (size_t)B * (S / 2) * (S / 2) * 2 * C * 2, s))) return rc;
     if ((rc = run_stage(h, h->swin[1], f2, B, S / 2, 2 * C, s, "swin2"))) return rc;                  // swin2 -> x4
@@ -485,9 +683,9 @@ stem_done:
         TailToImage ti;
         ti.w = h->to_image_chained; ti.bias = h->to_image.bias; ti.out = z; ti.H = S; ti.W = S; ti.ps = h->scale_factor;
         ti.n_real = h->to_image.n_real;
-        return run_stage(h, h->swin[4], top, B, S, h->top_dim, s, "swin5", &ti);
+        return run_stage(h, h->swin[4], top, B, S, h->top_dim, s, "swin5", &ti, skip_of(4));
     }
-    if ((rc = run_stage(h, h->swin[4], top, B, S, h->top_dim, s, "swin5"))) return rc;                // swin5
+    if ((rc = run_stage(h, h->swin[4], top, B, S, h->top_dim, s, "swin5", nullptr, skip_of(4)))) return rc;                // swin5
     if (h->scale_factor == 8) {
         f16 *pre = (f16 *)h->att.p;                 // the attention scratch map is free again: [B,S,S,192]
         if ((rc = run_gemm(h->to_image_pre, top, B, S, S, h->top_dim, S, S, 1, 0, 0, 1, 0, 2, 0.2f, nullptr, pre, 192, 1, s,
@@ -658,6 +856,7 @@ extern "C" int nunif_hip_swin_unet_get_tap(nunif_swin_unet *h, int32_t index, ch
 extern "C" void nunif_hip_swin_unet_destroy(nunif_swin_unet *h) {
     if (!h) return;
     h->clear_taps();
+    h->clear_plans();
     h->free_all();
     for (DeviceBuf *b : {&h->s1, &h->f1, &h->f2, &h->f3, &h->g1, &h->qkv, &h->att, &h->hid, &h->tile_out, &h->winmap[0], &h->winmap[1]}) b->release();
     delete h;
@@ -667,6 +866,13 @@ extern "C" int nunif_hip_swin_unet_forward(nunif_swin_unet *h, const float *x, f
                                            int32_t tile_size, void *stream) {
     NUNIF_REQUIRE(h && x && z && batch > 0, "swin_unet_forward: bad argument");
     return forward_impl(h, x, nullptr, nullptr, 0, z, batch, tile_size, (hipStream_t)stream);
+}
+
+// NUNIF_SWIN_SKIP_PAD=0: the frame entry points push whole tiles through every block, as the tile entry always does (A/B runs);
+// read at call time
+static bool skip_pad_enabled() {
+    const char *v = getenv("NUNIF_SWIN_SKIP_PAD");
+    return !(v && atoi(v) == 0);
 }
 
 extern "C" int nunif_hip_swin_unet_render(nunif_swin_unet *h, const float *x, float *y, int32_t x_h, int32_t x_w,
@@ -684,9 +890,10 @@ extern "C" int nunif_hip_swin_unet_render(nunif_swin_unet *h, const float *x, fl
     if ((rc = h->tile_out.ensure((size_t)n_tiles * 3 * To * To * sizeof(float)))) return rc;
     float *tile_out = (float *)h->tile_out.p;
     hipStream_t st = (hipStream_t)stream;
+    const bool skip_pad = skip_pad_enabled();
     for (int t0 = 0; t0 < n_tiles; t0 += batch_size) {
         const int nb = std::min(batch_size, n_tiles - t0);
-        if ((rc = forward_impl(h, nullptr, x, &g, t0, tile_out + (size_t)t0 * 3 * To * To, nb, tile_size, st)))
+        if ((rc = forward_impl(h, nullptr, x, &g, t0, tile_out + (size_t)t0 * 3 * To * To, nb, tile_size, st, skip_pad)))
             return rc;
     }
     return launch_stitch(tile_out, y, &g, 3, st);
@@ -717,9 +924,10 @@ extern "C" int nunif_hip_swin_unet_render_tile_rows(nunif_swin_unet *h, const fl
     const size_t To = g.out_tile_size;
     float *tile_out = (float *)h->tile_out.p;
     const int t_end = row_end * g.w_blocks;
+    const bool skip_pad = skip_pad_enabled();
     for (int t0 = row_begin * g.w_blocks; t0 < t_end; t0 += batch_size) {
         const int nb = std::min(batch_size, t_end - t0);
-        if ((rc = forward_impl(h, nullptr, x, &g, t0, tile_out + (size_t)t0 * 3 * To * To, nb, tile_size, (hipStream_t)stream)))
+        if ((rc = forward_impl(h, nullptr, x, &g, t0, tile_out + (size_t)t0 * 3 * To * To, nb, tile_size, (hipStream_t)stream, skip_pad)))
             return rc;
     }
     return NUNIF_HIP_OK;
