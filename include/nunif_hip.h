@@ -108,7 +108,7 @@ int nunif_hip_swin_unet_render(nunif_swin_unet *handle, const float *x, float *y
  *   stitch_rows       the single-pass stitch of output rows [y_row_begin, y_row_end) into a compact [3][rows][y_w] band.
  * Same tile grid, same tile store layout and the same stitch kernel as nunif_hip_swin_unet_render: bit-identical results.
  * The tile store is defined only where a stitch of the frame reads it: of a tile of the last tile row / column, the pixels past the
- * frame's edge are not written by a frame render (NUNIF_SWIN_SKIP_PAD), and a band exported by tile_row_band
+ * frame's edge are not written by a frame render (NUNIF_SWIN_SKIP_PAD: 0 whole tiles, 1 level-1 C = 96 blocks only, default 2 every fast block), and a band exported by tile_row_band
  * carries whatever the store held there.  No stitch reads those pixels on either side of an exchange. */
 int nunif_hip_swin_unet_render_tile_rows(nunif_swin_unet *handle, const float *x, int32_t x_h, int32_t x_w,
                                          int32_t tile_size, int32_t batch_size, int32_t row_begin, int32_t row_end,
@@ -131,6 +131,29 @@ typedef struct {
 } nunif_swin_block_extent;
 int nunif_hip_swin_unet_tile_extents(const nunif_tile_grid *grid, int32_t tile_index, const int32_t *blocks_per_stage,
                                      const int32_t *shifts, int32_t to_image_fused, nunif_swin_block_extent *out);
+
+/* The tokens of one block's active windows as groups of at most 16 token slots, the unit of work of the C = 192 tail kernel (host-only
+ * integer math, like the extents above).  ext[n_tiles]: that block's extent of each tile of a minibatch; S: side of the block's token
+ * map (a multiple of 6); shift: 0 or 3.  Token = (tile * S + y) * S + x; a tile's active tokens are those of its active windows,
+ * wrap window included.  They are packed in ascending order, so only the LAST group of a table is partly filled unless a group
+ * would need more than 6 contiguous pieces (runs are at least 3 tokens long, so it never does).
+ * A group names slot r in [0, cnt) as adj[p] + r, where p is the last piece whose first slot is <= r: bits [5 (p - 1), 5 p) of
+ * `bounds` hold the first slot of piece p = 1 .. 5 (16: no such piece), bits [25, 30) hold cnt (1 .. 16).
+ * out == NULL only counts; otherwise at most `cap` groups are written (more needed: an error).  n_groups / n_tokens: totals. */
+typedef struct {
+    int32_t adj[6];
+    uint32_t bounds;
+    uint32_t reserved;
+} nunif_swin_tail_group;
+int nunif_hip_swin_unet_tail_groups(const nunif_swin_block_extent *ext, int32_t n_tiles, int32_t S, int32_t shift,
+                                    nunif_swin_tail_group *out, int64_t cap, int64_t *n_groups, int64_t *n_tokens);
+
+/* Tests only: ONE launch of the C = 192 tail of block `block` of stage `stage` (1 .. 3, or 4 on the 4x net) on caller buffers (device
+ * memory): att and x are [n_tokens][192] fp16, x is updated in place.  groups == NULL: every token; else a device copy of a table
+ * of nunif_hip_swin_unet_tail_groups (n_groups entries naming n_listed tokens), and only those tokens are read and written. */
+int nunif_hip_swin_unet_tail192_test(nunif_swin_unet *handle, int32_t stage, int32_t block, const void *att, void *x,
+                                     int64_t n_tokens, const nunif_swin_tail_group *groups, int64_t n_groups, int64_t n_listed,
+                                     int32_t rev, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * waifu2x CUNet.  Replaces waifu2x/models/cunet.py CUNet.forward :183-196 (UNet1 :52-67, UNet2 :99-121, SEBlock

@@ -40,6 +40,16 @@ class SwinBlockExtent(ctypes.Structure):
     _fields_ = [("n_win", c_int32 * 2), ("wrap", c_int32 * 2)]
 
 
+class SwinTailGroup(ctypes.Structure):
+    """``nunif_swin_tail_group``: up to 16 token slots of the C = 192 tail as contiguous pieces (see ``include/nunif_hip.h``)."""
+    _fields_ = [("adj", c_int32 * 6), ("bounds", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    def tokens(self):
+        cnt = (self.bounds >> 25) & 31
+        firsts = [0] + [(self.bounds >> (5 * p)) & 31 for p in range(5)]
+        return [self.adj[max(p for p in range(6) if firsts[p] <= r)] + r for r in range(cnt)]
+
+
 class TensorDesc(ctypes.Structure):
     _fields_ = [("name", c_char_p), ("data", c_void_p), ("ndim", c_int32), ("shape", c_int64 * 4)]
 
@@ -81,6 +91,10 @@ SIGNATURES = {
     "nunif_hip_swin_unet_stitch_rows": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "nunif_hip_swin_unet_tile_extents": (c_int32, [ctypes.POINTER(TileGrid), c_int32, ctypes.POINTER(c_int32), ctypes.POINTER(c_int32),
                                                    c_int32, ctypes.POINTER(SwinBlockExtent)]),
+    "nunif_hip_swin_unet_tail_groups": (c_int32, [ctypes.POINTER(SwinBlockExtent), c_int32, c_int32, c_int32,
+                                                  ctypes.POINTER(SwinTailGroup), c_int64, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
+    "nunif_hip_swin_unet_tail192_test": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64,
+                                                   c_int32, c_void_p]),
     "nunif_hip_swin_unet_v2_create": (c_int32, [ctypes.POINTER(TensorDesc), c_int32, c_int32, ctypes.POINTER(c_void_p)]),
     "nunif_hip_swin_unet_v2_destroy": (None, [c_void_p]),
     "nunif_hip_swin_unet_v2_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
@@ -274,6 +288,20 @@ def swin_tile_extents(grid, tile_index, blocks_per_stage=(2, 2, 6, 2, 2), shifts
     out = (SwinBlockExtent * n)()
     check(lib().nunif_hip_swin_unet_tile_extents(ctypes.byref(grid), tile_index, per, sh, 1 if to_image_fused else 0, out))
     return [(e.n_win[0], e.n_win[1], e.wrap[0], e.wrap[1]) for e in out]
+
+
+def swin_tail_groups(extents, S, shift):
+    """Token groups of one C = 192 block over a tile minibatch (``nunif_hip_swin_unet_tail_groups``; host-only integer math).
+    ``extents``: that block's ``(n_win_y, n_win_x, wrap_y, wrap_x)`` of each tile; returns ``(ctypes array of SwinTailGroup, n_tokens)``."""
+    ext = (SwinBlockExtent * len(extents))()
+    for e, (ny, nx, wy, wx) in zip(ext, extents):
+        e.n_win[0], e.n_win[1], e.wrap[0], e.wrap[1] = ny, nx, wy, wx
+    ng, nt = c_int64(0), c_int64(0)
+    check(lib().nunif_hip_swin_unet_tail_groups(ext, len(extents), S, shift, None, 0, ctypes.byref(ng), ctypes.byref(nt)))
+    out = (SwinTailGroup * max(1, ng.value))()
+    if ng.value:
+        check(lib().nunif_hip_swin_unet_tail_groups(ext, len(extents), S, shift, out, ng.value, ctypes.byref(ng), ctypes.byref(nt)))
+    return (SwinTailGroup * ng.value).from_buffer(out) if ng.value else (SwinTailGroup * 0)(), nt.value
 
 
 def blend_ramp(blend_size):

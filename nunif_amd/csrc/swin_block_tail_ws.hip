@@ -46,14 +46,27 @@ constexpr int kWsWpFrags = 4 * 18, kWsW0Frags = 4 * 36, kWsW3Frags = 4 * 36;
 
 constexpr int kDmaAhead = 2;              // the att / x tiles of stage A are requested this many trips ahead
 constexpr int kInSlots = kDmaAhead + 1;
+constexpr int kTokSlots = 8;              // LIST: ring of the token indices, written 2 + kDmaAhead trips before they are read
 constexpr int kWsLdsKiB = 2 * kInSlots * 6 + 3 * 6 + 2 * 12 + kWsWpFrags;     // 153 KiB (+ 3 KiB of biases) of 160
 
 int proj_mlp_ws_stream_frags() { return kWsWpFrags + kWsW0Frags + kWsW3Frags; }
 
-template <bool G32 = false>
+// A token group of a LISTED launch (nunif_swin_tail_group of nunif_hip.h, read with one 32-byte scalar load)
+struct alignas(32) TailGroup { int adj[6]; unsigned bounds, reserved; };
+static_assert(sizeof(TailGroup) == sizeof(nunif_swin_tail_group) && sizeof(TailGroup) == 32, "the public group descriptor is 32 bytes");
+
+// LIST: the unit of work is a token GROUP of a table instead of 16 consecutive tokens (frame renders that leave out the windows which
+// only feed padding).  The tail is pointwise per token, so only the two address computations change: dma_in of the
+// H waves and the stage C store of the P waves.  A group is a wave-uniform descriptor — one scalar load per H wave and trip, which
+// counts on lgkmcnt: the loop still has no compiler-visible VECTOR load and the hand-counted vmcnt immediates stay as written.
+// The P waves do not read the table: the H wave of slice 0 leaves the 16 tokens of a tile in a small LDS ring when it requests
+// the tile, four trips before stage C stores it (an outstanding scalar load turns every LDS wait behind it into lgkmcnt(0), and a
+// P wave waits on LDS in every k-step; its first form, one descriptor load per P wave and trip, gave back all that skipping saved).
+// M = 16 x groups.  The whole-tile instance (LIST = false) is the code of before, instruction for instruction.
+template <bool G32 = false, bool LIST = false>
 __global__ void __launch_bounds__(512, 2)
 proj_mlp_ws_kernel(const f16 *__restrict__ att, f16 *x, const f16 *__restrict__ wws, const float *__restrict__ bp,
-                   const float *__restrict__ b0, const float *__restrict__ b3, long M, int rev) {
+                   const float *__restrict__ b0, const float *__restrict__ b3, long M, int rev, const TailGroup *__restrict__ groups) {
     constexpr int C = kWsC, KS = C / 32, HS = 2 * C / 32;   // k-steps of the C-wide and of the hidden (2C) contraction
     constexpr int PT = 3, HT = 6;                           // 16-row output tiles per wave: proj / mlp.3, mlp.0
     constexpr int TOK = 16;
@@ -65,6 +78,7 @@ proj_mlp_ws_kernel(const f16 *__restrict__ att, f16 *x, const f16 *__restrict__ 
     f16x8 *h_l = y_l + 3 * Y_SLOT;                          // [2][HS][64]  chained k order
     f16x8 *wp_l = h_l + 2 * H_SLOT;                         // [4][PT][KS][64]
     float *bias_l = reinterpret_cast<float *>(wp_l + kWsWpFrags * 64);   // bp[C] | b0[2C] | b3[C]
+    int *tok_l = reinterpret_cast<int *>(bias_l + 4 * kWsC);             // LIST: [kTokSlots][16] token of slot r16 of tile k (-1: none)
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -96,6 +110,24 @@ proj_mlp_ws_kernel(const f16 *__restrict__ att, f16 *x, const f16 *__restrict__ 
         return rev ? n_tiles - 1 - t : t;                    // snake order between consecutive kernels
     };
 
+    // LIST: the descriptor of this workgroup's k-th group (k clamped: a prefetch may run one past the last) and the token of this
+    // lane's slot r16 in it.  Slots past the group's count name its last token: loaded, never stored (as m >= M is handled).
+    auto group_of = [&](int k) -> TailGroup { return groups[tile_of(k < n_mine ? k : n_mine - 1)]; };
+    auto group_token = [&](const TailGroup &g, bool &live) -> long {
+        const unsigned bw = g.bounds;
+        const int cnt = (int)((bw >> 25) & 31u);
+        live = r16 < cnt;
+        const int r = live ? r16 : cnt - 1;
+        int off = r >= (int)(bw & 31u) ? g.adj[1] : g.adj[0];
+        if (((bw >> 5) & 31u) < 16u) {                       // (wave-uniform) more than two pieces: short runs, rare
+#pragma unroll
+            for (int p = 2; p < 6; ++p) off = r >= (int)((bw >> (5 * (p - 1))) & 31u) ? g.adj[p] : off;
+        }
+        return (long)(off + r);
+    };
+    TailGroup g_dma = {};                   // H waves: the group of the NEXT trip's DMA
+    static_assert(kTokSlots > 2 + kDmaAhead && (kTokSlots & (kTokSlots - 1)) == 0, "a tile's tokens outlive its trips in the ring");
+
     // The att AND the x tile of the k-th tile go straight from HBM into LDS slot k % kInSlots (LDS-DMA, no registers):
     // fragment ks = lane (r16, grp) holds row[token r16][32 ks + 8 grp .. + 7].  Issued by the H waves kDmaAhead tiles ahead
     // of stage A; slice w takes fragments w and w + 4 of both tiles.  Inline asm on purpose: hipcc orders every later
@@ -106,9 +138,16 @@ proj_mlp_ws_kernel(const f16 *__restrict__ att, f16 *x, const f16 *__restrict__ 
         const unsigned lds_addr = (unsigned)reinterpret_cast<size_t>(dst);
         asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(lds_addr) : "memory");
     };
-    auto dma_in = [&](int k, int slot) {
-        long m = tile_of(k) * TOK + r16;
-        m = m < M ? m : M - 1;
+    auto dma_in = [&](int k, int slot, const TailGroup &g) {
+        long m;
+        if constexpr (LIST) {
+            bool live;
+            m = group_token(g, live);
+            if (slice == 0 && grp == 0) tok_l[(k & (kTokSlots - 1)) * 16 + r16] = live ? (int)m : -1;       // for stage C of tile k
+        } else {
+            m = tile_of(k) * TOK + r16;
+            m = m < M ? m : M - 1;
+        }
         const long off = m * C + grp * 8 + slice * 32;
         dma_frag(att + off, att_l + slot * ATT_SLOT + slice * 64);
         dma_frag(x + off, x_l + slot * ATT_SLOT + slice * 64);
@@ -135,8 +174,12 @@ proj_mlp_ws_kernel(const f16 *__restrict__ att, f16 *x, const f16 *__restrict__ 
     if (role_h) {
 #pragma unroll
         for (int k = 0; k < kDmaAhead; ++k)
-            if (k < n_mine) dma_in(k, k);
+            if (k < n_mine) {
+                if constexpr (LIST) g_dma = group_of(k);
+                dma_in(k, k, g_dma);
+            }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if constexpr (LIST) g_dma = group_of(kDmaAhead);
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 
@@ -153,7 +196,7 @@ proj_mlp_ws_kernel(const f16 *__restrict__ att, f16 *x, const f16 *__restrict__ 
             if (pipe) {
                 int slot = in_a + kDmaAhead;
                 slot = slot >= kInSlots ? slot - kInSlots : slot;
-                dma_in(i + 2 + kDmaAhead, slot);
+                dma_in(i + 2 + kDmaAhead, slot, g_dma);
             }
             if (i + 1 >= 0 && i + 1 < n_mine) {
                 const f16x8 *ys = y_l + y_b * Y_SLOT + lane;
@@ -183,7 +226,16 @@ proj_mlp_ws_kernel(const f16 *__restrict__ att, f16 *x, const f16 *__restrict__ 
                     for (int j = 0; j < 2 * KS; ++j) mfma_at(p, j);
                     hd[(3 * slice + p - 1) * 64] = gelu8t<G32>(acc[2 * p - 2], acc[2 * p - 1]);
                 }
+                // LIST: the group of the next trip's DMA, requested in front of the last GELU (pinned: hipcc sinks it to the trip's
+                // end otherwise): ~90 VALU operations with no LDS wait behind it before the trip's closing lgkmcnt(0)
+                if constexpr (LIST) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    g_dma = group_of(i + 3 + kDmaAhead);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
                 hd[(3 * slice + HT / 2 - 1) * 64] = gelu8t<G32>(acc[HT - 2], acc[HT - 1]);
+            } else if constexpr (LIST) {
+                g_dma = group_of(i + 3 + kDmaAhead);
             }
             // the next trip's stage A reads tile i + 3: requested kDmaAhead trips ago
             dma_wait(pipe);
@@ -208,6 +260,10 @@ proj_mlp_ws_kernel(const f16 *__restrict__ att, f16 *x, const f16 *__restrict__ 
             if (do_c) {
                 const f16x8 *hs = h_l + h_c * H_SLOT + lane;
                 const f16x8 *ys = y_l + y_c * Y_SLOT + lane;
+                // LIST: this lane's token of tile i, read early (the opaque use in the loop below keeps hipcc from sinking the read
+                // to the store, where it stood behind a full LDS wait; LDS returns in order, so an early read costs no wait of its own)
+                int tok_c = 0;
+                if constexpr (LIST) tok_c = tok_l[(i & (kTokSlots - 1)) * 16 + r16];
                 f16x8 hq[kHAhead + 1];
 #pragma unroll
                 for (int ks = 0; ks < kHAhead; ++ks) hq[ks] = hs[ks * 64];
@@ -222,6 +278,7 @@ proj_mlp_ws_kernel(const f16 *__restrict__ att, f16 *x, const f16 *__restrict__ 
 #pragma unroll
                 for (int ks = 0; ks < HS; ++ks) {
                     if (ks + kHAhead < HS) hq[(ks + kHAhead) % (kHAhead + 1)] = hs[(ks + kHAhead) * 64];
+                    if constexpr (LIST) { if (ks == 1) asm volatile("" : "+v"(tok_c)); }
                     if (ks == HS - 4) req_a(0);
                     if (ks == HS - 2) req_a(1);
 #pragma unroll
@@ -229,8 +286,16 @@ proj_mlp_ws_kernel(const f16 *__restrict__ att, f16 *x, const f16 *__restrict__ 
                         acc[nt] = MFMA_16x16x32(wr[nt * HS + ks], hq[ks % (kHAhead + 1)], acc[nt]);
                     }
                 }
-                const long m = tile_of(i) * TOK + r16;
-                if (m < M) {
+                long m;
+                bool live;
+                if constexpr (LIST) {
+                    m = tok_c;
+                    live = tok_c >= 0;
+                } else {
+                    m = tile_of(i) * TOK + r16;
+                    live = m < M;
+                }
+                if (live) {
 #pragma unroll
                     for (int nt = 0; nt < PT; ++nt) {
                         const f16x4 o = {(f16)acc[nt][0], (f16)acc[nt][1], (f16)acc[nt][2], (f16)acc[nt][3]};
@@ -281,23 +346,28 @@ proj_mlp_ws_kernel(const f16 *__restrict__ att, f16 *x, const f16 *__restrict__ 
 }
 
 int launch_proj_mlp_ws(const f16 *att, f16 *x, const f16 *wws, const float *bp, const float *b0, const float *b3, long M,
-                       hipStream_t s, int rev, int gelu32) {
+                       hipStream_t s, int rev, int gelu32, const nunif_swin_tail_group *groups, long n_groups, long n_listed) {
     if (M == 0) return NUNIF_HIP_OK;
-    ProfScope ps("proj_mlp_ws_kernel", s, 2.0 * (double)M * kWsC * kWsC * 5.0, (double)M * kWsC * 2.0 * 3.0);
-    constexpr size_t smem = (size_t)kWsLdsKiB * 1024 + 4 * kWsC * 4;
+    NUNIF_REQUIRE(!groups || (n_groups > 0 && n_listed > 0 && n_listed <= 16 * n_groups && n_listed <= M && ((size_t)groups & 31) == 0),
+                  "proj_mlp_ws: a table of %ld groups cannot name %ld of %ld tokens", n_groups, n_listed, M);
+    if (groups) M = 16 * n_groups;                   // the kernel's unit of work: one group per 16 token slots
+    const double work = (double)(groups ? n_listed : M);          // a listed launch counts the tokens it names
+    ProfScope ps("proj_mlp_ws_kernel", s, 2.0 * work * kWsC * kWsC * 5.0, work * kWsC * 2.0 * 3.0);
+    const size_t smem = (size_t)kWsLdsKiB * 1024 + 4 * kWsC * 4 + (groups ? kTokSlots * 16 * 4 : 0);
     const long n_tiles = (M + 15) / 16;
     const unsigned blocks = (unsigned)std::min<long>(n_tiles, 256);
     auto go = [&](auto kern, int slot) -> int {
-        static bool configured[2] = {false, false};
+        static bool configured[4] = {false, false, false, false};
         if (!configured[slot]) {
             NUNIF_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
             configured[slot] = true;
         }
-        kern<<<blocks, 512, smem, s>>>(att, x, wws, bp, b0, b3, M, rev);
+        kern<<<blocks, 512, smem, s>>>(att, x, wws, bp, b0, b3, M, rev, reinterpret_cast<const TailGroup *>(groups));
         return NUNIF_HIP_OK;
     };
     int rc;
-    rc = gelu32 ? go(proj_mlp_ws_kernel<true>, 1) : go(proj_mlp_ws_kernel<false>, 0);
+    if (groups) rc = gelu32 ? go(proj_mlp_ws_kernel<true, true>, 3) : go(proj_mlp_ws_kernel<false, true>, 2);
+    else rc = gelu32 ? go(proj_mlp_ws_kernel<true, false>, 1) : go(proj_mlp_ws_kernel<false, false>, 0);
     if (rc) return rc;
     NUNIF_LAUNCH_CHECK();
     return NUNIF_HIP_OK;

@@ -184,8 +184,11 @@ int launch_swin_block96(f16 *x, const f16 *wqkv, const float *bqkv, const float 
 // ---- the same tail at C = 192 with the weights stationary on chip (swin_block_tail_ws.hip) --------------------------
 // wws: Wp [slice 4][nt 3][ks 6] (plain k order) | W0 [4][nt 6][ks 6] | W3 [4][nt 3][ks 12] (chained k order), 1-KiB fragments
 int proj_mlp_ws_stream_frags();
+// groups (frame renders that leave out padding-only windows): a device table of n_groups token groups naming
+// n_listed tokens (nunif_hip_swin_unet_tail_groups, 32-byte aligned); only those tokens of att are read and of x updated
 int launch_proj_mlp_ws(const f16 *att, f16 *x, const f16 *wws, const float *bp, const float *b0, const float *b3, long M,
-                       hipStream_t s, int rev = 0, int gelu32 = 0);
+                       hipStream_t s, int rev = 0, int gelu32 = 0, const nunif_swin_tail_group *groups = nullptr, long n_groups = 0,
+                       long n_listed = 0);
 
 // ---- fused qkv Linear + (shifted) 6x6 window attention, one window per wave, qkv weights resident in LDS, no barrier in the
 // window loop (swin_qkv_attn_r.hip); C = 96 (6 heads of 16) or 192 (6 heads of 32).  x: [B,H,W,C] -> att: [B,H,W,C]
@@ -198,8 +201,9 @@ constexpr int kQkvBiasFloatsPerHead = 36 * 52;
 int launch_qkv_attn_r(const f16 *x, f16 *att, const f16 *wres, const float *bqkv, const float *btab32,
                       int B, int H, int W, int C, int heads, int shift, hipStream_t s, int rev = 0, int window_major = 0,
                       const unsigned *win_list = nullptr, int n_list = 0);
-// win_list (window_major only): run the n_list windows it names, entry = batch << 16 | window row << 8 | window column, instead of
-// all B (H / 6) (W / 6); window i of the list lands at slot i of the window-major att map (a compact map of 36 n_list tokens)
+// win_list: run the n_list windows it names, entry = batch << 16 | window row << 8 | window column, instead of all
+// B (H / 6) (W / 6).  window_major: window i of the list lands at slot i of the window-major att map (a compact map of 36 n_list
+// tokens); pixel-major: a listed window writes att at its own pixels, and the pixels of the other windows are left untouched
 
 // ---- (shifted) 6x6 window attention on a fused qkv map ----------------------------------------------------------
 // qkv: [B,H,W,3C] fp16 (q | k | v, each heads x hd), out: [B,H,W,C]; bias: [heads][36][48] fp32 with the

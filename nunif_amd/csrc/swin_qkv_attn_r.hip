@@ -427,8 +427,9 @@ int launch_qkv_attn_r(const f16 *x, f16 *att, const f16 *wres, const float *bqkv
     QkvAttnRArgs a;
     a.x = x; a.att = att; a.wres = wres; a.bqkv = bqkv; a.btab32 = btab32;
     a.B = B; a.H = H; a.W = W; a.shift = shift;
-    NUNIF_REQUIRE(!win_list || (window_major && n_list > 0 && n_list <= B * (H / 6) * (W / 6) && B < 65536 && H / 6 < 256 && W / 6 < 256),
-                  "qkv_attn: a window list needs the window-major map and at most 65535 x 255 x 255 windows");
+    // (a pixel-major launch writes a listed window at its own pixels: the kernel decodes the window from the list in both map orders)
+    NUNIF_REQUIRE(!win_list || (n_list > 0 && n_list <= B * (H / 6) * (W / 6) && B < 65536 && H / 6 < 256 && W / 6 < 256),
+                  "qkv_attn: a window list holds 1 .. B (H / 6) (W / 6) windows of at most 65535 x 255 x 255");
     a.n_windows = win_list ? n_list : B * (H / 6) * (W / 6);
     a.wlist = win_list;
     a.rev = rev;            // snake order between consecutive kernels (swin_unet.cpp next_dir)

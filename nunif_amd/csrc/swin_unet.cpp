@@ -12,6 +12,7 @@
 
 #include "host_weights.h"
 #include "swin_kernels.h"
+#include "swin_tail_groups_host.h"
 
 namespace nunif {
 
@@ -46,12 +47,16 @@ struct Block {
     float *b96_btab = nullptr;
 };
 
-// Windows of one C = 96 block that a frame render runs (pad skipping), for one tile minibatch: `list` holds one
-// entry per active window, (tile in the minibatch << 16 | window row << 8 | window column), tile-major; the attention kernel
-// writes window i of the list at slot i of the window-major att map and the tail walks `pixmap` (token 36 i + t -> pixel).
+// Windows of one block that a frame render runs (pad skipping), for one tile minibatch: `list` holds one
+// entry per active window, (tile in the minibatch << 16 | window row << 8 | window column), tile-major.  C = 96: the attention
+// kernel writes window i of the list at slot i of the window-major att map and the tail walks `pixmap` (token 36 i + t -> pixel).
+// C = 192: the attention kernel writes a listed window at its own pixels and the tail walks `groups`, the same tokens in pixel
+// order packed 16 to a group (nunif_hip_swin_unet_tail_groups).
 struct SkipBlock {
     unsigned *list = nullptr;
     int *pixmap = nullptr;
+    const nunif_swin_tail_group *groups = nullptr;
+    long n_groups = 0, n_tokens = 0;
     int n_windows = 0;
 };
 
@@ -61,6 +66,7 @@ struct SkipBlock {
 struct SkipPlan {
     nunif_tile_grid grid = {};
     int tile_begin = 0, B = 0;
+    int level = 0;                        // NUNIF_SWIN_SKIP_PAD of the call that built it: 1 = level-1 C = 96 blocks only, 2 = all fast blocks
     std::vector<SkipBlock> stage[5];      // empty where the stage runs whole
     void *dev = nullptr;
     size_t bytes = 0;
@@ -130,6 +136,14 @@ extern "C" int nunif_hip_swin_unet_tile_extents(const nunif_tile_grid *g, int32_
         const int e2_in = stage_back(1, std::min(size[1], std::max(2 * e3_in, e4_in)));
         (void)stage_back(0, std::min(size[0], std::max(2 * e2_in, top_in)));
     }
+    return NUNIF_HIP_OK;
+}
+
+// Pure integer host function (declared in nunif_hip.h): swin_tail_groups_host.h
+extern "C" int nunif_hip_swin_unet_tail_groups(const nunif_swin_block_extent *ext, int32_t n_tiles, int32_t S, int32_t shift,
+                                               nunif_swin_tail_group *out, int64_t cap, int64_t *n_groups, int64_t *n_tokens) {
+    const char *msg = swin_tail_groups_host(ext, n_tiles, S, shift, out, cap, n_groups, n_tokens);
+    NUNIF_REQUIRE(!msg, "%s", msg);
     return NUNIF_HIP_OK;
 }
 
@@ -459,8 +473,10 @@ int run_stage(nunif_swin_unet *h, std::vector<Block> &blocks, f16 *x, int B, int
         // window order); debug taps want the pixel-major map the oracle has
         // (the tail indexes the window-major map in 32 bits: 96 tok elements; larger launches take the pixel-major map)
         const bool att_wm = dim == 96 && h->att_wm && !h->taps_on && 96L * (long)tok < (1L << 31);
-        // frame renders: only the windows the stitch depends on (skip_plan); att is then compact, slot i = window i of the list
-        const SkipBlock *sk = skip && att_wm && i < skip->size() && (*skip)[i].list ? &(*skip)[i] : nullptr;
+        // frame renders: only the windows the stitch depends on (skip_plan).  C = 96: att is then compact, slot i = window i of the
+        // list; C = 192: att stays pixel-major, written at the listed windows only, and the tail walks the same tokens (sk->groups)
+        const SkipBlock *sk = skip && i < skip->size() && (*skip)[i].list && (dim == 192 ? (*skip)[i].groups != nullptr : att_wm)
+                                  ? &(*skip)[i] : nullptr;
         if ((rc = launch_qkv_attn_r(x, att, bl.qkv_res, bl.qkv_rbias, bl.attn_btab32, B, S, S, dim, h->heads, shift, s, next_dir(h),
                                     att_wm ? 1 : 0, sk ? sk->list : nullptr, sk ? sk->n_windows : 0)))
             return rc;
@@ -469,7 +485,8 @@ int run_stage(nunif_swin_unet *h, std::vector<Block> &blocks, f16 *x, int B, int
         const bool last = i + 1 == blocks.size();
         if (dim == 192) {
             // C = 192: weights stationary in registers / LDS (swin_block_tail_ws.hip)
-            if ((rc = launch_proj_mlp_ws(att, x, bl.tail_ws, bl.proj.bias, bl.mlp0.bias, bl.mlp3.bias, (long)tok, s, next_dir(h), h->gelu32)))
+            if ((rc = launch_proj_mlp_ws(att, x, bl.tail_ws, bl.proj.bias, bl.mlp0.bias, bl.mlp3.bias, (long)tok, s, next_dir(h), h->gelu32,
+                                         sk ? sk->groups : nullptr, sk ? sk->n_groups : 0, sk ? sk->n_tokens : 0)))
                 return rc;
         } else {
             const int eff_shift = S <= 6 ? 0 : shift;
@@ -521,19 +538,24 @@ int ensure_workspace(nunif_swin_unet *h, int B, int T) {
 // INVARIANT the skipping rests on: the stem, PatchDown, PatchUp and the un-fused to_image always process WHOLE tiles, so every
 // activation map is fully rewritten from the current frame before a block reads it; a token a block skips keeps that block's
 // input (finite, a function of the current frame).  The far half of a shifted block's wrap window is read as masked keys whose
-// softmax weight is an exact fp16 zero, and 0 x finite = 0 where 0 x a stale Inf / NaN would not be.  Only the C = 96 blocks skip
-// (their tail walks the same compact list through `pixmap`, and the compact att map is written in full before it is read);
-// C = 192 blocks and the generic block path run whole tiles, which is a superset of what their consumers need.
+// softmax weight is an exact fp16 zero, and 0 x finite = 0 where 0 x a stale Inf / NaN would not be.  Every stage whose blocks are
+// all `fast` skips (level 2; level 1: the level-1 C = 96 stages only).  A C = 96 tail walks the compact list through `pixmap`, and
+// the compact att map is written in full before it is read; a C = 192 tail walks the tokens of exactly the windows its attention
+// ran (`groups`), so it reads no att the launch before it did not write and updates every listed token exactly once (it works in
+// place on x).  The generic block path runs whole tiles, which is a superset of what its consumers need.
+// Plan bytes per tile of 256 whose every block lists: 4 C = 96 blocks x 1 600 windows x 148 B + 2 200 windows of the 10 C = 192 blocks
+// x (4 B + 36 / 16 groups x 32 B) = 0.95 + 0.17 MB, so kMaxPlanBytes holds about 950 tiles: 21 geometries of 1080p (a plan lists every
+// tile of its minibatch once one of them has windows to leave out).
 constexpr size_t kMaxPlans = 1024, kMaxPlanBytes = (size_t)1 << 30;
 
-int skip_plan(nunif_swin_unet *h, const nunif_tile_grid *g, int t0, int B, hipStream_t s, const SkipPlan **out) {
+int skip_plan(nunif_swin_unet *h, const nunif_tile_grid *g, int t0, int B, int level, hipStream_t s, const SkipPlan **out) {
     *out = nullptr;
     const int S = g->tile_size - 16, nw = S / 6;
     if (!h->att_wm || h->taps_on || h->block96 || S <= 6 || nw >= 256 || B >= 65536 || 96L * B * S * S >= (1L << 31) ||
         g->out_tile_size != S * g->scale)
         return NUNIF_HIP_OK;
     for (auto it = h->plans.begin(); it != h->plans.end(); ++it)
-        if (it->tile_begin == t0 && it->B == B && memcmp(g, &it->grid, sizeof(*g)) == 0) {
+        if (it->tile_begin == t0 && it->B == B && it->level == level && memcmp(g, &it->grid, sizeof(*g)) == 0) {
             h->plans.splice(h->plans.begin(), h->plans, it);
             if (it->dev && it->built_on != s) NUNIF_HIP_CHECK(hipStreamWaitEvent(s, it->ready, 0));
             *out = &*it;
@@ -552,15 +574,19 @@ int skip_plan(nunif_swin_unet *h, const nunif_tile_grid *g, int t0, int B, hipSt
         if ((rc = nunif_hip_swin_unet_tile_extents(g, t0 + b, per_stage, shifts.data(), 0, ext[b].data()))) return rc;
     h->plans.emplace_front();
     SkipPlan &plan = h->plans.front();
-    plan.grid = *g; plan.tile_begin = t0; plan.B = B; plan.built_on = s;
-    struct Piece { int st, i, shift; size_t first, n; };
+    auto fail = [&](int code) { h->drop_plan(h->plans.begin()); return code; };
+    plan.grid = *g; plan.tile_begin = t0; plan.B = B; plan.level = level; plan.built_on = s;
+    struct Piece { int st, i, shift, dim; size_t first, n, gfirst; int64_t n_groups, n_tokens; };
     std::vector<Piece> pieces;
     int first = 0;
     for (int st = 0; st < 5; first += per_stage[st], ++st) {
         const int dim = st == 0 ? h->C : (st == 4 ? h->top_dim : 2 * h->C);
-        bool fast = (st == 0 || st == 4) && dim == 96;      // level 1 of the 1x / 2x nets and swin1 of the 4x net
+        // level 1: level 1 of the 1x / 2x nets and swin1 of the 4x net; level 2: every stage of fast blocks
+        bool fast = level >= 2 ? dim == 96 || dim == 192 : (st == 0 || st == 4) && dim == 96;
         for (const Block &bl : h->swin[st]) fast = fast && bl.fast;
         if (!fast) continue;
+        const int Ss = st == 0 || st == 4 ? S : (st == 2 ? S / 4 : S / 2), nw = Ss / 6;       // this stage's token map
+        if (Ss <= 6) continue;
         plan.stage[st].resize(per_stage[st]);
         for (int i = 0; i < per_stage[st]; ++i) {
             const size_t at = plan.host.size();
@@ -575,14 +601,32 @@ int skip_plan(nunif_swin_unet *h, const nunif_tile_grid *g, int t0, int B, hipSt
             }
             const size_t n = plan.host.size() - at;
             if (n == (size_t)B * nw * nw || n == 0) { plan.host.resize(at); continue; }   // nothing to leave out: the whole-tile path
-            pieces.push_back({st, i, shifts[first + i], at, n});
+            Piece pc = {st, i, shifts[first + i], dim, at, n, 0, 0, 0};
+            if (dim == 192) {
+                // the same tokens in pixel order, 16 to a group: 8 words per group behind the list, 32-byte aligned
+                std::vector<nunif_swin_block_extent> eb(B);
+                for (int b = 0; b < B; ++b) eb[b] = ext[b][first + i];
+                // (one pass: 36 n tokens fill ceil(36 n / 16) groups; the slack is for a group closed early, which the builder never needs)
+                const int64_t cap = (36 * (int64_t)n + 15) / 16 + 8;
+                plan.host.resize((plan.host.size() + 7) / 8 * 8);
+                pc.gfirst = plan.host.size();
+                plan.host.resize(pc.gfirst + 8 * (size_t)cap);
+                static_assert(sizeof(nunif_swin_tail_group) == 8 * sizeof(unsigned), "a group is 8 words of the plan");
+                if ((rc = nunif_hip_swin_unet_tail_groups(eb.data(), B, Ss, pc.shift, (nunif_swin_tail_group *)&plan.host[pc.gfirst], cap,
+                                                          &pc.n_groups, &pc.n_tokens)))
+                    return fail(rc);
+                plan.host.resize(pc.gfirst + 8 * (size_t)pc.n_groups);
+                if (pc.n_tokens != 36 * (int64_t)n) { set_error("internal: %lld grouped tokens for %zu windows", (long long)pc.n_tokens, n); return fail(NUNIF_HIP_EINVAL); }
+            }
+            pieces.push_back(pc);
         }
     }
     if (pieces.empty()) { *out = &plan; return NUNIF_HIP_OK; }       // (cached all the same: the next frame finds it)
-    // layout: all lists | token tables (36 ints per listed window), the tables 256-byte aligned
+    // layout: all lists and group tables (one upload) | C = 96 token tables (36 ints per listed window), the tables 256-byte aligned
     const size_t list_bytes = (plan.host.size() * 4 + 255) / 256 * 256;
-    plan.bytes = list_bytes + plan.host.size() * 36 * 4;
-    auto fail = [&](int code) { h->drop_plan(h->plans.begin()); return code; };
+    size_t n_pix = 0;
+    for (const Piece &pc : pieces) n_pix += pc.dim == 96 ? pc.n * 36 : 0;
+    plan.bytes = list_bytes + n_pix * 4;
     if (hipMalloc(&plan.dev, plan.bytes) != hipSuccess) {
         set_error("hipMalloc(%zu) of the window lists failed", plan.bytes);
         plan.bytes = 0;
@@ -594,11 +638,18 @@ int skip_plan(nunif_swin_unet *h, const nunif_tile_grid *g, int t0, int B, hipSt
         set_error("upload of the window lists failed");
         return fail(NUNIF_HIP_EHIP);
     }
+    size_t pix_at = 0;
     for (const Piece &pc : pieces) {
         SkipBlock &sb = plan.stage[pc.st][pc.i];
         sb.list = (unsigned *)plan.dev + pc.first;
-        sb.pixmap = (int *)((char *)plan.dev + list_bytes) + pc.first * 36;
         sb.n_windows = (int)pc.n;
+        if (pc.dim == 192) {
+            sb.groups = (const nunif_swin_tail_group *)((unsigned *)plan.dev + pc.gfirst);
+            sb.n_groups = (long)pc.n_groups; sb.n_tokens = (long)pc.n_tokens;
+            continue;
+        }
+        sb.pixmap = (int *)((char *)plan.dev + list_bytes) + pix_at;
+        pix_at += pc.n * 36;
         if ((rc = launch_winmap_list_build(sb.pixmap, sb.list, sb.n_windows, S, S, pc.shift, s))) return fail(rc);
     }
     if (hipEventRecord(plan.ready, s) != hipSuccess) { set_error("hipEventRecord failed"); return fail(NUNIF_HIP_EHIP); }
@@ -609,13 +660,13 @@ int skip_plan(nunif_swin_unet *h, const nunif_tile_grid *g, int t0, int B, hipSt
 
 // x: tile mode [B,3,T,T] or (frame != NULL) the frame + grid; z: [B,3,S*s,S*s]
 int forward_impl(nunif_swin_unet *h, const float *x, const float *frame, const nunif_tile_grid *grid,
-                 int tile_begin, float *z, int B, int T, hipStream_t s, bool skip_pad = false) {
+                 int tile_begin, float *z, int B, int T, hipStream_t s, int skip_pad = 0) {
     const int S = T - 16, C = h->C;
     NUNIF_REQUIRE(T > 16 && S % 12 == 0 && S % 16 == 0, "tile_size %d is not valid for swin_unet", T);
     int rc;
     if ((rc = ensure_workspace(h, B, T))) return rc;
     h->plan = nullptr;
-    if (frame && skip_pad && (rc = skip_plan(h, grid, tile_begin, B, s, &h->plan))) return rc;
+    if (frame && skip_pad && (rc = skip_plan(h, grid, tile_begin, B, skip_pad, s, &h->plan))) return rc;
     auto skip_of = [&](int st) { return h->plan && !h->plan->stage[st].empty() ? &h->plan->stage[st] : nullptr; };
     f16 *s1 = (f16 *)h->s1.p, *f1 = (f16 *)h->f1.p, *f2 = (f16 *)h->f2.p, *f3 = (f16 *)h->f3.p;
 
@@ -654,7 +705,7 @@ stem_done:
     if ((rc = run_stage(h, h->swin[0], f1, B, S, C, s, "swin1", nullptr, skip_of(0)))) return rc;                          // swin1 -> x3
     if ((rc = run_patchdown(h->down1, f1, B, S / 2, S / 2, C, 0, f2, s, "gemm_down1", next_dir(h)))) return rc;
     if ((rc = tap(h, "down1", f2, (size_t)B * (S / 2) * (S / 2) * 2 * C * 2, s))) return rc;
-    if ((rc = run_stage(h, h->swin[1], f2, B, S / 2, 2 * C, s, "swin2"))) return rc;                  // swin2 -> x4
+    if ((rc = run_stage(h, h->swin[1], f2, B, S / 2, 2 * C, s, "swin2", nullptr, skip_of(1)))) return rc;                  // swin2 -> x4
     if (h->down2_split) {
         if ((rc = run_patchdown(h->down2, f2, B, S / 4, S / 4, 2 * C, 0, f3, s, "gemm_down2", next_dir(h)))) return rc;
     } else if ((rc = run_gemm(h->down2, f2, B, S / 2, S / 2, 2 * C, S / 4, S / 4, 2, 0, 0, 2, 0, 0, 0.f, nullptr, f3,
@@ -664,11 +715,11 @@ stem_done:
                                          2 * C, 1, s, "gemm_down2b", next_dir(h))))
         return rc;
     if ((rc = tap(h, "down2", f3, (size_t)B * (S / 4) * (S / 4) * 2 * C * 2, s))) return rc;
-    if ((rc = run_stage(h, h->swin[2], f3, B, S / 4, 2 * C, s, "swin3"))) return rc;                  // swin3
+    if ((rc = run_stage(h, h->swin[2], f3, B, S / 4, 2 * C, s, "swin3", nullptr, skip_of(2)))) return rc;                  // swin3
     // x = up2(x5) + x4, written in place over x4 (each lane reads then writes its own 8 bytes)
     if ((rc = run_patchup(h->up2, f3, B, S / 4, S / 4, 2 * C, f2, s, "gemm_up2", next_dir(h)))) return rc;
     if ((rc = tap(h, "up2", f2, (size_t)B * (S / 2) * (S / 2) * 2 * C * 2, s))) return rc;
-    if ((rc = run_stage(h, h->swin[3], f2, B, S / 2, 2 * C, s, "swin4"))) return rc;                  // swin4
+    if ((rc = run_stage(h, h->swin[3], f2, B, S / 2, 2 * C, s, "swin4", nullptr, skip_of(3)))) return rc;                  // swin4
     f16 *top = f1;
     if (h->has_proj2) {
         // 4x: x = up1(x) + proj2(x3)   (swin_unet.py:166,195-196)
@@ -868,11 +919,24 @@ extern "C" int nunif_hip_swin_unet_forward(nunif_swin_unet *h, const float *x, f
     return forward_impl(h, x, nullptr, nullptr, 0, z, batch, tile_size, (hipStream_t)stream);
 }
 
-// NUNIF_SWIN_SKIP_PAD=0: the frame entry points push whole tiles through every block, as the tile entry always does (A/B runs);
-// read at call time
-static bool skip_pad_enabled() {
+// NUNIF_SWIN_SKIP_PAD, read at call time: 0 = the frame entry points push whole tiles through every block, as the tile entry always
+// does; 1 = only the level-1 C = 96 blocks leave windows out (A/B runs against the C = 192 skipping); unset or >= 2 = every fast block
+static int skip_pad_level() {
     const char *v = getenv("NUNIF_SWIN_SKIP_PAD");
-    return !(v && atoi(v) == 0);
+    if (!v) return 2;
+    const int l = atoi(v);
+    return l <= 0 ? 0 : (l == 1 ? 1 : 2);
+}
+
+extern "C" int nunif_hip_swin_unet_tail192_test(nunif_swin_unet *h, int32_t stage, int32_t block, const void *att, void *x,
+                                                int64_t n_tokens, const nunif_swin_tail_group *groups, int64_t n_groups,
+                                                int64_t n_listed, int32_t rev, void *stream) {
+    NUNIF_REQUIRE(h && att && x && n_tokens > 0 && stage >= 0 && stage < 5 && block >= 0 && block < (int)h->swin[stage].size(),
+                  "tail192_test: bad argument");
+    const Block &bl = h->swin[stage][block];
+    NUNIF_REQUIRE(bl.fast && bl.tail_ws, "tail192_test: stage %d block %d has no C = 192 tail", stage, block);
+    return launch_proj_mlp_ws((const f16 *)att, (f16 *)x, bl.tail_ws, bl.proj.bias, bl.mlp0.bias, bl.mlp3.bias, (long)n_tokens,
+                              (hipStream_t)stream, rev ? 1 : 0, h->gelu32, groups, (long)n_groups, (long)n_listed);
 }
 
 extern "C" int nunif_hip_swin_unet_render(nunif_swin_unet *h, const float *x, float *y, int32_t x_h, int32_t x_w,
@@ -890,7 +954,7 @@ extern "C" int nunif_hip_swin_unet_render(nunif_swin_unet *h, const float *x, fl
     if ((rc = h->tile_out.ensure((size_t)n_tiles * 3 * To * To * sizeof(float)))) return rc;
     float *tile_out = (float *)h->tile_out.p;
     hipStream_t st = (hipStream_t)stream;
-    const bool skip_pad = skip_pad_enabled();
+    const int skip_pad = skip_pad_level();
     for (int t0 = 0; t0 < n_tiles; t0 += batch_size) {
         const int nb = std::min(batch_size, n_tiles - t0);
         if ((rc = forward_impl(h, nullptr, x, &g, t0, tile_out + (size_t)t0 * 3 * To * To, nb, tile_size, st, skip_pad)))
@@ -924,7 +988,7 @@ extern "C" int nunif_hip_swin_unet_render_tile_rows(nunif_swin_unet *h, const fl
     const size_t To = g.out_tile_size;
     float *tile_out = (float *)h->tile_out.p;
     const int t_end = row_end * g.w_blocks;
-    const bool skip_pad = skip_pad_enabled();
+    const int skip_pad = skip_pad_level();
     for (int t0 = row_begin * g.w_blocks; t0 < t_end; t0 += batch_size) {
         const int nb = std::min(batch_size, t_end - t0);
         if ((rc = forward_impl(h, nullptr, x, &g, t0, tile_out + (size_t)t0 * 3 * To * To, nb, tile_size, (hipStream_t)stream, skip_pad)))

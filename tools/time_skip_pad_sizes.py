@@ -1,9 +1,10 @@
-"""Frames of DIFFERENT sizes through one swin_unet 2x handle, NUNIF_SWIN_SKIP_PAD on versus off: what a folder of images pays for
-the window lists of pad skipping — a new list per frame geometry the first time it is seen, a cached one after.
+"""Frames of DIFFERENT sizes through one swin_unet 2x handle at two levels of NUNIF_SWIN_SKIP_PAD (0 = whole tiles, 1 = the level-1
+C = 96 blocks skip, 2 = every fast block): what a folder of images pays for the window lists and group tables of pad skipping
+ — new ones per frame geometry the first time it is seen, cached ones after.
 
-    python tools/time_skip_pad_sizes.py [--rounds 3] [--out FILE]
+    python tools/time_skip_pad_sizes.py [--levels 1,2] [--rounds 3] [--out FILE]
 
-Prints, per switch setting, ms per frame of (a) the first pass over the sizes (every geometry new), (b) later passes (every
+Prints, per level, ms per frame of (a) the first pass over the sizes (every geometry new), (b) later passes (every
 geometry cached), (c) a stream of never-repeating sizes, and (d) 60 frames of one 1080p geometry on a fresh handle (the
 benchmark's single-stream leg, first frame included)."""
 import argparse
@@ -33,12 +34,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--levels", default="1,2", help="the two NUNIF_SWIN_SKIP_PAD levels to alternate between")
     a = ap.parse_args()
     g = torch.Generator().manual_seed(1)
     frames = [torch.rand(3, h, w, generator=g).to("cuda:0") for h, w in SIZES]
     fresh = [torch.rand(3, 700 + 7 * i, 1100 + 11 * i, generator=g).to("cuda:0") for i in range(24)]      # 24 sizes, each seen once
     res = {}
-    for on in ("0", "1", "0", "1"):
+    lo, hi = a.levels.split(",")
+    for on in (lo, hi, lo, hi):
         os.environ["NUNIF_SWIN_SKIP_PAD"] = on                 # read by the library at every call
         m = SwinUNet2x().eval().to("cuda:0")
         m.render_frame(frames[-1][:, :300, :300].contiguous(), tile_size=256, batch_size=64)      # kernels loaded, workspace exists
