@@ -755,6 +755,15 @@ int nunif_hip_cliqa_select_patches(const float *image, int32_t H, int32_t W, int
  *   capacity is smaller than the body, out_len[b] = -1 and nothing of slot b is written; max_bytes is always enough.  workspace:
  *   workspace_bytes() bytes of device memory, 256-byte aligned; calls that overlap need their own.  1 <= H, W <= 8192, B <= 16;
  *   anything else is refused.
+ * Forms 4..6 (the waifu2x image route: waifu2x/ui_utils.py:42-100 process_image / process_images, nunif/utils/pil_io.py:240-323
+ *   to_image / save_image) take planar fp32 colour [B,colour_channels,H,W] and, apart from it, a planar fp32 alpha [B,1,H,W], as
+ *   Waifu2x.convert returns them; every plane is quantised as form 0 is (quantize256).  3 names no form and stays refused.
+ *   4 = RGBA 8 (colour type 6; colour_channels 3); 5 = grey 8 (colour type 0; alpha NULL); 6 = grey + alpha 8 (colour type 4).
+ *   The grey forms take colour_channels 1 (the plane itself) or 3: the three bytes of a pixel go through PIL's
+ *   Image.convert("L"), (19595 R + 38470 G + 7471 B + 0x8000) >> 16, as save_image's meta["grayscale"] branch does.
+ *   header, max_bytes and workspace_bytes take these forms; encode and debug_filtered refuse them: encode_planes and
+ *   debug_filtered_planes are the same calls with the two source pointers, and take forms 4..6 only.  debug_codes takes them with
+ *   src = one tensor [B,C+1,H,W] (C = 3 for form 4, 1 for form 6) whose last plane is the alpha, or [B,1,H,W] for form 5.
  * debug_filtered (tests) runs the first launch alone: the filtered bytes [B][H][1 + W * bpp] u8 (device), the filter type first.
  * debug_codes (tests) runs the first three launches: per stripe the histogram and the code lengths, [B][stripes][336] i32 each
  *   (device): 286 literal / length symbols, 30 distance symbols, 19 code-length symbols, one word of padding. */
@@ -767,6 +776,11 @@ int nunif_hip_png_encode(const void *src, int32_t form, int32_t B, int32_t H, in
 int nunif_hip_png_debug_filtered(const void *src, int32_t form, int32_t B, int32_t H, int32_t W, uint8_t *filtered, void *stream);
 int nunif_hip_png_debug_codes(const void *src, int32_t form, int32_t B, int32_t H, int32_t W, int32_t stripe_rows, int32_t *hist,
                               int32_t *lengths, void *workspace, void *stream);
+int nunif_hip_png_encode_planes(const float *colour, const float *alpha, int32_t colour_channels, int32_t form, int32_t B, int32_t H,
+                                int32_t W, int32_t stripe_rows, uint8_t *out, int64_t capacity, int32_t *out_len, void *workspace,
+                                void *stream);
+int nunif_hip_png_debug_filtered_planes(const float *colour, const float *alpha, int32_t colour_channels, int32_t form, int32_t B,
+                                        int32_t H, int32_t W, uint8_t *filtered, void *stream);
 
 /* Test hooks (tests/ only): snapshot every stage's NHWC fp16 output during the next forward calls, then read
  * them back one by one (returns 1 past the last tap).  Names match oracle.swin_unet.unet_forward(taps=...). */

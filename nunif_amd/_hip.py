@@ -208,6 +208,8 @@ SIGNATURES = {
     "nunif_hip_png_encode": (c_int32, [c_void_p] + [c_int32] * 5 + [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "nunif_hip_png_debug_filtered": (c_int32, [c_void_p] + [c_int32] * 4 + [c_void_p, c_void_p]),
     "nunif_hip_png_debug_codes": (c_int32, [c_void_p] + [c_int32] * 5 + [c_void_p] * 4),
+    "nunif_hip_png_encode_planes": (c_int32, [c_void_p, c_void_p] + [c_int32] * 6 + [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "nunif_hip_png_debug_filtered_planes": (c_int32, [c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p, c_void_p]),
     "nunif_hip_hdr2sdr": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, ctypes.POINTER(Hdr2SdrParams), c_int32,
                                     c_void_p]),
     "nunif_hip_hdr2sdr_constants": (c_int32, [c_int32, c_int32, ctypes.POINTER(Hdr2SdrParams), ctypes.POINTER(c_float),

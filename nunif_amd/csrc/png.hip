@@ -2,7 +2,7 @@
 // save_image, iw3/base_depth_model.py:197-210 save_normalized_depth, reference), as five launches on one stream and no host
 // synchronisation.  DESIGN.md ("PNG frame encoder") states the stream; tests/png_ref.py restates it from the specifications.
 //
-//   png_filter_kernel<FORM>  one wave per row: quantise, try the five filter types, keep the one with the smallest sum of
+//   png_filter_kernel<FORM>  (png_filter.h; the forms 4..6 are instantiated in png_planes.hip) one wave per row: quantise, try the five filter types, keep the one with the smallest sum of
 //                            |byte as signed| (the lowest type on a tie), write the filtered row and its two Adler sums
 //   png_hist_kernel          one workgroup per stripe, 4 096 filtered bytes per pass (16 per lane, one 16-byte load): the bytes
 //                            that repeat the byte one pixel before them, the run position of every byte by a scan carried from
@@ -20,13 +20,14 @@
 // disjoint bits: the bytes depend on the input alone.  Every store is checked against the size it was promised.
 #include "common.h"
 #include "png_host.h"
+#include "png_filter.h"
 
 namespace nunif {
 namespace {
 
 using namespace png;
+using namespace png_dev;
 
-constexpr int kThreads = 256;
 constexpr int kPass = kThreads * 16;                             // filtered bytes per pass of a stripe's workgroup
 constexpr int kAhead = 17;                                       // 16-byte groups read past a pass: a match of 258 needs 257 + 1
 constexpr int kEqWords = kThreads + 32;                          // 16 "repeats" bits per lane, the look-ahead, zero fill
@@ -41,121 +42,6 @@ __device__ const uint16_t kLenBaseDev[29] = {3,  4,  5,  6,  7,  8,  9,  10, 11,
                                              31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
 __device__ const uint8_t kLenExtraDev[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
 __device__ const uint8_t kClOrderDev[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-
-struct Frame {
-    int B, H, W, form, bpp, stripe_rows, stripes;
-    long row, stripe_stride;
-};
-
-// ---- quantise, filter ----------------------------------------------------------------------------------------------------------------
-struct Px {
-    int c[3];
-};
-
-template <int FORM>
-__device__ __forceinline__ Px load_px(const void *src, long b, int y, int x, int H, int W) {
-    Px p;
-    if (x < 0 || y < 0) {
-        p.c[0] = p.c[1] = p.c[2] = 0;
-        return p;
-    }
-    if (FORM == kRgb8F32) {
-        const float *f = static_cast<const float *>(src) + (b * 3 * H + y) * (long)W + x;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) p.c[k] = (int)rintf(fminf(fmaxf(f[(long)k * H * W], 0.f), 1.f) * 255.f);
-    } else if (FORM == kRgb8U8) {
-        const uint8_t *u = static_cast<const uint8_t *>(src) + ((b * H + y) * (long)W + x) * 3;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) p.c[k] = u[k];
-    } else {
-        const float d = static_cast<const float *>(src)[(b * H + y) * (long)W + x];
-        const unsigned v = (unsigned)(65535.f * fminf(fmaxf(d, 0.f), 1.f));
-        p.c[0] = (int)(v >> 8);
-        p.c[1] = (int)(v & 255u);
-        p.c[2] = 0;
-    }
-    return p;
-}
-
-__device__ __forceinline__ int paeth(int a, int b, int c) {
-    const int p = a + b - c, pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
-    return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
-}
-__device__ __forceinline__ int filtered(int type, int x, int a, int b, int c) {
-    int pred = 0;
-    if (type == 1) pred = a;
-    else if (type == 2) pred = b;
-    else if (type == 3) pred = (a + b) >> 1;
-    else if (type == 4) pred = paeth(a, b, c);
-    return (x - pred) & 255;
-}
-__device__ __forceinline__ int signed_abs(int v) { return v < 128 ? v : 256 - v; }
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
-// out: the filtered bytes; row r of frame b at out + b * frame_stride + (r / stripe_rows) * stripe_stride + (r % stripe_rows) * row
-template <int FORM>
-__global__ void __launch_bounds__(kThreads) png_filter_kernel(const void *__restrict__ src, uint8_t *__restrict__ out,
-                                                               uint32_t *__restrict__ rowsum, const Frame f, long frame_stride) {
-    constexpr int BPP = FORM == kGray16F32 ? 2 : 3;
-    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const long b = blockIdx.y;
-    if (r >= f.H) return;
-    int cost[5] = {0, 0, 0, 0, 0};
-    for (int x = lane; x < f.W; x += 64) {
-        const Px cur = load_px<FORM>(src, b, r, x, f.H, f.W), left = load_px<FORM>(src, b, r, x - 1, f.H, f.W);
-        const Px up = load_px<FORM>(src, b, r - 1, x, f.H, f.W), ul = load_px<FORM>(src, b, r - 1, r > 0 ? x - 1 : -1, f.H, f.W);
-#pragma unroll
-        for (int k = 0; k < BPP; ++k)
-#pragma unroll
-            for (int t = 0; t < 5; ++t) cost[t] += signed_abs(filtered(t, cur.c[k], left.c[k], up.c[k], ul.c[k]));
-    }
-    int best = 0, best_cost = 0;
-#pragma unroll
-    for (int t = 0; t < 5; ++t) {
-        const int c = wave_sum(cost[t]);
-        if (t == 0 || c < best_cost) {                           // the lowest type on a tie
-            best = t;
-            best_cost = c;
-        }
-    }
-    uint8_t *dst = out + b * frame_stride + (long)(r / f.stripe_rows) * f.stripe_stride + (long)(r % f.stripe_rows) * f.row;
-    unsigned long long sa = 0, sb = 0;                           // sum of d[i] and of (row - i) d[i]
-    if (lane == 0) {
-        dst[0] = (uint8_t)best;
-        sa = (unsigned)best;
-        sb = (unsigned long long)f.row * (unsigned)best;
-    }
-    for (int x = lane; x < f.W; x += 64) {
-        const Px cur = load_px<FORM>(src, b, r, x, f.H, f.W), left = load_px<FORM>(src, b, r, x - 1, f.H, f.W);
-        const Px up = load_px<FORM>(src, b, r - 1, x, f.H, f.W), ul = load_px<FORM>(src, b, r - 1, r > 0 ? x - 1 : -1, f.H, f.W);
-#pragma unroll
-        for (int k = 0; k < BPP; ++k) {
-            const long i = 1 + (long)x * BPP + k;
-            const int v = filtered(best, cur.c[k], left.c[k], up.c[k], ul.c[k]);
-            dst[i] = (uint8_t)v;
-            sa += (unsigned)v;
-            sb += (unsigned long long)(f.row - i) * (unsigned)v;
-        }
-    }
-    if (rowsum) {
-        sa = wave_sum64(sa);
-        sb = wave_sum64(sb);
-        if (lane == 0) {
-            rowsum[(b * f.H + r) * 2] = (uint32_t)(sa % 65521u);
-            rowsum[(b * f.H + r) * 2 + 1] = (uint32_t)(sb % 65521u);
-        }
-    }
-}
 
 // ---- the token walk ------------------------------------------------------------------------------------------------------------------
 // A byte "repeats" when it equals the byte one pixel before it in the same stripe.  Let k be the number of repeating bytes that end
@@ -190,7 +76,7 @@ __device__ __forceinline__ int ones_from(const uint16_t *eq, int p, int cap) {
 
 struct StripeWalk {
     const uint8_t *d;                                            // the stripe's filtered bytes, 16-byte aligned
-    int n;                                                       // how many (a stripe holds at most 8 192 x 24 577 bytes)
+    int n;                                                       // how many (a stripe holds at most 8 192 x 32 769 bytes)
     int bpp;
     int carry;                                                   // repeating bytes that end right before this pass
 };
@@ -202,15 +88,18 @@ __device__ __forceinline__ unsigned repeats16(const StripeWalk &w, int off, uint
     if (off < w.n) {
         q = *reinterpret_cast<const uint4 *>(w.d + off);          // the slot is padded to 16 bytes
         const uint32_t before = off > 0 ? *reinterpret_cast<const uint32_t *>(w.d + off - 4) : 0u;
-        const uint32_t wd[5] = {before, q.x, q.y, q.z, q.w};
+        const uint32_t wd[5] = {before, q.x, q.y, q.z, q.w};      // 20 bytes; the bytes of this lane start at byte 4
         const int valid = min(16, w.n - off);
+        const int back = 8 * (4 - w.bpp);                        // bpp 1..4: the 16 bytes one pixel back start at byte 4 - bpp
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const unsigned cur = (wd[1 + (i >> 2)] >> (8 * (i & 3))) & 255u;                   // wd holds 20 bytes; cur is byte 4 + i
-            const unsigned prev2 = (wd[(2 + i) >> 2] >> (8 * ((2 + i) & 3))) & 255u;
-            const unsigned prev3 = (wd[(1 + i) >> 2] >> (8 * ((1 + i) & 3))) & 255u;
-            const unsigned prev = w.bpp == 3 ? prev3 : prev2;
-            if (i < valid && off + i >= w.bpp && cur == prev) mask |= 1u << i;
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t pw = (uint32_t)((((unsigned long long)wd[k + 1] << 32) | wd[k]) >> back);
+            const uint32_t diff = wd[k + 1] ^ pw;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int i = 4 * k + j;
+                if (i < valid && off + i >= w.bpp && ((diff >> (8 * j)) & 255u) == 0u) mask |= 1u << i;
+            }
         }
     }
     if (bytes) *bytes = q;
@@ -885,11 +774,13 @@ Frame make_frame(int B, int H, int W, int form, int stripe_rows, const Workspace
     return f;
 }
 
-int launch_filter(const void *src, const Frame &f, uint8_t *filt, uint32_t *rowsum, long frame_stride, hipStream_t s) {
+int launch_filter(const void *src, const Planes &pl, const Frame &f, uint8_t *filt, uint32_t *rowsum, long frame_stride,
+                  hipStream_t s) {
     const dim3 grid(cdiv(f.H, 4), f.B);
-    if (f.form == kRgb8F32) png_filter_kernel<kRgb8F32><<<grid, kThreads, 0, s>>>(src, filt, rowsum, f, frame_stride);
-    else if (f.form == kRgb8U8) png_filter_kernel<kRgb8U8><<<grid, kThreads, 0, s>>>(src, filt, rowsum, f, frame_stride);
-    else png_filter_kernel<kGray16F32><<<grid, kThreads, 0, s>>>(src, filt, rowsum, f, frame_stride);
+    if (f.form == kRgb8F32) png_filter_kernel<kRgb8F32><<<grid, kThreads, 0, s>>>(src, pl, filt, rowsum, f, frame_stride);
+    else if (f.form == kRgb8U8) png_filter_kernel<kRgb8U8><<<grid, kThreads, 0, s>>>(src, pl, filt, rowsum, f, frame_stride);
+    else if (f.form == kGray16F32) png_filter_kernel<kGray16F32><<<grid, kThreads, 0, s>>>(src, pl, filt, rowsum, f, frame_stride);
+    else return launch_filter_planes(src, pl, f, filt, rowsum, frame_stride, s);
     NUNIF_LAUNCH_CHECK();
     return NUNIF_HIP_OK;
 }
@@ -914,10 +805,10 @@ Parts parts(void *workspace, const Workspace &ws) {
 }
 
 // launches 1 to 3: filtered bytes, histograms, codes
-int launch_front(const void *src, const Frame &f, const Workspace &ws, const Parts &p, hipStream_t s) {
+int launch_front(const void *src, const Planes &pl, const Frame &f, const Workspace &ws, const Parts &p, hipStream_t s) {
     {
         ProfScope prof("png_filter", s, 0.0, 0.0);
-        if (int e = launch_filter(src, f, p.filt, p.rowsum, (long)f.stripes * ws.stripe_stride, s)) return e;
+        if (int e = launch_filter(src, pl, f, p.filt, p.rowsum, (long)f.stripes * ws.stripe_stride, s)) return e;
     }
     {
         ProfScope prof("png_hist", s, 0.0, 0.0);
@@ -933,9 +824,75 @@ int launch_front(const void *src, const Frame &f, const Workspace &ws, const Par
 int check_frame(const char *who, const void *src, int B, int H, int W, int form, int stripe_rows) {
     NUNIF_REQUIRE(src, "%s: NULL frame", who);
     NUNIF_REQUIRE(valid_frame(B, H, W, form, stripe_rows),
-                  "%s: B=%d H=%d W=%d form=%d stripe_rows=%d is outside 1 <= B <= %d, 1 <= H, W <= %d, form 0 | 1 | 2, "
+                  "%s: B=%d H=%d W=%d form=%d stripe_rows=%d is outside 1 <= B <= %d, 1 <= H, W <= %d, form 0 | 1 | 2 | 4 | 5 | 6, "
                   "1 <= stripe_rows <= H", who, B, H, W, form, stripe_rows, kMaxBatch, kMaxDim);
     return NUNIF_HIP_OK;
+}
+
+// the entries that take one source pointer: forms 0..2
+int check_single(const char *who, const void *src, int B, int H, int W, int form, int stripe_rows) {
+    if (int e = check_frame(who, src, B, H, W, form, stripe_rows)) return e;
+    NUNIF_REQUIRE(!planes_form(form), "%s: form %d takes its colour and alpha planes through %s_planes", who, form, who);
+    return NUNIF_HIP_OK;
+}
+
+// the entries that take the colour planes and the alpha plane apart: forms 4..6
+int check_planes(const char *who, const float *colour, const float *alpha, int channels, int B, int H, int W, int form,
+                 int stripe_rows, Planes *pl) {
+    if (int e = check_frame(who, colour, B, H, W, form, stripe_rows)) return e;
+    NUNIF_REQUIRE(planes_form(form), "%s: form %d is not one of 4 (RGBA 8), 5 (grey 8), 6 (grey + alpha 8)", who, form);
+    NUNIF_REQUIRE(form == kRgba8F32 ? channels == 3 : (channels == 1 || channels == 3),
+                  "%s: form %d with %d colour planes (RGBA takes 3, the grey forms 1 or 3)", who, form, channels);
+    NUNIF_REQUIRE(has_alpha(form) ? alpha != nullptr : alpha == nullptr, "%s: form %d %s", who, form,
+                  has_alpha(form) ? "needs an alpha plane" : "has no alpha: pass NULL");
+    pl->alpha = alpha;
+    pl->channels = channels;
+    pl->colour_stride = (long)channels * H * W;
+    pl->alpha_stride = (long)H * W;
+    return NUNIF_HIP_OK;
+}
+
+const Planes kNoPlanes = {nullptr, 0, 0, 0};
+
+// One tensor [B][channels + 1][H][W] that holds the colour planes (3 for RGBA, 1 for the grey forms) and then the alpha plane:
+// how debug_codes, which has one source pointer, receives forms 4..6
+Planes packed_planes(const void *src, int form, int H, int W) {
+    if (!planes_form(form)) return kNoPlanes;
+    Planes pl;
+    pl.channels = form == kRgba8F32 ? 3 : 1;
+    const long planes = pl.channels + (has_alpha(form) ? 1 : 0);
+    pl.colour_stride = pl.alpha_stride = planes * H * W;
+    pl.alpha = has_alpha(form) ? static_cast<const float *>(src) + (long)pl.channels * H * W : nullptr;
+    return pl;
+}
+
+int encode_frames(const char *who, const void *src, const Planes &pl, int form, int B, int H, int W, int stripe_rows, uint8_t *out,
+                  int64_t capacity, int32_t *out_len, void *workspace, void *stream) {
+    NUNIF_REQUIRE(out && out_len && capacity >= 0, "%s: NULL output or negative capacity", who);
+    NUNIF_REQUIRE(workspace && aligned256(workspace), "%s: the workspace must be 256-byte aligned", who);
+    hipStream_t s = (hipStream_t)stream;
+    const png::Workspace ws = png::workspace(B, H, W, form, stripe_rows);
+    const Frame f = make_frame(B, H, W, form, stripe_rows, ws);
+    const Parts p = parts(workspace, ws);
+    if (int e = launch_front(src, pl, f, ws, p, s)) return e;
+    {
+        ProfScope prof("png_scan", s, 0.0, 0.0);
+        png_scan_kernel<<<B, kThreads, 0, s>>>(p.meta, p.rowsum, p.frame, f, out, (long)capacity, out_len);
+        NUNIF_LAUNCH_CHECK();
+    }
+    ProfScope prof("png_emit", s, 0.0, 0.0);
+    png_emit_kernel<<<dim3(f.stripes, B), kThreads, 0, s>>>(p.filt, p.codes, p.header, p.meta, p.frame, f, out, (long)capacity,
+                                                           out_len);
+    NUNIF_LAUNCH_CHECK();
+    return NUNIF_HIP_OK;
+}
+
+int filtered_frames(const void *src, const Planes &pl, int form, int B, int H, int W, uint8_t *filtered, void *stream) {
+    // one stripe of H rows and no padding: the rows of a frame, and the frames, lie one behind the other
+    png::Workspace ws = png::workspace(B, H, W, form, H);
+    ws.stripe_stride = png::geometry(H, W, form, H).stripe_bytes;
+    const Frame f = make_frame(B, H, W, form, H, ws);
+    return launch_filter(src, pl, f, filtered, nullptr, (long)ws.stripe_stride, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -962,35 +919,31 @@ extern "C" int64_t nunif_hip_png_workspace_bytes(int32_t B, int32_t H, int32_t W
 
 extern "C" int nunif_hip_png_encode(const void *src, int32_t form, int32_t B, int32_t H, int32_t W, int32_t stripe_rows, uint8_t *out,
                                     int64_t capacity, int32_t *out_len, void *workspace, void *stream) {
-    if (int e = check_frame("png_encode", src, B, H, W, form, stripe_rows)) return e;
-    NUNIF_REQUIRE(out && out_len && capacity >= 0, "png_encode: NULL output or negative capacity");
-    NUNIF_REQUIRE(workspace && aligned256(workspace), "png_encode: the workspace must be 256-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    const png::Workspace ws = png::workspace(B, H, W, form, stripe_rows);
-    const Frame f = make_frame(B, H, W, form, stripe_rows, ws);
-    const Parts p = parts(workspace, ws);
-    if (int e = launch_front(src, f, ws, p, s)) return e;
-    {
-        ProfScope prof("png_scan", s, 0.0, 0.0);
-        png_scan_kernel<<<B, kThreads, 0, s>>>(p.meta, p.rowsum, p.frame, f, out, (long)capacity, out_len);
-        NUNIF_LAUNCH_CHECK();
-    }
-    ProfScope prof("png_emit", s, 0.0, 0.0);
-    png_emit_kernel<<<dim3(f.stripes, B), kThreads, 0, s>>>(p.filt, p.codes, p.header, p.meta, p.frame, f, out, (long)capacity,
-                                                           out_len);
-    NUNIF_LAUNCH_CHECK();
-    return NUNIF_HIP_OK;
+    if (int e = check_single("png_encode", src, B, H, W, form, stripe_rows)) return e;
+    return encode_frames("png_encode", src, kNoPlanes, form, B, H, W, stripe_rows, out, capacity, out_len, workspace, stream);
+}
+
+extern "C" int nunif_hip_png_encode_planes(const float *colour, const float *alpha, int32_t colour_channels, int32_t form, int32_t B,
+                                           int32_t H, int32_t W, int32_t stripe_rows, uint8_t *out, int64_t capacity,
+                                           int32_t *out_len, void *workspace, void *stream) {
+    Planes pl;
+    if (int e = check_planes("png_encode_planes", colour, alpha, colour_channels, B, H, W, form, stripe_rows, &pl)) return e;
+    return encode_frames("png_encode_planes", colour, pl, form, B, H, W, stripe_rows, out, capacity, out_len, workspace, stream);
 }
 
 extern "C" int nunif_hip_png_debug_filtered(const void *src, int32_t form, int32_t B, int32_t H, int32_t W, uint8_t *filtered,
                                             void *stream) {
-    if (int e = check_frame("png_debug_filtered", src, B, H, W, form, 1)) return e;
+    if (int e = check_single("png_debug_filtered", src, B, H, W, form, 1)) return e;
     NUNIF_REQUIRE(filtered, "png_debug_filtered: NULL output");
-    // one stripe of H rows and no padding: the rows of a frame, and the frames, lie one behind the other
-    png::Workspace ws = png::workspace(B, H, W, form, H);
-    ws.stripe_stride = png::geometry(H, W, form, H).stripe_bytes;
-    const Frame f = make_frame(B, H, W, form, H, ws);
-    return launch_filter(src, f, filtered, nullptr, (long)ws.stripe_stride, (hipStream_t)stream);
+    return filtered_frames(src, kNoPlanes, form, B, H, W, filtered, stream);
+}
+
+extern "C" int nunif_hip_png_debug_filtered_planes(const float *colour, const float *alpha, int32_t colour_channels, int32_t form,
+                                                   int32_t B, int32_t H, int32_t W, uint8_t *filtered, void *stream) {
+    Planes pl;
+    if (int e = check_planes("png_debug_filtered_planes", colour, alpha, colour_channels, B, H, W, form, 1, &pl)) return e;
+    NUNIF_REQUIRE(filtered, "png_debug_filtered_planes: NULL output");
+    return filtered_frames(colour, pl, form, B, H, W, filtered, stream);
 }
 
 extern "C" int nunif_hip_png_debug_codes(const void *src, int32_t form, int32_t B, int32_t H, int32_t W, int32_t stripe_rows,
@@ -1002,7 +955,7 @@ extern "C" int nunif_hip_png_debug_codes(const void *src, int32_t form, int32_t 
     const png::Workspace ws = png::workspace(B, H, W, form, stripe_rows);
     const Frame f = make_frame(B, H, W, form, stripe_rows, ws);
     const Parts p = parts(workspace, ws);
-    if (int e = launch_front(src, f, ws, p, s)) return e;
+    if (int e = launch_front(src, packed_planes(src, form, H, W), f, ws, p, s)) return e;
     const size_t bytes = (size_t)B * f.stripes * png::kSymbolStride * 4;
     NUNIF_HIP_CHECK(hipMemcpyAsync(hist, p.hist, bytes, hipMemcpyDeviceToDevice, s));
     NUNIF_HIP_CHECK(hipMemcpyAsync(lengths, p.lens, bytes, hipMemcpyDeviceToDevice, s));

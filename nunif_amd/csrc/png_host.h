@@ -10,7 +10,8 @@ namespace png {
 
 constexpr int kMaxDim = 8192;            // H and W
 constexpr int kMaxBatch = 16;
-enum Form { kRgb8F32 = 0, kRgb8U8 = 1, kGray16F32 = 2 };
+// 3 is refused (it never named a form); 4..6 take planar fp32 colour and, where the form has one, a separate fp32 alpha plane
+enum Form { kRgb8F32 = 0, kRgb8U8 = 1, kGray16F32 = 2, kRgba8F32 = 4, kGray8F32 = 5, kGrayA8F32 = 6 };
 
 constexpr int kNumLit = 286, kNumDist = 30, kNumCl = 19;
 constexpr int kSymbols = kNumLit + kNumDist + kNumCl;        // 335: one stripe's histogram or code lengths, in this order
@@ -26,8 +27,19 @@ constexpr uint8_t kLenExtra[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 
 // RFC 1951 section 3.2.7: the order in which the code lengths of the code-length alphabet are sent
 constexpr uint8_t kClOrder[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
 
-inline bool valid_form(int form) { return form == kRgb8F32 || form == kRgb8U8 || form == kGray16F32; }
-inline int bytes_per_pixel(int form) { return form == kGray16F32 ? 2 : 3; }
+inline bool valid_form(int form) {
+    return form == kRgb8F32 || form == kRgb8U8 || form == kGray16F32 || form == kRgba8F32 || form == kGray8F32 || form == kGrayA8F32;
+}
+inline bool planes_form(int form) { return form == kRgba8F32 || form == kGray8F32 || form == kGrayA8F32; }
+inline bool has_alpha(int form) { return form == kRgba8F32 || form == kGrayA8F32; }
+inline int bytes_per_pixel(int form) {
+    return form == kRgba8F32 ? 4 : form == kGray8F32 ? 1 : (form == kGray16F32 || form == kGrayA8F32) ? 2 : 3;
+}
+// IHDR: bit depth and colour type (0 grey, 2 RGB, 4 grey + alpha, 6 RGB + alpha)
+inline int bit_depth(int form) { return form == kGray16F32 ? 16 : 8; }
+inline int colour_type(int form) {
+    return form == kRgba8F32 ? 6 : form == kGrayA8F32 ? 4 : (form == kGray16F32 || form == kGray8F32) ? 0 : 2;
+}
 inline bool valid_frame(int64_t B, int64_t H, int64_t W, int form, int64_t stripe_rows) {
     return B >= 1 && B <= kMaxBatch && H >= 1 && H <= kMaxDim && W >= 1 && W <= kMaxDim && valid_form(form) &&
            stripe_rows >= 1 && stripe_rows <= H;
@@ -157,7 +169,7 @@ struct ByteSink {
     void crc_since(int64_t from) { const uint32_t c = ok ? crc32(p + from, n - from) : 0u; u32(c); }
 };
 
-// The PNG signature, IHDR (8-bit RGB or 16-bit grey, deflate, adaptive filtering, no interlace) and one tEXt chunk per entry
+// The PNG signature, IHDR (bit depth and colour type of the form, deflate, adaptive filtering, no interlace) and one tEXt chunk per entry
 // (keyword 1..79 bytes, a zero byte, the text) into out[capacity]; returns the length, -1 for arguments the encoder refuses,
 // -2 where the capacity is too small.
 inline int64_t header(int H, int W, int form, const char *const *keys, const char *const *values, int n_text, uint8_t *out,
@@ -175,7 +187,7 @@ inline int64_t header(int H, int W, int form, const char *const *keys, const cha
     int64_t from = s.n;
     s.bytes("IHDR", 4);
     s.u32((uint32_t)W); s.u32((uint32_t)H);
-    s.u8(form == kGray16F32 ? 16 : 8); s.u8(form == kGray16F32 ? 0 : 2); s.u8(0); s.u8(0); s.u8(0);
+    s.u8(bit_depth(form)); s.u8(colour_type(form)); s.u8(0); s.u8(0); s.u8(0);
     s.crc_since(from);
     for (int i = 0; i < n_text; ++i) {
         const int64_t k = (int64_t)std::strlen(keys[i]), v = (int64_t)std::strlen(values[i]);
