@@ -700,6 +700,20 @@ int nunif_hip_tensor_to_yuv(const float *src, int32_t H, int32_t W, int32_t form
 int nunif_hip_pixfmt_constants(int32_t matrix, int32_t full_range, int32_t bits, int32_t direction, float *coefficients,
                                float *offsets);
 
+/* HDR video that enters as YUV planes (nunif_amd/csrc/hdr_planes.hip): what hdr2sdr (nunif/utils/video.py:309-416) and the to_tensor
+ * behind it make of a decoded BT.2020 PQ / HLG frame, from the decoder's planes in ONE launch.  The reference's rgb48 step
+ * frame.to_ndarray(format="rgb48le") (:322-325, host libswscale; the reference asserts colorspace == BT2020, :318) is yuv_to_tensor's
+ * arithmetic with the bt2020 matrix, rounded to the 16-bit codes its `frame` output holds; the map (:327-398) is hdr2sdr's; form 1
+ * is to_tensor (:218-223) of the mapped frame.  The result is bit-equal to nunif_hip_yuv_to_tensor(format 2, matrix 2020, frame =
+ * rgb48) followed by nunif_hip_hdr2sdr on that frame; the rgb48 frame itself never exists.
+ * format: must be 2 (yuv420p10le); the matrix is bt2020 by definition; full_range 0 / 1; trc 16 (PQ) or 18 (HLG); colorspace 709 or
+ * 601; 1 <= H, W <= 8192; params and form (0 u16 HWC, 1 chw fp32, 2 debug HWC fp32) as for nunif_hip_hdr2sdr; planes as for
+ * nunif_hip_yuv_to_tensor (device or pinned host memory, byte pitches, padding never read past a row's samples).  Anything else —
+ * formats 0 / 1, a null plane, a pitch shorter than its row — is refused with NUNIF_HIP_EINVAL and nothing is launched. */
+int nunif_hip_yuv_hdr_to_tensor(const nunif_pixfmt_planes *src, int32_t format, int32_t H, int32_t W, int32_t full_range,
+                                int32_t trc, int32_t colorspace, const nunif_hdr2sdr_params *params, int32_t form,
+                                void *dst, void *stream);
+
 /* cliqa's image-quality nets and patch selection (nunif_amd/csrc/cliqa.hip), eval mode, fp16 operands with fp32 accumulation
  * (the reference runs them under fp16 autocast, cliqa/utils.py:65,78,91), NHWC fp16 maps.
  * create replaces the constructors and eval-mode BatchNorm of cliqa/models/jpeg_quality.py JPEGQuality :8-41 (kind 0),

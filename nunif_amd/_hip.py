@@ -217,6 +217,8 @@ SIGNATURES = {
     "nunif_hip_yuv_to_tensor": (c_int32, [ctypes.POINTER(PixfmtPlanes)] + [c_int32] * 6 + [c_void_p, c_void_p, c_void_p]),
     "nunif_hip_tensor_to_yuv": (c_int32, [c_void_p] + [c_int32] * 5 + [ctypes.POINTER(PixfmtPlanes), c_void_p]),
     "nunif_hip_pixfmt_constants": (c_int32, [c_int32] * 4 + [ctypes.POINTER(c_float), ctypes.POINTER(c_float)]),
+    "nunif_hip_yuv_hdr_to_tensor": (c_int32, [ctypes.POINTER(PixfmtPlanes)] + [c_int32] * 6 + [ctypes.POINTER(Hdr2SdrParams), c_int32,
+                                                                                                c_void_p, c_void_p]),
     "nunif_hip_cliqa_create": (c_int32, [ctypes.POINTER(TensorDesc), c_int32, c_int32, ctypes.POINTER(c_void_p)]),
     "nunif_hip_cliqa_destroy": (None, [c_void_p]),
     "nunif_hip_cliqa_workspace_bytes": (c_int64, [c_void_p] + [c_int32] * 4),

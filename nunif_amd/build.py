@@ -32,7 +32,9 @@ EXTRA_FLAGS = {"stitch.hip": ["-ffp-contract=off"], "iw3_warp.hip": ["-ffp-contr
                # hdr.hip: the reference's fp32 expressions operation by operation (its error is the tests' yardstick)
                "hdr.hip": ["-ffp-contract=off"] + NO_SLP,
                # pixfmt.hip: every multiply and add is one rounding, in the order tests/pixfmt_ref.py states them
-               "pixfmt.hip": ["-ffp-contract=off"] + NO_SLP}
+               "pixfmt.hip": ["-ffp-contract=off"] + NO_SLP,
+               # hdr_planes.hip: the gather of pixfmt.hip and the map of hdr.hip in one kernel, bit-equal to the two in a row
+               "hdr_planes.hip": ["-ffp-contract=off"] + NO_SLP}
 
 
 def sources():

@@ -61,13 +61,15 @@ class PipelineOps:
     """Device functions used by the scheduler.  Defaults: the HIP engine (``nunif_amd.iw3.utils``)."""
 
     def __init__(self, to_tensor=None, preprocess_image=None, apply_divergence=None, apply_rgbd=None,
-                 postprocess_image=None, to_frame=None,
+                 postprocess_image=None, to_frame=None, hdr=None,
                  in_format=None, in_matrix="bt709", in_full_range=False,
                  out_format=None, out_matrix="bt709", out_full_range=False):
         """``in_format`` / ``in_matrix`` / ``in_full_range``: the frames going in are the decoder's planes (``frame.data`` is a
         pair ``(flat uint8 array or tensor, pixfmt.PlaneLayout)`` of that format) and ``to_tensor`` is the engine's planar entry;
         ``out_format`` / ``out_matrix`` / ``out_full_range``: a stereo pair leaves as the encoder's planes (a flat uint8 tensor in
-        ``out_layout(h, w)``) instead of an HWC frame.  By default both ends are rgb, as before."""
+        ``out_layout(h, w)``) instead of an HWC frame.  By default both ends are rgb, as before.  ``hdr``: an entry from
+        ``nunif_amd.nunif.utils.hdr.hdr_entry`` — the planes are those of a BT.2020 PQ / HLG source and the planar entry tone-maps
+        them in the same launch; only with ``in_format="yuv420p10le"`` and ``in_matrix="bt2020"``."""
         from . import utils as U
         from ..nunif.utils import pixfmt
         for name, fmt, matrix in (("in", in_format, in_matrix), ("out", out_format, out_matrix)):
@@ -79,6 +81,12 @@ class PipelineOps:
             raise ValueError("PipelineOps: in_format= replaces to_tensor; pass one of them")
         if out_format is not None and to_frame is not None:
             raise ValueError("PipelineOps: out_format= replaces to_frame; pass one of them")
+        if hdr is not None:
+            from ..nunif.utils import hdr as hdr_utils
+            refusal = hdr_utils.planar_entry_refusal(pixfmt._ALIASES.get(in_format, in_format), in_matrix, hdr)
+            if refusal:
+                raise ValueError(f"PipelineOps: {refusal}")
+        self.hdr = hdr
         self.in_format, self.in_matrix = pixfmt._ALIASES.get(in_format, in_format), in_matrix
         self.in_full_range = bool(in_full_range) or (in_format or "").startswith("yuvj")
         self.out_format, self.out_matrix = pixfmt._ALIASES.get(out_format, out_format), out_matrix
@@ -104,7 +112,7 @@ class PipelineOps:
         ``configure_colorspace`` then records ``config.state["engine_pixfmt"]``, the six format options are taken from there at
         the first frame: the scheduler is handed the decoder's frames and returns the encoder's planes."""
         from ..nunif.utils.video import declare_engine_callback
-        fixed = not self._own_edges or self.in_format is not None or self.out_format is not None
+        fixed = not self._own_edges or self.in_format is not None or self.out_format is not None or self.hdr is not None
         self._config = config if declare_engine_callback(config, vf=vf, turns=fixed) else None
 
     def _settle(self):
@@ -169,7 +177,12 @@ class PipelineOps:
             slot = self._pinned_slot(layout.nbytes)
             np.copyto(slot[0].numpy()[:layout.nbytes], host[:layout.nbytes])
             buf = slot[0]
-        x = pixfmt.yuv_to_tensor(buf, layout, self.in_matrix, self.in_full_range, device=device)
+        if self.hdr is not None:
+            from ..nunif.utils import hdr as hdr_utils
+            x = hdr_utils.hdr2sdr_planes(buf, layout, self.in_full_range, self.hdr.color_trc, self.hdr.output_colorspace,
+                                         form="chw", device=device, **self.hdr.params)
+        else:
+            x = pixfmt.yuv_to_tensor(buf, layout, self.in_matrix, self.in_full_range, device=device)
         if slot is not None:
             slot[1] = torch.cuda.Event()
             slot[1].record(torch.cuda.current_stream(x.device))

@@ -15,6 +15,7 @@ import torch
 from ..frame_ring import FrameRing
 from ..iw3 import _ops
 from ..iw3.frame_pipeline import pix_fmt_requires_16bit
+from ..nunif.utils import hdr as hdr_utils
 from ..nunif.utils import pixfmt, rgb_noise
 
 
@@ -40,10 +41,12 @@ class Waifu2xVideoStream:
         that rule.  The depth of the frames going in is each frame's own (uint8 or uint16), as in ``VU.to_tensor``.  ``hdr``: an
         entry from ``nunif_amd.nunif.utils.hdr.hdr_entry`` — the frames going in are then the rgb48 frames of a BT.2020 PQ / HLG
         source as decoded, and the tone mapping of ``VU.hdr2sdr`` is the ring's entry step (not together with a quarter turn).
+        Together with ``in_format="yuv420p10le"`` and ``in_matrix="bt2020"`` the frames going in are that source's planes instead,
+        and the entry step is the fused ``hdr.hdr_yuv_entry`` built from the entry's curve, colorspace and parameters.
 
         ``in_format`` (``yuv420p`` / ``yuv444p`` / ``yuv420p10le`` or a ``yuvj*`` alias, with ``in_matrix`` and ``in_full_range``):
         the frames going in are the decoder's planes, each a pair ``(flat uint8 array, pixfmt.PlaneLayout)``, and the conversion
-        to rgb is the ring's entry step (``nunif_amd.nunif.utils.pixfmt``; not with a quarter turn, not with ``hdr``).
+        to rgb is the ring's entry step (``nunif_amd.nunif.utils.pixfmt``; not with a quarter turn; with ``hdr`` in the one form above).
         ``out_format`` (with ``out_matrix`` / ``out_full_range``): the frames coming out are the encoder's planes, flat uint8
         arrays in ``self.out_layout``; the film grain then runs as launches of its own in front of the conversion."""
         self.ctx, self.args = ctx, args
@@ -85,7 +88,9 @@ class Waifu2xVideoStream:
             raise ValueError("Waifu2xVideoStream: in_format= cannot be combined with --rotate-left / --rotate-right: the planar "
                              "entry has no quarter turn; pass rgb frames")
         if in_format is not None and self.hdr is not None:
-            raise ValueError("Waifu2xVideoStream: in_format= and hdr= exclude each other: an HDR source goes through hdr2sdr")
+            refusal = hdr_utils.planar_entry_refusal(pixfmt._ALIASES.get(in_format, in_format), in_matrix, self.hdr)
+            if refusal:
+                raise ValueError(f"Waifu2xVideoStream: {refusal}")
         self.in_format, self.in_matrix = pixfmt._ALIASES.get(in_format, in_format), in_matrix
         self.in_full_range = bool(in_full_range) or (in_format or "").startswith("yuvj")
         self.out_format, self.out_matrix = pixfmt._ALIASES.get(out_format, out_format), out_matrix
@@ -167,7 +172,13 @@ class Waifu2xVideoStream:
         self._in_shape, self._in_bits = tuple(in_shape), in_bits
         out_shape = self.output_shape(in_shape)
         in_layout = self._in_layout if self.in_format is not None else None
-        self._yuv_enter = None if in_layout is None else pixfmt.yuv_entry(in_layout, self.in_matrix, self.in_full_range)
+        if in_layout is None:
+            self._yuv_enter = None
+        elif self.hdr is not None:                      # the HDR planes of the decoder: gather and tone map in one launch
+            self._yuv_enter = hdr_utils.hdr_yuv_entry(in_layout, self.in_full_range, self.hdr.color_trc, self.hdr.output_colorspace,
+                                                      **self.hdr.params)
+        else:
+            self._yuv_enter = pixfmt.yuv_entry(in_layout, self.in_matrix, self.in_full_range)
         if self.out_format is not None:
             self.out_layout = pixfmt.PlaneLayout(self.out_format, out_shape[1], out_shape[0])
             self._yuv_leave = pixfmt.yuv_leave(self.out_layout, self.out_matrix, self.out_full_range)
