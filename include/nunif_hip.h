@@ -264,6 +264,23 @@ void nunif_hip_row_flow_destroy(nunif_row_flow *handle);
 int nunif_hip_row_flow_delta(nunif_row_flow *handle, const float *x, float *delta, int32_t B, int32_t h, int32_t w,
                              int32_t flip, void *stream);
 
+/* iw3 "sbs.row_flow_v2" (iw3/models/row_flow_v2.py :9-92, --method row_flow_v2, the previous default): seven row
+ * convolutions, delta = non_overlap + overlap_residual (_forward :44-48) as _forward_delta_only :80-86 evaluates them
+ * (replicate pad 28, net, crop 28 == the unpadded stack on clamped input coordinates), in ONE launch.  create() takes
+ * the reference state dict (keys feature.0.*, non_overlap.*, overlap_residual.{0,2,4,6}.*, delta_scale).  x: [B,3,h,w]
+ * f32 device, delta: [B,1,h,w] f32 device, any h, w >= 1.  flip as nunif_hip_row_flow_delta: the planes are read
+ * mirrored and delta stays in the mirrored frame, which is what nunif_hip_delta_warp(flip = 1) expects. */
+typedef struct nunif_row_flow_v2 nunif_row_flow_v2;
+int nunif_hip_row_flow_v2_create(const nunif_tensor_desc *tensors, int32_t n_tensors, nunif_row_flow_v2 **handle);
+void nunif_hip_row_flow_v2_destroy(nunif_row_flow_v2 *handle);
+int nunif_hip_row_flow_v2_delta(nunif_row_flow_v2 *handle, const float *x, float *delta, int32_t B, int32_t h, int32_t w,
+                                int32_t flip, void *stream);
+/* The same launch, also writing the intermediate maps (row_flow_v2.py :15-33) as f32 [B,C,h,w] for the tests: feature
+ * (16, after ReLU), the three 1x9 ReLU outputs (16, 32, 32), non_overlap (1) and overlap_residual (1). */
+int nunif_hip_row_flow_v2_debug_taps(nunif_row_flow_v2 *handle, const float *x, float *delta, float *feature, float *relu1,
+                                     float *relu2, float *relu3, float *non_overlap, float *residual, int32_t B, int32_t h,
+                                     int32_t w, int32_t flip, void *stream);
+
 /* Replaces iw3/backward_warp.py backward_warp :67-83 for a horizontal flow map: grid = make_grid + [delta, 0] *
  * delta_scale at (dh, dw), bilinear (align_corners) resize to (H, W), grid_sample(bilinear, border, align_corners) +
  * clamp(0,1).  flip = 1: out = flip(backward_warp(flip(c), ...)) without materialising the flips. */

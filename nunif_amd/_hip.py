@@ -109,6 +109,10 @@ SIGNATURES = {
     "nunif_hip_row_flow_create": (c_int32, [ctypes.POINTER(TensorDesc), c_int32, ctypes.POINTER(c_void_p)]),
     "nunif_hip_row_flow_destroy": (None, [c_void_p]),
     "nunif_hip_row_flow_delta": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "nunif_hip_row_flow_v2_create": (c_int32, [ctypes.POINTER(TensorDesc), c_int32, ctypes.POINTER(c_void_p)]),
+    "nunif_hip_row_flow_v2_destroy": (None, [c_void_p]),
+    "nunif_hip_row_flow_v2_delta": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "nunif_hip_row_flow_v2_debug_taps": (c_int32, [c_void_p] * 9 + [c_int32] * 4 + [c_void_p]),
     "nunif_hip_delta_warp": (c_int32, [c_void_p, c_void_p, c_void_p] + [c_int32] * 6 + [c_double, c_int32, c_void_p]),
     "nunif_hip_mlbw_create": (c_int32, [ctypes.POINTER(TensorDesc), c_int32, ctypes.POINTER(c_void_p)]),
     "nunif_hip_mlbw_destroy": (None, [c_void_p]),

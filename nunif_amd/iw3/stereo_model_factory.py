@@ -13,6 +13,7 @@ from ..nunif.models import load_model
 from .forward_inpaint import ForwardInpaint
 from .mlbw_inpaint import MLBWInpaint
 
+ROW_FLOW_V2 = "iw3_row_flow_v2_20240130.pth"
 ROW_FLOW_V3 = "iw3_row_flow_v3_20250627.pth"
 ROW_FLOW_V3_SYM = "iw3_row_flow_v3_sym_20250628.pth"
 MLBW = {("l2", 1): "iw3_mlbw_l2_d1_20250627.pth", ("l2", 2): "iw3_mlbw_l2_d2_20250627.pth",
@@ -77,9 +78,19 @@ def load_row_flow_model(method, device_id, model_dir=None):
         model = _load(ROW_FLOW_V3_SYM, device_id, model_dir)
         model.symmetric = True
     elif method == "row_flow_v2":
-        raise NotImplementedError("row_flow_v2 (the 2024 legacy net) is not on the HIP engine; use row_flow_v3")
+        raise NotImplementedError("row_flow_v2 is not wired into this factory yet: load it with load_row_flow_v2_model(device_id) "
+                                  "and pass it as apply_divergence(..., side_model=...), or use row_flow_v3")
     else:
         raise ValueError(method)
+    model.delta_output = True
+    return model
+
+
+def load_row_flow_v2_model(device_id, model_dir=None):
+    """``--method row_flow_v2`` (reference ``load_row_flow_model`` :97-112, its ROW_FLOW_V2_URL): the 2024 row-conv net,
+    ``nunif_amd.iw3.models.row_flow_v2.RowFlowV2``.  A loader of its own while ``load_row_flow_model("row_flow_v2")`` keeps
+    refusing the name."""
+    model = _load(ROW_FLOW_V2, device_id, model_dir)
     model.delta_output = True
     return model
 

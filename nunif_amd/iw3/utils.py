@@ -3,7 +3,7 @@
 ``postprocess_image`` :430-487 (IPD pad, ``postprocess_padding`` :394-427, VR180 projection, half-SBS / half-TB / half-RGBD
 bicubic-antialias resize, anaglyph / SBS / TB / cross-eyed compose, max-output resize), ``apply_rgbd`` :74-88 and ``nunif/utils/video.py`` ``to_tensor`` / ``to_frame`` :218-269 (``to_frame_tensor`` here returns
 the quantised HWC tensor; wrapping it into an ``av.VideoFrame`` is the caller's codec business).
-``row_flow_v3`` (the default method), ``mlbw_l2/l4/l2s/l4s`` and the inpaint side models (``forward_inpaint`` ->
+``row_flow_v3`` (the default method), ``row_flow_v2``, ``mlbw_l2/l4/l2s/l4s`` and the inpaint side models (``forward_inpaint`` ->
 ``nunif_amd.iw3.forward_inpaint.ForwardInpaint``, ``mlbw_l2_inpaint`` -> ``nunif_amd.iw3.mlbw_inpaint.MLBWInpaint``) run on the
 engine."""
 import torch
@@ -60,8 +60,8 @@ def apply_divergence(depth, im, args, side_model, reset_pts=None):
         left, right = apply_divergence_forward_warp(im, depth, args.divergence, convergence=convergence,
                                                     method=args.method, synthetic_view=args.synthetic_view,
                                                     width_base=False)
-    elif args.method in {"row_flow_v3", "row_flow", "row_flow_v3_sym", "row_flow_sym", "mlbw_l2", "mlbw_l4", "mlbw_l2s",
-                         "mlbw_l4s"}:
+    elif args.method in {"row_flow_v3", "row_flow", "row_flow_v3_sym", "row_flow_sym", "row_flow_v2", "mlbw_l2", "mlbw_l4",
+                         "mlbw_l2s", "mlbw_l4s"}:
         # iw3/utils.py:369-387: optional --stereo-width resize of the depth, then the NN backward warp
         if side_model is None:
             raise ValueError(f"method={args.method} needs a side model (nunif_amd.iw3.models.row_flow_v3.RowFlowV3)")

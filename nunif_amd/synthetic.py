@@ -294,6 +294,27 @@ def row_flow_v3_state_dict(seed, regime="benign"):
     return sd
 
 
+def row_flow_v2_state_dict(seed):
+    """Seeded ``sbs.row_flow_v2`` weights in the reference's key layout, every bias non-zero.  The stem is scaled up (its inputs
+    are a depth in [0, 1] and two constants of a few hundredths) and the two heads so that delta sits in the range of a trained
+    model's (a std of about one depth pixel), i.e. the warp really moves pixels."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+
+    def conv(key, cout, cin, kh, kw, gain=1.0, bstd=0.1):
+        sd[key + ".weight"] = torch.randn((cout, cin, kh, kw), generator=g) * (gain * math.sqrt(2.0 / (cin * kh * kw)))
+        sd[key + ".bias"] = torch.randn(cout, generator=g) * bstd
+
+    conv("feature.0", 16, 3, 1, 3, gain=4.0, bstd=0.5)
+    conv("non_overlap", 1, 16, 1, 1, gain=2.0, bstd=1.0)
+    conv("overlap_residual.0", 16, 16, 1, 9)
+    conv("overlap_residual.2", 32, 16, 1, 9)
+    conv("overlap_residual.4", 32, 32, 1, 9)
+    conv("overlap_residual.6", 1, 32, 3, 3, gain=2.0, bstd=1.0)
+    sd["delta_scale"] = torch.tensor(1.0 / 127.0)
+    return sd
+
+
 def _heat_window_net(sd, qkv=2.5, branch=2.0, bias=1.75):
     """The window-attention nets of iw3 (row_flow_v3, mlbw) in the regime of a trained net: see row_flow_v3_state_dict."""
     for k in list(sd):
