@@ -243,6 +243,40 @@ int nunif_hip_depth_anything_forward(nunif_depth_anything *handle, const float *
 int nunif_hip_depth_anything_reset_state(nunif_depth_anything *handle);
 int nunif_hip_depth_anything_is_temporal(const nunif_depth_anything *handle);
 
+/* The six activations the published DepthAnythingCore hooks for ZoeDepth (iw3/zoedepth_model.py:161-164 loads
+ * "DepthAnythingMetricDepth" through torch.hub; the net is not in the reference tree): the 32-channel map behind the first conv +
+ * ReLU of depth_head.scratch.output_conv2 [B,h,w,32], layer4_rn [B,bh,bw,C] and the refinenet outputs r4, r3, r2, r1
+ * [B,rh[i],rw[i],C] — NHWC fp16 device pointers into the engine's workspace, valid until the next call on that handle. */
+typedef struct nunif_da_features {
+    const void *outconv;
+    const void *bottleneck;
+    const void *blocks[4];
+    int32_t bh, bw, rh[4], rw[4], channels;
+} nunif_da_features;
+/* nunif_hip_depth_anything_forward that also leaves those maps behind (per-frame engines only).  `depth` is bit for bit what
+ * _forward writes. */
+int nunif_hip_depth_anything_forward_features(nunif_depth_anything *handle, const float *x, const float *pos, float *depth,
+                                              int32_t B, int32_t h, int32_t w, nunif_da_features *features, void *stream);
+
+/* ZoeDepth metric-bins head over those maps (--depth-model ZoeD_Any_N / ZoeD_Any_K): replaces `model(x)['metric_depth']` and
+ * torch.nan_to_num of iw3/zoedepth_model.py:23-27 `_forward`.  Tensors carry HuggingFace's
+ * ZoeDepthMetricDepthEstimationHead names (softplus bin centres, un-normed attractors, 64 bins); alpha is the attractor strength
+ * (gamma 2, kind "mean"), min_temp / max_temp the conditional log-binomial's temperature range. */
+typedef struct nunif_zoedepth_head nunif_zoedepth_head;
+int nunif_hip_zoedepth_head_create(const nunif_tensor_desc *tensors, int32_t n_tensors, float alpha, float min_temp, float max_temp,
+                                   nunif_zoedepth_head **handle);
+/* rel: [B,h,w] f32 device, the relative depth (same size as features->outconv); out: [B,h,w] f32 device. */
+int nunif_hip_zoedepth_head_forward(nunif_zoedepth_head *handle, const nunif_da_features *features, const float *rel, float *out,
+                                    int32_t B, int32_t h, int32_t w, void *stream);
+/* Bin centres of the last _forward: tap 0 = seed centres, 1..4 = behind each attractor.  dst: [B,th,tw,64] f32 device or NULL;
+ * dims: host {B, th, tw} or NULL. */
+int nunif_hip_zoedepth_head_debug_taps(nunif_zoedepth_head *handle, int32_t tap, float *dst, int32_t *dims, void *stream);
+void nunif_hip_zoedepth_head_destroy(nunif_zoedepth_head *handle);
+/* Tail of batch_preprocess (iw3/zoedepth_model.py:66-83): reflection_pad2d_loop (nunif/modules/reflection_pad2d.py:49-68; a pad
+ * may exceed the map), clamp(0, 1), (x - 0.5) / 0.5.  x: [planes,h,w] f32 -> y: [planes,h+top+bottom,w+left+right] f32. */
+int nunif_hip_zoedepth_pad_normalize(const float *x, float *y, int64_t planes, int32_t h, int32_t w, int32_t left, int32_t right,
+                                     int32_t top, int32_t bottom, void *stream);
+
 /* iw3 "iw3.depth_aa" (iw3/models/depth_aa.py :29-95, --depth-aa): depth anti-aliasing net.  x, y: [B,1,h,w] f32 device.
  * mode 0: forward(clamp=False); 1: forward(clamp=True) (eval default); 2: infer() = tensor-wide min-max normalise,
  * forward(clamp=False), de-normalise (what BaseDepthModel.infer(depth_aa=True) calls). */

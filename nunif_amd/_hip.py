@@ -69,6 +69,12 @@ class PixfmtPlanes(ctypes.Structure):
     _fields_ = [("data", c_void_p * 3), ("pitch", c_int64 * 3)]
 
 
+class DaFeatures(ctypes.Structure):
+    """``nunif_da_features``: the six NHWC fp16 maps the Depth-Anything engine leaves for ZoeDepth's head, and their sizes."""
+    _fields_ = [("outconv", c_void_p), ("bottleneck", c_void_p), ("blocks", c_void_p * 4), ("bh", c_int32), ("bw", c_int32),
+                ("rh", c_int32 * 4), ("rw", c_int32 * 4), ("channels", c_int32)]
+
+
 class ProfRecord(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 48), ("total_ms", c_double), ("launches", c_int64),
                 ("flops", c_double), ("bytes", c_double)]
@@ -141,6 +147,15 @@ SIGNATURES = {
     "nunif_hip_depth_anything_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "nunif_hip_depth_anything_reset_state": (c_int32, [c_void_p]),
     "nunif_hip_depth_anything_is_temporal": (c_int32, [c_void_p]),
+    "nunif_hip_depth_anything_forward_features": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                                            ctypes.POINTER(DaFeatures), c_void_p]),
+    "nunif_hip_zoedepth_head_create": (c_int32, [ctypes.POINTER(TensorDesc), c_int32, c_float, c_float, c_float,
+                                                 ctypes.POINTER(c_void_p)]),
+    "nunif_hip_zoedepth_head_forward": (c_int32, [c_void_p, ctypes.POINTER(DaFeatures), c_void_p, c_void_p, c_int32, c_int32,
+                                                  c_int32, c_void_p]),
+    "nunif_hip_zoedepth_head_debug_taps": (c_int32, [c_void_p, c_int32, c_void_p, ctypes.POINTER(c_int32), c_void_p]),
+    "nunif_hip_zoedepth_head_destroy": (None, [c_void_p]),
+    "nunif_hip_zoedepth_pad_normalize": (c_int32, [c_void_p, c_void_p, c_int64] + [c_int32] * 6 + [c_void_p]),
     "nunif_hip_tta_view": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "nunif_hip_tta_merge": (c_int32, [ctypes.POINTER(c_void_p), c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "nunif_hip_alpha_border_padding": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),

@@ -404,6 +404,7 @@ struct nunif_depth_anything : DeviceOwner {
     // the reassemble branch of tap k (project -> resize -> layer_rn conv) on a stream of its own, beside the encoder layers that
     // follow the tap: per-branch temporaries, fork / join events (forward())
     DeviceBuf bm1[4], bm2[4], bpart[4];
+    DeviceBuf fr[3];                        // forward_features: r4, r3, r2 (the refinenet outputs without the next stage's RCU1)
     DeviceBuf bt1[3], br1[3];               // RCU1 of refinenets 1-3 beside the encoder: conv1's map, RCU1(skip) (forward())
     hipStream_t side[3] = {nullptr, nullptr, nullptr};
     hipEvent_t ev_fork[3] = {nullptr, nullptr, nullptr}, ev_join[3] = {nullptr, nullptr, nullptr};
@@ -814,7 +815,7 @@ extern "C" void nunif_hip_depth_anything_destroy(nunif_depth_anything *h) {
                    &h->feat[3], &h->rnb[0], &h->rnb[1], &h->rnb[2], &h->rnb[3], &h->m1, &h->m2, &h->m3, &h->m4, &h->m5, &h->part, &h->col};
     for (DeviceBuf *b : bufs) b->release();
     for (int i = 0; i < 4; ++i) { h->bm1[i].release(); h->bm2[i].release(); h->bpart[i].release(); }
-    for (int i = 0; i < 3; ++i) { h->bt1[i].release(); h->br1[i].release(); }
+    for (int i = 0; i < 3; ++i) { h->bt1[i].release(); h->br1[i].release(); h->fr[i].release(); }
     for (TMod &tmod : h->tm)
         for (TAtt &at : tmod.at) { at.kc.release(); at.vc.release(); }
     for (DeviceBuf *b : {&h->ta, &h->th, &h->tqkv, &h->tatt, &h->thid, &h->tgg, &h->tpart}) b->release();
@@ -828,8 +829,11 @@ extern "C" void nunif_hip_depth_anything_destroy(nunif_depth_anything *h) {
 
 // x: [B,3,h,w] f32 (ImageNet-normalised), pos: [1 + gh*gw][D] f32 (interpolated position embedding, device),
 // depth: [B,h,w] f32
-extern "C" int nunif_hip_depth_anything_forward(nunif_depth_anything *h, const float *x, const float *pos, float *depth,
-                                                int32_t B, int32_t hh, int32_t ww, void *stream) {
+// feat (optional): the maps ZoeDepth's head reads are left in the workspace and described there (nunif_da_features); the
+// launches that produce `depth` are the same with and without it
+static int da_forward(nunif_depth_anything *h, const float *x, const float *pos, float *depth, int32_t B, int32_t hh, int32_t ww,
+                      nunif_da_features *feat, void *stream) {
+    NUNIF_REQUIRE(!feat || !h || !h->temporal, "depth_anything_forward_features: per-frame engines only");
     NUNIF_REQUIRE(h && x && pos && depth && B > 0 && hh >= 28 && ww >= 28 && hh % kPatch == 0 && ww % kPatch == 0,
                   "depth_anything_forward: h, w must be multiples of 14 (>= 28)");
     hipStream_t s = (hipStream_t)stream;
@@ -891,6 +895,9 @@ extern "C" int nunif_hip_depth_anything_forward(nunif_depth_anything *h, const f
         for (int i = 0; i < 3; ++i)
             if ((rc = h->bt1[i].ensure((size_t)B * Hs[i] * Ws[i] * F * e2)) || (rc = h->br1[i].ensure((size_t)B * Hs[i] * Ws[i] * F * e2)))
                 return rc;
+    if (feat)            // r4 / r3 / r2 live on the grids of layer 3 / 2 / 1
+        for (int i = 0; i < 3; ++i)
+            if ((rc = h->fr[i].ensure((size_t)B * Hs[2 - i] * Ws[2 - i] * F * e2))) return rc;
     if (h->rs3g.w && (rc = h->col.ensure((size_t)B * H4 * W4 * 9 * h->OCP[3] * e2))) return rc;
     if (side_streams && !h->side[0]) {
         for (int i = 0; i < 3; ++i) {
@@ -1126,9 +1133,11 @@ extern "C" int nunif_hip_depth_anything_forward(nunif_depth_anything *h, const f
         if ((rc = run_lin(h->fus[3].out, m2, B, W4, W4, 0, 0, nullptr, m3, s, "da_out_conv", 0, 0, 1, H4))) return rc;
         // (rcu1_branch: m4 = path4 + RCU1(layer3_rn) right away)
         if ((rc = upsample(m3, H4, W4, H3, W3, F, m4, rcu1_branch ? (const f16 *)h->br1[2].p : nullptr))) return rc;       // path4 in m4
+        if (feat && (rc = upsample(m3, H4, W4, H3, W3, F, (f16 *)h->fr[0].p))) return rc;                                    // r4 itself
     } else {
         if ((rc = upsample(m2, H4, W4, H3, W3, F, m3))) return rc;
         if ((rc = run_lin(h->fus[3].out, m3, B, W3, W3, 0, 0, nullptr, m4, s, "da_out_conv", 0, 0, 1, H3))) return rc;      // path4 in m4
+        if (feat) NUNIF_HIP_CHECK(hipMemcpyAsync(h->fr[0].p, m4, (size_t)B * H3 * W3 * F * e2, hipMemcpyDeviceToDevice, s));
     }
     if (h->temporal && (rc = run_tmod(2, m4, s))) return rc;                     // motion_modules[2] on path_4
     // path3 .. path1
@@ -1146,9 +1155,11 @@ extern "C" int nunif_hip_depth_anything_forward(nunif_depth_anything *h, const f
         if (conv_first) {
             if ((rc = run_lin(h->fus[k].out, m3, B, Wc, Wc, 0, 0, nullptr, m1, s, "da_out_conv", 0, 0, 1, Hc))) return rc;
             if ((rc = upsample(m1, Hc, Wc, Hn, Wn, F, pout, rcu1_branch && k > 0 ? (const f16 *)h->br1[k - 1].p : nullptr))) return rc;
+            if (feat && k > 0 && (rc = upsample(m1, Hc, Wc, Hn, Wn, F, (f16 *)h->fr[3 - k].p))) return rc;                   // r3 (k = 2), r2 (k = 1)
         } else {
             if ((rc = upsample(m3, Hc, Wc, Hn, Wn, F, m2))) return rc;
             if ((rc = run_lin(h->fus[k].out, m2, B, Wn, Wn, 0, 0, nullptr, pout, s, "da_out_conv", 0, 0, 1, Hn))) return rc;
+            if (feat && k > 0) NUNIF_HIP_CHECK(hipMemcpyAsync(h->fr[3 - k].p, pout, (size_t)B * Hn * Wn * F * e2, hipMemcpyDeviceToDevice, s));
         }
         if (h->temporal && k == 2 && (rc = run_tmod(3, pout, s))) return rc;      // motion_modules[3] on path_3
         path = pout;
@@ -1165,7 +1176,29 @@ extern "C" int nunif_hip_depth_anything_forward(nunif_depth_anything *h, const f
         NUNIF_LAUNCH_CHECK();
     }
     if (h->temporal) { h->t_len = t_len_end; h->t_start = t_start_end; }                    // the B frames joined the window
+    if (feat) {
+        // m3: output_conv2's first conv + ReLU; `path`: r1 (the last refinenet joins no skip behind it); neither is written again
+        feat->outconv = m3; feat->bottleneck = rn[3]; feat->bh = H4; feat->bw = W4; feat->channels = F;
+        feat->blocks[0] = h->fr[0].p; feat->rh[0] = H3; feat->rw[0] = W3;
+        feat->blocks[1] = h->fr[1].p; feat->rh[1] = H2; feat->rw[1] = W2;
+        feat->blocks[2] = h->fr[2].p; feat->rh[2] = H1; feat->rw[2] = W1;
+        feat->blocks[3] = path; feat->rh[3] = HF; feat->rw[3] = WF;
+    }
     return NUNIF_HIP_OK;
+}
+
+extern "C" int nunif_hip_depth_anything_forward(nunif_depth_anything *h, const float *x, const float *pos, float *depth,
+                                                int32_t B, int32_t hh, int32_t ww, void *stream) {
+    return da_forward(h, x, pos, depth, B, hh, ww, nullptr, stream);
+}
+
+// The same forward that also describes the six maps ZoeDepth's DepthAnythingCore hooks (`out_conv`, `l4_rn`, `r4` .. `r1`; the
+// torch.hub net behind iw3/zoedepth_model.py:161-164): zoedepth_head.hip reads them.  With RCU1 beside the encoder the stage
+// resize adds the next skip at once, so r4 / r3 / r2 get a plain resize of their own (three small launches more).
+extern "C" int nunif_hip_depth_anything_forward_features(nunif_depth_anything *h, const float *x, const float *pos, float *depth,
+                                                         int32_t B, int32_t hh, int32_t ww, nunif_da_features *features, void *stream) {
+    NUNIF_REQUIRE(features, "depth_anything_forward_features: NULL features");
+    return da_forward(h, x, pos, depth, B, hh, ww, features, stream);
 }
 
 // `model.reset_state()` (iw3/video_depth_anything_streaming_model.py:74-75, at scene cuts): the next frame starts a new window.

@@ -510,7 +510,7 @@ DEPTH_ANYTHING_ENCODERS = {      # published geometries (Depth-Anything-V2 dpt.p
 }
 
 
-def depth_anything_v2_state_dict(seed, grid=37, encoder="vits", regime="benign"):
+def depth_anything_v2_state_dict(seed, grid=37, encoder="vits", regime="benign", features=None):
     """Seeded weights in the public checkpoint's key layout (``encoder``: vits / vitb / vitl).  LayerScale gammas are
     O(1) * 0.3 (0.2 for the 24 blocks of vitl) and the residual branches are damped so that the blocks keep the token rms O(1)
     (a trained ViT's regime), every bias is non-zero.
@@ -523,7 +523,7 @@ def depth_anything_v2_state_dict(seed, grid=37, encoder="vits", regime="benign")
     g = torch.Generator().manual_seed(seed)
     sd = {}
     cfg = DEPTH_ANYTHING_ENCODERS[encoder]
-    EMBED, DEPTH, OUT_CH, FEAT = cfg["embed"], cfg["depth"], cfg["out_channels"], cfg["features"]
+    EMBED, DEPTH, OUT_CH, FEAT = cfg["embed"], cfg["depth"], cfg["out_channels"], features or cfg["features"]
     MLP = 4 * EMBED
     ls = 0.3 if DEPTH == 12 else 0.2
 
@@ -581,6 +581,44 @@ def depth_anything_v2_state_dict(seed, grid=37, encoder="vits", regime="benign")
     # a depth map, not a mostly-clipped one: positive mixing weights and bias in the last 1x1 (the ReLU then rarely bites)
     sd[h + "scratch.output_conv2.2.weight"] = sd[h + "scratch.output_conv2.2.weight"].abs() * 0.5
     sd[h + "scratch.output_conv2.2.bias"] = sd[h + "scratch.output_conv2.2.bias"].abs() * 0.2 + 0.1
+    return sd
+
+
+ZOEDEPTH_ATTRACTORS = (16, 8, 4, 1)
+
+
+def zoedepth_head_state_dict(seed, prefix="metric_head."):
+    """Seeded weights of ZoeDepth's metric-bins head at its real dimensions (256 / 128, 64 bins, attractors 16-8-4-1, MLP
+    161 -> 80 -> 4) under HuggingFace's ``ZoeDepthMetricDepthEstimationHead`` names.  Biases are non-trivial: the seed centres
+    spread over ~0.3 .. 4, the attractors land among them (so ``dx / (1 + alpha dx^2)`` is exercised on both sides of its peak),
+    and the four outputs of the log-binomial MLP sit away from zero (probability and temperature away from 1/2)."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+
+    def conv(key, cout, cin, gain=1.0, bstd=0.1, bmean=0.0):
+        sd[prefix + key + ".weight"] = torch.randn((cout, cin, 1, 1), generator=g) * (gain * math.sqrt(1.0 / cin))
+        sd[prefix + key + ".bias"] = torch.randn((cout,), generator=g) * bstd + bmean
+
+    conv("conv2", 256, 256)
+    conv("seed_bin_regressor.conv1", 256, 256, gain=1.4, bstd=0.2)
+    conv("seed_bin_regressor.conv2", 64, 256, gain=1.0, bstd=1.2, bmean=0.8)
+    conv("seed_projector.conv1", 128, 256, gain=1.4, bstd=0.2)
+    conv("seed_projector.conv2", 128, 128)
+    for i, na in enumerate(ZOEDEPTH_ATTRACTORS):
+        conv(f"projectors.{i}.conv1", 128, 256, gain=1.4, bstd=0.2)
+        conv(f"projectors.{i}.conv2", 128, 128)
+        conv(f"attractors.{i}.conv1", 128, 128, gain=1.4, bstd=0.2)
+        conv(f"attractors.{i}.conv2", na, 128, gain=1.0, bstd=1.0, bmean=0.8)
+    conv("conditional_log_binomial.mlp.0", 80, 161, gain=1.2, bstd=0.3)
+    conv("conditional_log_binomial.mlp.2", 4, 80, gain=1.5, bstd=0.7, bmean=0.3)
+    return sd
+
+
+def zoedepth_any_state_dict(seed, grid=37):
+    """``ZoeD_Any_*`` at test size: a ViT-S encoder under a DPT neck of width 256 (``pretrained.*`` / ``depth_head.*``, the
+    Depth-Anything layout) plus the metric-bins head (``metric_head.*``) at its real dimensions."""
+    sd = depth_anything_v2_state_dict(seed, grid=grid, encoder="vits", features=256)
+    sd.update(zoedepth_head_state_dict(seed + 1))
     return sd
 
 
