@@ -21,12 +21,11 @@
 #include <string>
 #include <vector>
 
+#include "gemm_f32.h"
 #include "host_weights.h"
 
 namespace nunif {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kWin = 8;                  // window side = stride of the net
 constexpr int kTok = kWin * kWin;        // tokens per window / pixels per pool tile
@@ -34,13 +33,6 @@ constexpr int kHead = 32;                // channels per attention head
 constexpr int kUnit = 64;                // OutpaintBase pads to a multiple of mod * downscaling_factor
 
 enum { MODE_COMPOSITE = 0, MODE_RAW = 1, MODE_FORWARD = 2 };
-
-__device__ __forceinline__ f32x16 zero16() {
-    f32x16 v;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) v[r] = 0.f;
-    return v;
-}
 
 // acc += A[32 rows][K] * B[K][32 columns]; A in LDS with element (i, k) at A[i * sa + k], B in global memory row-major with
 // element (k, j) at B[k * ldb + j].  Lane l feeds A[l & 31][k + (l >> 5)] and B[k + (l >> 5)][l & 31].
@@ -64,9 +56,6 @@ __device__ __forceinline__ f32x16 mm_ll(const float *A, int sa, const float *B, 
         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(A[lr * sa + k + lk], B[(k + lk) * sbk + lr * sbj], acc, 0, 0, 0);
     return acc;
 }
-
-// accumulator register r of lane l: row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31
-__device__ __forceinline__ int acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 __device__ __forceinline__ float leaky(float v) { return v > 0.f ? v : 0.2f * v; }
 __device__ __forceinline__ float sigmoidf(float v) { return 1.f / (1.f + expf(-v)); }

@@ -14,16 +14,12 @@
 #include <string>
 #include <vector>
 
+#include "gemm_f32.h"
 #include "host_weights.h"
 
 namespace nunif {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kBK = 16;          // k per LDS stage
-constexpr int kPad = 4;          // LDS row padding (floats)
-constexpr int kFlush = 128;      // k per accumulation chain
 constexpr int kCell = 8;         // stride of the net: one 65-way softmax per 8 x 8 cell
 
 enum { A_PLAIN = 0, A_CONV = 1, A_CONV_POOL = 2 };
@@ -38,26 +34,21 @@ struct GemmArgs {
     int Hp, Wp;                  // pooled geometry
 };
 
-struct RowInfo { long long base; int h, w, ok; };
-
 template <int AMODE>
 __device__ __forceinline__ RowInfo row_info(const GemmArgs &g, int m) {
+    if (AMODE == A_PLAIN) return row_plain(m, g.M, g.lda);
+    if (AMODE == A_CONV) return row_conv(m, g.M, g.H, g.W);
+    // rows ordered (image, pooled pixel, 2x2 corner): (h, w) is the full-resolution pixel of corner m & 3
     RowInfo r;
     r.ok = m < g.M;
     if (!r.ok) m = 0;
-    if (AMODE == A_PLAIN) {
-        r.base = (long long)m * g.lda; r.h = 0; r.w = 0;
-    } else if (AMODE == A_CONV) {
-        const int hw = g.H * g.W, b = m / hw, p = m - b * hw;
-        r.h = p / g.W; r.w = p - r.h * g.W; r.base = b;
-    } else {
-        const int q = m & 3, mp = m >> 2, pp = g.Hp * g.Wp, b = mp / pp, p = mp - b * pp, ph = p / g.Wp, pw = p - ph * g.Wp;
-        r.h = 2 * ph + (q >> 1); r.w = 2 * pw + (q & 1); r.base = b;
-    }
+    const int q = m & 3, mp = m >> 2, pp = g.Hp * g.Wp, b = mp / pp, p = mp - b * pp, ph = p / g.Wp, pw = p - ph * g.Wp;
+    r.h = 2 * ph + (q >> 1); r.w = 2 * pw + (q & 1); r.base = b;
     return r;
 }
 
-// Four consecutive k of row r starting at k (k % 4 == 0; C % 4 == 0, so the four lie inside one tap).
+// Four consecutive k of row r starting at k (k % 4 == 0; C % 4 == 0, so the four lie inside one tap).  B is not zero padded
+// in k here, so k >= K loads zeros.
 template <int AMODE>
 __device__ __forceinline__ f32x4 load_a(const GemmArgs &g, const RowInfo &r, int k) {
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
@@ -74,24 +65,24 @@ __device__ __forceinline__ f32x4 load_a(const GemmArgs &g, const RowInfo &r, int
 
 // C[M][N] = A[M][K] * B[K][N] on v_mfma_f32_32x32x2_f32.  4 waves as WM x WN, each TM x TN tiles of 32 x 32.  A comes through
 // load_a (implicit im2col), B is a plain row-major matrix.  LDS holds both tiles k-major so that an MFMA operand is one
-// conflict-free ds_read_b32; two LDS stages and a register stage hide the global loads (the loop of transnetv2.hip).
+// conflict-free ds_read_b32; two LDS stages and a register stage hide the global loads.  tn_gemm of transnetv2.hip holds the same
+// loop (gemm_f32.h says why it is written twice): change both.
 template <int AMODE, int EMODE, int WM, int WN, int TM, int TN>
 __global__ __launch_bounds__(256) void sp_gemm(const GemmArgs g) {
-    constexpr int BM = WM * TM * 32, BN = WN * TN * 32, LDA = BM + kPad, LDB = BN + kPad;
-    constexpr int APASS = BM / 64, BVEC = kBK * BN / 4, BPASS = (BVEC + 255) / 256;
-    constexpr int STAGES = 2 * kBK * (LDA + LDB), TILE = (EMODE == E_DET || EMODE == E_DESC) ? BM * (BN + 1) : 0;
+    typedef GemmTile<WM, WN, TM, TN> Tile;
+    constexpr int BM = Tile::BM, BN = Tile::BN, LDA = Tile::LDA, LDB = Tile::LDB;
+    constexpr int AP = Tile::APASS, BVEC = Tile::BVEC, BPASS = Tile::BPASS;
+    constexpr int STAGES = 2 * (Tile::A_STAGE + Tile::B_STAGE), TILE = (EMODE == E_DET || EMODE == E_DESC) ? BM * (BN + 1) : 0;
     constexpr int SMEM = STAGES > TILE ? STAGES : TILE;
-    static_assert(WM * WN == 4 && (BM % 64 == 0 || BM == 32), "tile shape");
     static_assert(SMEM * 4 <= 65536, "LDS");
     __shared__ __attribute__((aligned(16))) float smem[SMEM];
     __shared__ float rown[BM];
-    float *As = smem, *Bs = smem + 2 * kBK * LDA;
+    float *As = smem, *Bs = smem + 2 * Tile::A_STAGE;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave / WN, wn = wave % WN;
     const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
 
     // A loader: thread -> (row arow, 4 k starting at kq); BM == 32 uses the first 128 threads only
-    constexpr int AP = APASS > 0 ? APASS : 1;
     const int kq = (tid & 3) * 4, arow = tid >> 2;
     const bool aload = BM >= 64 || arow < BM;
     RowInfo rows[AP];
@@ -172,7 +163,8 @@ __global__ __launch_bounds__(256) void sp_gemm(const GemmArgs g) {
         __syncthreads();
     }
 
-    // accumulator register r of lane l: row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31
+    // acc_row() of gemm_f32.h, spelled out (through the function the epilogues compile to other code): registers 4 q4 .. 4 q4 + 3
+    // of a lane are rows 8 q4 + 4 lk .. + 3 of the 32 x 32 tile
     if (EMODE == E_BN || EMODE == E_BN_POOL) {
 #pragma unroll
         for (int i = 0; i < TM; ++i)

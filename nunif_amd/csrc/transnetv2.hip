@@ -15,16 +15,12 @@
 #include <string>
 #include <vector>
 
+#include "gemm_f32.h"
 #include "host_weights.h"
 
 namespace nunif {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kBK = 16;          // k per LDS stage
-constexpr int kPad = 4;          // LDS row padding (floats)
-constexpr int kFlush = 128;      // k per accumulation chain
 constexpr int kH0 = 27, kW0 = 48, kLookup = 101, kHeadIn = 4864, kD = 1024, kFeat = 448;
 
 enum { A_PLAIN = 0, A_SPATIAL = 1, A_SPATIAL3 = 2, A_TEMPORAL = 3, A_TEMPORAL_POOL = 4 };
@@ -43,25 +39,21 @@ struct GemmArgs {
     long long b_z;
 };
 
-// One row of the A tile as its loader thread sees it.
-struct RowInfo { long long base; int h, w, ok; };
-
+// The temporal rows gather frames of one window: h = t, w = pixel inside the frame, base = first frame of the window.
 template <int AMODE>
 __device__ __forceinline__ RowInfo row_info(const GemmArgs &g, int m) {
+    if (AMODE == A_PLAIN) return row_plain(m, g.M, g.lda);
+    if (AMODE == A_SPATIAL || AMODE == A_SPATIAL3) return row_conv(m, g.M, g.H, g.W);
     RowInfo r;
     r.ok = m < g.M;
     if (!r.ok) m = 0;
-    if (AMODE == A_PLAIN) {
-        r.base = (long long)m * g.lda; r.h = 0; r.w = 0;
-    } else if (AMODE == A_SPATIAL || AMODE == A_SPATIAL3) {
-        const int hw = g.H * g.W, bt = m / hw, p = m - bt * hw;
-        r.h = p / g.W; r.w = p - r.h * g.W; r.base = bt;
-    } else if (AMODE == A_TEMPORAL) {
+    if (AMODE == A_TEMPORAL) {
         const int hw = g.H * g.W, bt = m / hw, p = m - bt * hw;
         r.h = bt % g.T;                                   // t
         r.w = p;                                          // pixel
         r.base = bt - r.h;                                // first frame of this window
     } else {
+        // rows ordered (frame, pooled pixel, 2x2 corner)
         const int q = m & 3, mp = m >> 2, pp = g.Hp * g.Wp, bt = mp / pp, p = mp - bt * pp, ph = p / g.Wp, pw = p - ph * g.Wp;
         r.h = bt % g.T;
         r.w = (2 * ph + (q >> 1)) * g.W + 2 * pw + (q & 1);
@@ -100,13 +92,15 @@ __device__ __forceinline__ f32x4 load_a(const GemmArgs &g, const RowInfo &r, int
 // C[M][N] = A[M][K] * B[K][N] on v_mfma_f32_32x32x2_f32.  4 waves as WM x WN, each TM x TN tiles of 32 x 32.
 // A comes through load_a (implicit im2col / temporal gather), B is a plain row-major matrix.  LDS holds both tiles k-major
 // ([k][row]) so that an MFMA operand is one conflict-free ds_read_b32; two LDS stages and a register stage hide the global loads.
+// sp_gemm of superpoint.hip holds the same loop (gemm_f32.h says why it is written twice): change both.
 template <int AMODE, int EMODE, int WM, int WN, int TM, int TN>
 __global__ __launch_bounds__(256) void tn_gemm(const GemmArgs g) {
-    constexpr int BM = WM * TM * 32, BN = WN * TN * 32, LDA = BM + kPad, LDB = BN + kPad;
-    constexpr int APASS = BM / 64, BVEC = kBK * BN / 4, BPASS = (BVEC + 255) / 256;
-    static_assert(WM * WN == 4 && BM % 64 == 0, "tile shape");
-    __shared__ float As[2][kBK * LDA];
-    __shared__ float Bs[2][kBK * LDB];
+    typedef GemmTile<WM, WN, TM, TN> Tile;
+    constexpr int BM = Tile::BM, BN = Tile::BN, LDA = Tile::LDA, LDB = Tile::LDB;
+    constexpr int APASS = Tile::APASS, BVEC = Tile::BVEC, BPASS = Tile::BPASS;
+    static_assert(BM % 64 == 0, "tile shape");
+    __shared__ float As[2][Tile::A_STAGE];
+    __shared__ float Bs[2][Tile::B_STAGE];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave / WN, wn = wave % WN;
     const int z = blockIdx.z;
@@ -192,7 +186,8 @@ __global__ __launch_bounds__(256) void tn_gemm(const GemmArgs g) {
         __syncthreads();
     }
 
-    // accumulator register r of lane l: row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31
+    // acc_row() of gemm_f32.h, spelled out (through the function the epilogue compiles to other code): registers 4 q4 .. 4 q4 + 3
+    // of a lane are rows 8 q4 + 4 lk .. + 3 of the 32 x 32 tile
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
