@@ -847,6 +847,52 @@ int nunif_hip_png_encode_planes(const float *colour, const float *alpha, int32_t
 int nunif_hip_png_debug_filtered_planes(const float *colour, const float *alpha, int32_t colour_channels, int32_t form, int32_t B,
                                         int32_t H, int32_t W, uint8_t *filtered, void *stream);
 
+/* iw3 --depth-model Any_V3_Mono / Any_V3_Mono_01: what iw3/depth_anything_v3_model.py wraps around the Depth-Anything-3 backbone,
+ * and iw3.da3mono_disparity (iw3/models/da3mono_disparity.py).  The backbone itself is an external hub net and is not part of the
+ * engine.  All maps are f32 device [B][H*W] (B <= 4096, 1 <= H, W <= 8192, H * W >= 3; anything else, or a NULL or too small
+ * workspace, answers NUNIF_HIP_EINVAL before anything is launched).  No entry synchronises with the host.  NaN inputs are out of
+ * contract (the order-preserving keys sort them past the infinities, torch.sort puts every NaN last; a NaN sky value counts as not
+ * sky, as in torch); -0.0 sorts before +0.0 where torch.sort keeps them in input order (equal as values).  Workspaces are
+ * caller-owned device bytes, 16-byte aligned, of at least the size the matching *_workspace_bytes answers (-1 for a bad shape), so
+ * calls on different streams never share scratch; every call clears what it uses.  Results are integer counts and per-pixel
+ * formulas only: bit-equal across calls and streams.
+ *
+ * da3_disparity replaces _forward :33-56 for the whole batch: w = (clamp(sky, t, 1) - t) / (1 - t) (:35), sky mask = sky > t
+ *   (:34), the non-sky count m on the device (:40; the reference reads it on the host per image).
+ *   raw_output == 0: out = 0 where m < 10 (:41-43), else (1 / (depth + shift)) * (1 - w) (:47-49; the reference's shift is 0.2),
+ *     one rounding per operation in that order.
+ *   raw_output != 0: q = the 0.99 quantile of depth[~sky_mask] (:51) = a + (b - a) * frac(p) with p = 0.99 * (m - 1) and a, b
+ *     the order statistics floor(p), ceil(p), found by an exact radix selection over the masked pixels (no sort, no compaction);
+ *     out = min(depth * (1 - w) + w * q, q) (:52).  p and the interpolation are evaluated in double and rounded once (torch
+ *     forms p in fp32, which drifts by whole ranks once m passes 2^24 / 100).  DIVERGENCE: with m == 0 the reference raises
+ *     (torch.quantile of an empty tensor); the engine cannot stop the host and writes zeros.
+ * da3_disparity_debug_stats (tests only): a, b, q ([B][3] f32) and m ([B] i32) of the last raw call that ran on `workspace`.
+ *
+ * da3mono_features replaces DA3MonoDisparity.extract_features :53-73: out [B][64] = minimum, the order statistics ranks[0..61],
+ *   maximum of each image, bit-equal to indexing torch.sort's output.  ranks: 62 int64 on the DEVICE, the values of
+ *   torch.linspace(1, n - 2, 62).long() (:65) computed once per n on the host by that expression; the kernels do not re-derive
+ *   them (out-of-range values are clamped to [0, n - 1]).  One selection serves all 64 ranks of an image: four 8-bit levels,
+ *   each one histogram pass over the map shared by every rank, whatever the values are (constant and two-valued maps included).
+ *
+ * da3mono: create() takes the MLP of forward :29-50 packed by nunif_amd/iw3/models/da3mono_disparity.py pack_weights, all f32:
+ *   mlp.0.wt [64][128] and mlp.2.wt [128][128] (the Linear weights transposed), mlp.4.weight [2][128], mlp.{0,2,4}.bias.
+ *   forward: the features, the 64 -> 128 -> 128 -> 2 MLP (SiLU, SiLU, ReLU; fp32 operands and activations, sums in double) ->
+ *   (shift, sky_shift) per image, then out = 1 / ((depth == max ? depth + sky_shift : depth) + shift) with max = feature 63
+ *   (:37-48; the 3-D form of the reference is B = 1). */
+int64_t nunif_hip_da3_disparity_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int nunif_hip_da3_disparity(const float *depth, const float *sky, int32_t B, int32_t H, int32_t W, double sky_thresh, double shift,
+                            int32_t raw_output, float *out, void *workspace, int64_t workspace_bytes, void *stream);
+int nunif_hip_da3_disparity_debug_stats(const void *workspace, int32_t B, float *stats, int32_t *counts, void *stream);
+int64_t nunif_hip_da3mono_features_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int nunif_hip_da3mono_features(const float *depth, int32_t B, int32_t H, int32_t W, const int64_t *ranks, float *out,
+                               void *workspace, int64_t workspace_bytes, void *stream);
+typedef struct nunif_da3mono nunif_da3mono;
+int nunif_hip_da3mono_create(const nunif_tensor_desc *tensors, int32_t n_tensors, nunif_da3mono **handle);
+void nunif_hip_da3mono_destroy(nunif_da3mono *handle);
+int64_t nunif_hip_da3mono_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int nunif_hip_da3mono_forward(nunif_da3mono *handle, const float *depth, int32_t B, int32_t H, int32_t W, const int64_t *ranks,
+                              float *out, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* Test hooks (tests/ only): snapshot every stage's NHWC fp16 output during the next forward calls, then read
  * them back one by one (returns 1 past the last tap).  Names match oracle.swin_unet.unet_forward(taps=...). */
 int nunif_hip_swin_unet_debug_taps(nunif_swin_unet *handle, int32_t enable);

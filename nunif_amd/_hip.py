@@ -244,6 +244,16 @@ SIGNATURES = {
     "nunif_hip_cliqa_forward": (c_int32, [c_void_p, c_void_p] + [c_int32] * 4 + [c_void_p, c_int64] + [c_void_p] * 3),
     "nunif_hip_cliqa_debug_taps": (c_int32, [c_void_p, c_void_p] + [c_int32] * 4 + [c_void_p, c_int64] + [c_void_p] * 7),
     "nunif_hip_cliqa_select_patches": (c_int32, [c_void_p] + [c_int32] * 4 + [c_void_p] * 4),
+    "nunif_hip_da3_disparity_workspace_bytes": (c_int64, [c_int32] * 3),
+    "nunif_hip_da3_disparity": (c_int32, [c_void_p, c_void_p] + [c_int32] * 3 + [c_double, c_double, c_int32, c_void_p, c_void_p,
+                                                                                 c_int64, c_void_p]),
+    "nunif_hip_da3_disparity_debug_stats": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "nunif_hip_da3mono_features_workspace_bytes": (c_int64, [c_int32] * 3),
+    "nunif_hip_da3mono_features": (c_int32, [c_void_p] + [c_int32] * 3 + [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "nunif_hip_da3mono_create": (c_int32, [ctypes.POINTER(TensorDesc), c_int32, ctypes.POINTER(c_void_p)]),
+    "nunif_hip_da3mono_destroy": (None, [c_void_p]),
+    "nunif_hip_da3mono_workspace_bytes": (c_int64, [c_int32] * 3),
+    "nunif_hip_da3mono_forward": (c_int32, [c_void_p, c_void_p] + [c_int32] * 3 + [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "nunif_hip_swin_unet_debug_taps":(c_int32, [c_void_p, c_int32]),
     "nunif_hip_swin_unet_get_tap": (c_int32, [c_void_p, c_int32, c_char_p, c_int32, c_void_p, c_int64,
                                               ctypes.POINTER(c_int64)]),
