@@ -108,7 +108,7 @@ int nunif_hip_swin_unet_render(nunif_swin_unet *handle, const float *x, float *y
  *   stitch_rows       the single-pass stitch of output rows [y_row_begin, y_row_end) into a compact [3][rows][y_w] band.
  * Same tile grid, same tile store layout and the same stitch kernel as nunif_hip_swin_unet_render: bit-identical results.
  * The tile store is defined only where a stitch of the frame reads it: of a tile of the last tile row / column, the pixels past the
- * frame's edge are not written by a frame render (NUNIF_SWIN_SKIP_PAD: 0 whole tiles, 1 level-1 C = 96 blocks only, default 2 every fast block), and a band exported by tile_row_band
+ * frame's edge are not written by a frame render (NUNIF_SWIN_SKIP_PAD: 0 whole tiles, 1 level-1 C = 96 blocks only, 2 every fast block, default 3 PatchDown2 / PatchUp as well), and a band exported by tile_row_band
  * carries whatever the store held there.  No stitch reads those pixels on either side of an exchange. */
 int nunif_hip_swin_unet_render_tile_rows(nunif_swin_unet *handle, const float *x, int32_t x_h, int32_t x_w,
                                          int32_t tile_size, int32_t batch_size, int32_t row_begin, int32_t row_end,
@@ -147,6 +147,31 @@ typedef struct {
 } nunif_swin_tail_group;
 int nunif_hip_swin_unet_tail_groups(const nunif_swin_block_extent *ext, int32_t n_tiles, int32_t S, int32_t shift,
                                     nunif_swin_tail_group *out, int64_t cap, int64_t *n_groups, int64_t *n_tokens);
+
+/* What the producers of a frame render have to write (NUNIF_SWIN_SKIP_PAD level 3, where down2, up2 and up1 use it; host-only integer math, like the extents above): a
+ * producer — the stem, PatchDown down1 / down2, PatchUp up2 / up1 — leaves a token out only if no launch of this frame reads it.
+ * ext[n_tiles][n_blocks]: every block's extent of each tile of a minibatch (nunif_hip_swin_unet_tile_extents); listed[n_blocks]: 1 =
+ * the block runs its active windows only, 0 = it runs whole tiles and so reads every token (NULL: all 1); S: side of the level-1
+ * token map; f1_whole: 1 = something reads the whole level-1 map (proj2 of the 4x net), so the stem writes all of it.
+ * Per tile and axis a stage's read set is the union of its blocks' active windows, BOTH halves of a wrap window, and a tile's set is
+ * the product of its two axes; the sets follow the 2 x 2 relations back from swin5 to the stem (swin_producer_tokens_host.h has the
+ * recurrence).  Written is a superset of read: no launch reads what this frame did not write.
+ * Token producers (DOWN1 / DOWN2: the OUTPUT map, side S / 2 and S / 4; UP2 / UP1: the INPUT map, side S / 4 and S / 2, every listed
+ * token writes its four children): out = token (tile * Ss + y) * Ss + x in ascending order, each once, then filled up to a multiple
+ * of 32 entries with the last token.  STEM: out = the patches of patch_h x patch_w output tokens that hold a wanted token,
+ * (tile * nty + ty) * ntx + tx with nty / ntx = patches per tile side, rounded up.  out == NULL only counts; cap: entries `out`
+ * holds (fill included; fewer than needed is an error).  n_out: tokens / patches before the fill. */
+enum { NUNIF_SWIN_PRODUCER_STEM = 0, NUNIF_SWIN_PRODUCER_DOWN1 = 1, NUNIF_SWIN_PRODUCER_DOWN2 = 2, NUNIF_SWIN_PRODUCER_UP2 = 3,
+       NUNIF_SWIN_PRODUCER_UP1 = 4 };
+int nunif_hip_swin_unet_producer_tokens(const nunif_swin_block_extent *ext, int32_t n_tiles, const int32_t *blocks_per_stage,
+                                        const int32_t *shifts, const int32_t *listed, int32_t S, int32_t f1_whole, int32_t producer,
+                                        int32_t patch_h, int32_t patch_w, uint32_t *out, int64_t cap, int64_t *n_out);
+
+/* Tests only: ONE PatchDown2 launch pair on caller buffers (device memory): a [B, 2 Ho, 2 Wo, 192] fp16 -> out [B, Ho, Wo, 192] fp16,
+ * the first tap row written, the second accumulated onto it.  acc_form: 1 = the second pass on the prefetching PatchDown kernel,
+ * 0 = on the generic resident-weight GEMM; the two give the same bits. */
+int nunif_hip_swin_unet_down2_test(nunif_swin_unet *handle, const void *a, void *out, int32_t B, int32_t Ho, int32_t Wo,
+                                   int32_t acc_form, void *stream);
 
 /* Tests only: ONE launch of the C = 192 tail of block `block` of stage `stage` (1 .. 3, or 4 on the 4x net) on caller buffers (device
  * memory): att and x are [n_tokens][192] fp16, x is updated in place.  groups == NULL: every token; else a device copy of a table

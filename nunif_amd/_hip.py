@@ -99,6 +99,10 @@ SIGNATURES = {
                                                    c_int32, ctypes.POINTER(SwinBlockExtent)]),
     "nunif_hip_swin_unet_tail_groups": (c_int32, [ctypes.POINTER(SwinBlockExtent), c_int32, c_int32, c_int32,
                                                   ctypes.POINTER(SwinTailGroup), c_int64, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
+    "nunif_hip_swin_unet_producer_tokens": (c_int32, [ctypes.POINTER(SwinBlockExtent), c_int32, ctypes.POINTER(c_int32), ctypes.POINTER(c_int32),
+                                                      ctypes.POINTER(c_int32), c_int32, c_int32, c_int32, c_int32, c_int32,
+                                                      ctypes.POINTER(ctypes.c_uint32), c_int64, ctypes.POINTER(c_int64)]),
+    "nunif_hip_swin_unet_down2_test": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "nunif_hip_swin_unet_tail192_test": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64,
                                                    c_int32, c_void_p]),
     "nunif_hip_swin_unet_v2_create": (c_int32, [ctypes.POINTER(TensorDesc), c_int32, c_int32, ctypes.POINTER(c_void_p)]),
@@ -335,6 +339,35 @@ def swin_tail_groups(extents, S, shift):
     if ng.value:
         check(lib().nunif_hip_swin_unet_tail_groups(ext, len(extents), S, shift, out, ng.value, ctypes.byref(ng), ctypes.byref(nt)))
     return (SwinTailGroup * ng.value).from_buffer(out) if ng.value else (SwinTailGroup * 0)(), nt.value
+
+
+SWIN_PRODUCERS = {"stem": 0, "down1": 1, "down2": 2, "up2": 3, "up1": 4}
+
+
+def swin_producer_tokens(extents, S, producer, blocks_per_stage=(2, 2, 6, 2, 2), shifts=None, listed=None, f1_whole=False,
+                         patch=(24, 16)):
+    """What one producer of a frame render writes over a tile minibatch (``nunif_hip_swin_unet_producer_tokens``; host-only integer
+    math).  ``extents``: per tile the list ``swin_tile_extents`` returns; ``producer``: a key of ``SWIN_PRODUCERS``.  Returns
+    ``(entries, n)``: the table as the kernels walk it (token producers: filled up to whole groups of 32) and the count before the fill."""
+    n_blocks = sum(blocks_per_stage)
+    if shifts is None:
+        shifts = [3 if i % 2 else 0 for k in blocks_per_stage for i in range(k)]
+    ext = (SwinBlockExtent * (len(extents) * n_blocks))()
+    for t, tile in enumerate(extents):
+        assert len(tile) == n_blocks
+        for i, (ny, nx, wy, wx) in enumerate(tile):
+            e = ext[t * n_blocks + i]
+            e.n_win[0], e.n_win[1], e.wrap[0], e.wrap[1] = ny, nx, wy, wx
+    per = (c_int32 * 5)(*blocks_per_stage)
+    sh = (c_int32 * n_blocks)(*shifts)
+    li = (c_int32 * n_blocks)(*[1 if v else 0 for v in listed]) if listed is not None else None
+    args = (ext, len(extents), per, sh, li, S, 1 if f1_whole else 0, SWIN_PRODUCERS[producer], patch[0], patch[1])
+    n = c_int64(0)
+    check(lib().nunif_hip_swin_unet_producer_tokens(*args, None, 0, ctypes.byref(n)))
+    cap = (n.value + 31) // 32 * 32
+    out = (ctypes.c_uint32 * max(1, cap))()
+    check(lib().nunif_hip_swin_unet_producer_tokens(*args, out, cap, ctypes.byref(n)))
+    return list(out)[:n.value if producer == "stem" else cap], n.value
 
 
 def blend_ramp(blend_size):

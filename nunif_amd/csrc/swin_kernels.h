@@ -41,7 +41,10 @@ int launch_gemm(const GemmArgs &g, hipStream_t s, const char *tag);
 // a: [B, Ho, Wo, 192]; w / bias: make_linear's packing with columns n = q Cq + c (q = 2 i + j the sub-pixel); res / out:
 // [B, 2 Ho, 2 Wo, Cq] (out may alias res).  Cq = 96 or 192.  Weights resident in LDS, persistent workgroups, the next token
 // group's activations and the skip tiles of the next four trips in flight.
-struct PatchUpArgs { const f16 *a, *w; const float *bias; const f16 *res; f16 *out; int B, Ho, Wo, Cq, rev; };
+// list (frame renders, swin_unet.cpp skip_plan): the launch walks the n_list INPUT tokens list[] names, (b Ho + y) Wo + x, instead of all
+// B Ho Wo; list[] holds whole groups of 32 entries (the last one filled up with its last token)
+struct PatchUpArgs { const f16 *a, *w; const float *bias; const f16 *res; f16 *out; int B, Ho, Wo, Cq, rev;
+                     const unsigned *list = nullptr; unsigned n_list = 0; };
 bool patchup_supported(const PatchUpArgs &g);
 int launch_patchup(const PatchUpArgs &g, hipStream_t s);
 
@@ -49,8 +52,11 @@ int launch_patchup(const PatchUpArgs &g, hipStream_t s);
 // a: [B, 2 Ho, 2 Wo, Cin]; Cin = 96: K = 384 = the four taps (dy, dx) of a token, k = (2 dy + dx) Cin + c; Cin = 192: K = 384 = the
 // two taps of input row 2 y + oy (the other row is a second, accumulating pass on gemm_res_kernel); Cin = 64, N = 64: cunet's
 // Conv2d(64, 64, 2, 2) + LeakyReLU.  w / bias: make_linear's packing ([n-tile][k-step]).
-struct PatchDownArgs { const f16 *a, *w; const float *bias; f16 *out; int B, Ho, Wo, Cin, oy, rev; int N = 192; int act = 0; float slope = 0.f; };     // act 2: LeakyReLU(slope)
+// list: as PatchUpArgs', OUTPUT tokens.  acc (Cin = 192): out += the pass, as gemm_res_kernel<12,2> with out as its residual computes it.
+struct PatchDownArgs { const f16 *a, *w; const float *bias; f16 *out; int B, Ho, Wo, Cin, oy, rev; int N = 192; int act = 0; float slope = 0.f;      // act 2: LeakyReLU(slope)
+                       const unsigned *list = nullptr; unsigned n_list = 0; int acc = 0; };
 bool patchdown_supported(const PatchDownArgs &g);
+bool patchdown_acc_enabled();
 int launch_patchdown(const PatchDownArgs &g, hipStream_t s);
 
 // ---- cunet's up step (cunet_up.hip): out[B, 2S, 2S, 64] = LeakyReLU(pixel_shuffle_2(Linear(64 -> 256)(in_scale * a))) + crop(res) ---

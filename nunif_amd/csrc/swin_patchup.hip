@@ -19,6 +19,11 @@
 //   * bias is the MFMA C operand (accumulators start from it), token coordinates are 32-bit divisions once per group.
 // Operand orientation as everywhere (swin_kernels.hip): weights = A (rows = output channels), activations = B (columns = tokens); a
 // lane's accumulator is 4 consecutive channels of one token, two adjacent tiles leave as one 16-byte run per lane (pair_to_run).
+//
+// LISTED instances (frame renders, swin_unet.cpp skip_plan): the launch walks the INPUT tokens a table names instead of all of them,
+// and only their 2 x 2 children are read and rewritten.  Only coords() differs, as in swin_patchdown.hip: a lane's token comes from
+// the table, requested one group earlier than the group whose loads it addresses, so that request is the oldest one outstanding
+// where it is waited for.  The table holds whole groups (its fill repeats the last token: the clamp of the whole-tile form).
 #include <algorithm>
 #include <cstdlib>
 
@@ -42,7 +47,7 @@ static_assert(kSmem <= 160 * 1024, "LDS");
 static_assert(kTrips % kD == 0, "the ring slot of a trip is static");
 }  // namespace
 
-template <int CQ>
+template <int CQ, bool LISTED = false>
 __global__ void __launch_bounds__(kWaves * 64) patchup_kernel(PatchUpArgs g) {
     constexpr int HALVES = 4 * CQ / (kNT * 16);      // 1 (Cq = 96) or 2 (Cq = 192: workgroup parity picks the sub-pixel row)
     static_assert(HALVES == 1 || HALVES == 2, "Cq is 96 or 192");
@@ -66,7 +71,7 @@ __global__ void __launch_bounds__(kWaves * 64) patchup_kernel(PatchUpArgs g) {
     }
 
     const unsigned Wo = (unsigned)g.Wo, Ho = (unsigned)g.Ho;
-    const unsigned M = (unsigned)g.B * Ho * Wo;
+    const unsigned M = LISTED ? g.n_list : (unsigned)g.B * Ho * Wo;
     const unsigned n_groups = (M + kMF * 16 - 1) / (kMF * 16);
     const unsigned step = nwb * kWaves;
     unsigned gi = wb * kWaves + wave;
@@ -80,15 +85,26 @@ __global__ void __launch_bounds__(kWaves * 64) patchup_kernel(PatchUpArgs g) {
         return (unsigned)(((q >> 1) * 2 * Wo + (q & 1)) * CQ + c);
     };
     struct Grp { unsigned pix[kMF], xo[kMF]; };      // BYTE offsets (32 bits: launcher guard), added to a wave-uniform base
-    auto coords = [&](unsigned gidx, Grp &c) {
+    struct Tok { unsigned m[kMF]; };                 // LISTED: a group's tokens as the table names them
+    auto fetch_tok = [&](unsigned gidx, Tok &t) {
+        const unsigned gg = g.rev ? n_groups - 1 - gidx : gidx;
+#pragma unroll
+        for (int f = 0; f < kMF; ++f) t.m[f] = g.list[gg * (kMF * 16) + f * 16 + r16];
+    };
+    auto coords = [&](unsigned gidx, const Tok &tk, Grp &c) {
         const unsigned gg = g.rev ? n_groups - 1 - gidx : gidx;
 #pragma unroll
         for (int f = 0; f < kMF; ++f) {
             // rows beyond M are clamped to the last token: such a lane loads what the last token's own lane loads and stores the same
             // values to the same address in the same instruction — no mask, hence no branch around the stores (a conditional store
             // also hides itself from hipcc's vmcnt bookkeeping: every wait in front of a skip tile then drained the ring)
-            unsigned m = gg * (kMF * 16) + f * 16 + r16;
-            m = m < M ? m : M - 1;
+            unsigned m;
+            if constexpr (LISTED) {
+                m = tk.m[f];
+            } else {
+                m = gg * (kMF * 16) + f * 16 + r16;
+                m = m < M ? m : M - 1;
+            }
             const unsigned t = m / Wo, x = m - t * Wo;
             const unsigned b = t / Ho, y = t - b * Ho;
             c.xo[f] = (m * (kKS * 32) + grp * 8) * 2;
@@ -112,7 +128,14 @@ __global__ void __launch_bounds__(kWaves * 64) patchup_kernel(PatchUpArgs g) {
     Grp cur, nxt;
     f16x8 xc[kMF][kKS], xn[kMF][kKS];
     f16x8 rr[kD][kMF];
-    coords(any ? gi : 0, cur);
+    Tok tnx = {};                                    // LISTED: the tokens of the NEXT group
+    if constexpr (LISTED) {
+        fetch_tok(any ? gi : 0, tnx);
+        coords(any ? gi : 0, tnx, cur);
+        fetch_tok(gi + step < n_groups ? gi + step : (any ? gi : 0), tnx);
+    } else {
+        coords(any ? gi : 0, tnx, cur);
+    }
     load_x(cur, xc);
 #pragma unroll
     for (int t = 0; t < kD; ++t) load_res(cur, t, rr[t]);
@@ -125,6 +148,7 @@ __global__ void __launch_bounds__(kWaves * 64) patchup_kernel(PatchUpArgs g) {
         for (int ks = 0; ks < kKS; ++ks) asm volatile("" : "+v"(xc[f][ks]));
 #pragma unroll
         for (int t = 0; t < kD; ++t) asm volatile("" : "+v"(rr[t][f]));
+        if constexpr (LISTED) asm volatile("" : "+v"(tnx.m[f]));
     }
     __syncthreads();
     if (!any) return;
@@ -132,7 +156,12 @@ __global__ void __launch_bounds__(kWaves * 64) patchup_kernel(PatchUpArgs g) {
     while (true) {
         const unsigned gn = gi + step;
         const bool has_next = gn < n_groups;                       // wave-uniform
-        coords(has_next ? gn : gi, nxt);                           // (no next group: harmless re-reads of this one)
+        coords(has_next ? gn : gi, tnx, nxt);                      // (no next group: harmless re-reads of this one)
+        if constexpr (LISTED) {
+            // the group after the next one (none: any valid group, its tokens are never used)
+            const unsigned g2 = gn + step;
+            fetch_tok(g2 < n_groups ? g2 : gi, tnx);
+        }
         load_x(nxt, xn);
         // the fragments are the same for every group: without an opaque offset hipcc hoists all 144 LDS reads out of the loop
         // (576 registers, spilled)
@@ -212,17 +241,21 @@ bool patchup_supported(const PatchUpArgs &g) {
     if (const char *e = getenv("NUNIF_PATCHUP")) if (atoi(e) == 0) return false;       // read per call (A/B runs)
     const long M = (long)g.B * g.Ho * g.Wo;
     // byte offsets into the activations (384 B per token) and the output map (8 Cq B per token) are 32-bit
-    return (g.Cq == 96 || g.Cq == 192) && g.res && M > 0 && M * 384 < (1L << 32) && M * 8 * g.Cq < (1L << 32);
+    // (a listed launch addresses the same maps: the guards are the whole map's; its table holds whole groups)
+    const bool list_ok = !g.list || (g.n_list > 0 && (long)g.n_list <= M);
+    return (g.Cq == 96 || g.Cq == 192) && g.res && M > 0 && M * 384 < (1L << 32) && M * 8 * g.Cq < (1L << 32) && list_ok;
 }
 
 int launch_patchup(const PatchUpArgs &g, hipStream_t s) {
     NUNIF_REQUIRE(g.a && g.w && g.bias && g.res && g.out && patchup_supported(g), "patchup: bad argument");
-    const long M = (long)g.B * g.Ho * g.Wo;
+    const long M = g.list ? (long)g.n_list : (long)g.B * g.Ho * g.Wo;
     static bool configured = false;
     static int cus = 256;
     if (!configured) {
         NUNIF_HIP_CHECK(hipFuncSetAttribute((const void *)patchup_kernel<96>, hipFuncAttributeMaxDynamicSharedMemorySize, kSmem));
         NUNIF_HIP_CHECK(hipFuncSetAttribute((const void *)patchup_kernel<192>, hipFuncAttributeMaxDynamicSharedMemorySize, kSmem));
+        NUNIF_HIP_CHECK(hipFuncSetAttribute((const void *)patchup_kernel<96, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kSmem));
+        NUNIF_HIP_CHECK(hipFuncSetAttribute((const void *)patchup_kernel<192, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kSmem));
         int dev = 0;
         NUNIF_HIP_CHECK(hipGetDevice(&dev));
         NUNIF_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
@@ -234,7 +267,13 @@ int launch_patchup(const PatchUpArgs &g, hipStream_t s) {
     const unsigned grid = (unsigned)(per_half * halves);
     const double flops = 2.0 * (double)M * 192.0 * 4.0 * g.Cq;
     const double bytes = (double)M * (192.0 * 2.0 + 4.0 * g.Cq * 2.0 * 2.0);
-    if (g.Cq == 96) {
+    if (g.list && g.Cq == 96) {
+        ProfScope ps("patchup_kernel<96,listed>", s, flops, bytes);
+        patchup_kernel<96, true><<<grid, kWaves * 64, kSmem, s>>>(g);
+    } else if (g.list) {
+        ProfScope ps("patchup_kernel<192,listed>", s, flops, bytes);
+        patchup_kernel<192, true><<<grid, kWaves * 64, kSmem, s>>>(g);
+    } else if (g.Cq == 96) {
         ProfScope ps("patchup_kernel<96>", s, flops, bytes);
         patchup_kernel<96><<<grid, kWaves * 64, kSmem, s>>>(g);
     } else {

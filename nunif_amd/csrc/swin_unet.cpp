@@ -12,6 +12,7 @@
 
 #include "host_weights.h"
 #include "swin_kernels.h"
+#include "swin_producer_tokens_host.h"
 #include "swin_tail_groups_host.h"
 
 namespace nunif {
@@ -60,14 +61,28 @@ struct SkipBlock {
     int n_windows = 0;
 };
 
+// What a producer launch of a frame render walks (level 3, nunif_hip_swin_unet_producer_tokens): `n` output tokens (PatchDown), input
+// tokens (PatchUp) or output patches (the stem).  list == NULL: the whole-tile launch.
+struct ProducerList {
+    const unsigned *list = nullptr;
+    unsigned n = 0;
+};
+
 // One plan per (grid, tile minibatch).  Everything of a plan lives in ONE device allocation: the lists of its blocks (uploaded
 // once, `host` keeps the source alive for the asynchronous copy) and behind them the token tables, which a kernel builds from
 // the lists on the stream that first uses the plan (launch_winmap_list_build) — `ready` orders any other stream behind that.
 struct SkipPlan {
     nunif_tile_grid grid = {};
     int tile_begin = 0, B = 0;
-    int level = 0;                        // NUNIF_SWIN_SKIP_PAD of the call that built it: 1 = level-1 C = 96 blocks only, 2 = all fast blocks
+    int level = 0;                        // NUNIF_SWIN_SKIP_PAD of the call that built it: 1 = level-1 C = 96 blocks only, 2 = all fast blocks,
+                                          // 3 = the producers as well
     std::vector<SkipBlock> stage[5];      // empty where the stage runs whole
+    // level 3: indexed by NUNIF_SWIN_PRODUCER_*.  list == NULL: that producer runs whole tiles — the stem and down1 always (their lists
+    // measured no faster), the others where their set is the whole map.  That is safe in any mix: a whole-tile producer WRITES a superset,
+    // and what it READS is whole only behind producers that write whole maps too (the stem and down1 in front of everything; a whole set
+    // of up2 / up1 makes every set in front of it whole through the recurrence)
+    ProducerList producer[5];
+    bool producers = false;
     void *dev = nullptr;
     size_t bytes = 0;
     std::vector<unsigned> host;
@@ -140,6 +155,17 @@ extern "C" int nunif_hip_swin_unet_tile_extents(const nunif_tile_grid *g, int32_
 }
 
 // Pure integer host function (declared in nunif_hip.h): swin_tail_groups_host.h
+// Pure integer host function (declared in nunif_hip.h): swin_producer_tokens_host.h
+extern "C" int nunif_hip_swin_unet_producer_tokens(const nunif_swin_block_extent *ext, int32_t n_tiles, const int32_t *blocks_per_stage,
+                                                   const int32_t *shifts, const int32_t *listed, int32_t S, int32_t f1_whole,
+                                                   int32_t producer, int32_t patch_h, int32_t patch_w, uint32_t *out, int64_t cap,
+                                                   int64_t *n_out) {
+    const char *msg = swin_producer_tokens_host(ext, n_tiles, blocks_per_stage, shifts, listed, S, f1_whole, producer, patch_h, patch_w,
+                                                out, cap, n_out);
+    NUNIF_REQUIRE(!msg, "%s", msg);
+    return NUNIF_HIP_OK;
+}
+
 extern "C" int nunif_hip_swin_unet_tail_groups(const nunif_swin_block_extent *ext, int32_t n_tiles, int32_t S, int32_t shift,
                                                nunif_swin_tail_group *out, int64_t cap, int64_t *n_groups, int64_t *n_tokens) {
     const char *msg = swin_tail_groups_host(ext, n_tiles, S, shift, out, cap, n_groups, n_tokens);
@@ -386,19 +412,27 @@ int run_gemm(const Linear &L, const f16 *a, int B, int Hi, int Wi, int Cin, int 
 
 // x = PatchUp(a) + skip, in place over the skip map (swin_unet.py:65-82,189-196): the resident-weight kernel when it takes the
 // shape (every launch of that shape, whatever the batch: results must not depend on the tile minibatch), else the generic GEMM
-int run_patchup(const Linear &L, const f16 *a, int B, int H, int W, int Cq, f16 *skip, hipStream_t s, const char *tag, int rev) {
+// `pl` (frame renders): only the listed input tokens; a launch that cannot take the list is an error, never a whole-tile launch
+int run_patchup(const Linear &L, const f16 *a, int B, int H, int W, int Cq, f16 *skip, hipStream_t s, const char *tag, int rev,
+                const ProducerList *pl = nullptr) {
     PatchUpArgs p = {a, L.w, L.bias, skip, skip, B, H, W, Cq, rev};
+    if (pl && pl->list) { p.list = pl->list; p.n_list = pl->n; }
     if (L.K == 192 && L.n_real == 4 * Cq && patchup_supported(p)) return launch_patchup(p, s);
+    NUNIF_REQUIRE(!p.list, "%s: no listed form of this PatchUp", tag);
     return run_gemm(L, a, B, H, W, L.K, H, W, 1, 0, 0, 1, 1, 0, 0.f, skip, skip, Cq, 1, s, tag, rev);
 }
 
 // PatchDown pass without a residual (swin_unet.py:45-62): a [B, 2 Ho, 2 Wo, Cin] -> out [B, Ho, Wo, 192], K = 384 = the taps of
 // input row(s) 2 y + oy ..; the K-outer prefetching kernel when it takes the shape (every launch of that shape), else the generic GEMM
+// acc: out += the pass (down2's second tap row).  `pl` as run_patchup's, output tokens.
 int run_patchdown(const Linear &L, const f16 *a, int B, int Ho, int Wo, int Cin, int oy, f16 *out, hipStream_t s, const char *tag,
-                  int rev) {
+                  int rev, const ProducerList *pl = nullptr, int acc = 0) {
     PatchDownArgs p;
-    p.a = a; p.w = L.w; p.bias = L.bias; p.out = out; p.B = B; p.Ho = Ho; p.Wo = Wo; p.Cin = Cin; p.oy = oy; p.rev = rev;
+    p.a = a; p.w = L.w; p.bias = L.bias; p.out = out; p.B = B; p.Ho = Ho; p.Wo = Wo; p.Cin = Cin; p.oy = oy; p.rev = rev; p.acc = acc;
+    if (pl && pl->list) { p.list = pl->list; p.n_list = pl->n; }
     if (L.K == 384 && L.n_real == 192 && patchdown_supported(p)) return launch_patchdown(p, s);
+    NUNIF_REQUIRE(!p.list, "%s: no listed form of this PatchDown", tag);
+    if (acc) return run_gemm(L, a, B, 2 * Ho, 2 * Wo, Cin, Ho, Wo, 2, oy, 0, 2, 0, 0, 0.f, out, out, L.n_real, 1, s, tag, rev);
     return run_gemm(L, a, B, 2 * Ho, 2 * Wo, Cin, Ho, Wo, 2, oy, 0, 2, 0, 0, 0.f, nullptr, out, L.n_real, 1, s, tag, rev);
 }
 
@@ -535,17 +569,26 @@ int ensure_workspace(nunif_swin_unet *h, int B, int T) {
 // The window lists of tile minibatch [t0, t0 + B) of grid g (frame entry points only).  What a tile runs depends on the grid and
 // the tile's index alone — never on the minibatch or the stream — so any split of a frame into minibatches computes the same bits.
 //
-// INVARIANT the skipping rests on: the stem, PatchDown, PatchUp and the un-fused to_image always process WHOLE tiles, so every
-// activation map is fully rewritten from the current frame before a block reads it; a token a block skips keeps that block's
-// input (finite, a function of the current frame).  The far half of a shifted block's wrap window is read as masked keys whose
-// softmax weight is an exact fp16 zero, and 0 x finite = 0 where 0 x a stale Inf / NaN would not be.  Every stage whose blocks are
-// all `fast` skips (level 2; level 1: the level-1 C = 96 stages only).  A C = 96 tail walks the compact list through `pixmap`, and
-// the compact att map is written in full before it is read; a C = 192 tail walks the tokens of exactly the windows its attention
-// ran (`groups`), so it reads no att the launch before it did not write and updates every listed token exactly once (it works in
-// place on x).  The generic block path runs whole tiles, which is a superset of what its consumers need.
+// INVARIANT the skipping rests on: WRITTEN IS A SUPERSET OF READ — no launch of a frame render reads a token that no launch of the
+// same frame wrote before it, so nothing stale (a previous frame's or geometry's values, finite or not) is ever an operand.
+//   * Blocks.  A block that lists reads and updates, in place, exactly the tokens of its listed windows, the far half of a shifted
+//     block's wrap window included (read as masked keys).  A C = 96 tail walks the compact list through `pixmap`, and the compact att
+//     map is written in full before it is read; a C = 192 tail walks the tokens of exactly the windows its attention ran (`groups`).
+//     A block that does not list (the generic path, a stage that is not all `fast`, a minibatch with nothing to leave out) runs whole
+//     tiles and reads every token of its map.
+//   * Producers (the stem, PatchDown down1 / both passes of down2, PatchUp up2 / up1).  Level 3: down2, up2 and up1 list (the stem and
+//     down1 run whole tiles, a superset: their lists measured no faster); a producer that lists writes the tokens that anything
+//     behind it in the frame reads — the read set of the consuming stage, the 2 x 2 parents of what a PatchDown must produce, the
+//     inputs of a PatchUp whose children are read, and the skip tokens a PatchUp adds onto in place
+//     (nunif_hip_swin_unet_producer_tokens has the recurrence) — and reads only what the producer in front of it wrote.  The
+//     lists are used together or not at all; a block that runs whole tiles makes its stage's read set the whole map.  Levels 0 - 2,
+//     tile mode, taps: every producer processes whole tiles, which is a superset of everything.
+//   * The un-fused to_image and the 4x net's proj2 run whole tiles: proj2 reads the whole level-1 map, so the stem of that net writes
+//     all of it (f1_whole), and the whole top map it writes is what the un-fused to_image reads.
 // Plan bytes per tile of 256 whose every block lists: 4 C = 96 blocks x 1 600 windows x 148 B + 2 200 windows of the 10 C = 192 blocks
 // x (4 B + 36 / 16 groups x 32 B) = 0.95 + 0.17 MB, so kMaxPlanBytes holds about 950 tiles: 21 geometries of 1080p (a plan lists every
-// tile of its minibatch once one of them has windows to leave out).
+// tile of its minibatch once one of them has windows to leave out).  The producer lists (down2, up2, up1) add 4 B per token: (14 400 + 2 x 3 600) x 4 B =
+// 0.09 MB per tile of 256.
 constexpr size_t kMaxPlans = 1024, kMaxPlanBytes = (size_t)1 << 30;
 
 int skip_plan(nunif_swin_unet *h, const nunif_tile_grid *g, int t0, int B, int level, hipStream_t s, const SkipPlan **out) {
@@ -568,10 +611,11 @@ int skip_plan(nunif_swin_unet *h, const nunif_tile_grid *g, int t0, int B, int l
         for (int i = 0; i < per_stage[st]; ++i) shifts.push_back(i % 2 == 1 ? 3 : 0);      // swin_unet.py:30
         n_blocks += per_stage[st];
     }
-    std::vector<std::vector<nunif_swin_block_extent>> ext(B, std::vector<nunif_swin_block_extent>(n_blocks));
+    std::vector<nunif_swin_block_extent> ext((size_t)B * n_blocks);          // [tile][block]
+    std::vector<int32_t> listed(n_blocks, 0);
     int rc;
     for (int b = 0; b < B; ++b)
-        if ((rc = nunif_hip_swin_unet_tile_extents(g, t0 + b, per_stage, shifts.data(), 0, ext[b].data()))) return rc;
+        if ((rc = nunif_hip_swin_unet_tile_extents(g, t0 + b, per_stage, shifts.data(), 0, &ext[(size_t)b * n_blocks]))) return rc;
     h->plans.emplace_front();
     SkipPlan &plan = h->plans.front();
     auto fail = [&](int code) { h->drop_plan(h->plans.begin()); return code; };
@@ -591,7 +635,7 @@ int skip_plan(nunif_swin_unet *h, const nunif_tile_grid *g, int t0, int B, int l
         for (int i = 0; i < per_stage[st]; ++i) {
             const size_t at = plan.host.size();
             for (int b = 0; b < B; ++b) {
-                const nunif_swin_block_extent &e = ext[b][first + i];
+                const nunif_swin_block_extent &e = ext[(size_t)b * n_blocks + first + i];
                 auto active = [&](int ax, int w) { return w < e.n_win[ax] || (e.wrap[ax] && w == nw - 1); };
                 for (int wy = 0; wy < nw; ++wy) {
                     if (!active(0, wy)) continue;
@@ -605,7 +649,7 @@ int skip_plan(nunif_swin_unet *h, const nunif_tile_grid *g, int t0, int B, int l
             if (dim == 192) {
                 // the same tokens in pixel order, 16 to a group: 8 words per group behind the list, 32-byte aligned
                 std::vector<nunif_swin_block_extent> eb(B);
-                for (int b = 0; b < B; ++b) eb[b] = ext[b][first + i];
+                for (int b = 0; b < B; ++b) eb[b] = ext[(size_t)b * n_blocks + first + i];
                 // (one pass: 36 n tokens fill ceil(36 n / 16) groups; the slack is for a group closed early, which the builder never needs)
                 const int64_t cap = (36 * (int64_t)n + 15) / 16 + 8;
                 plan.host.resize((plan.host.size() + 7) / 8 * 8);
@@ -619,9 +663,36 @@ int skip_plan(nunif_swin_unet *h, const nunif_tile_grid *g, int t0, int B, int l
                 if (pc.n_tokens != 36 * (int64_t)n) { set_error("internal: %lld grouped tokens for %zu windows", (long long)pc.n_tokens, n); return fail(NUNIF_HIP_EINVAL); }
             }
             pieces.push_back(pc);
+            listed[first + i] = 1;
         }
     }
     if (pieces.empty()) { *out = &plan; return NUNIF_HIP_OK; }       // (cached all the same: the next frame finds it)
+    // level 3: what the producers write, behind the lists in the same upload.  A producer with nothing to leave out keeps list == NULL
+    struct ProdPiece { int producer; size_t first; int64_t n; };
+    std::vector<ProdPiece> prods;
+    if (level >= 3 && h->C == 96 && h->down2_split && S % 24 == 0) {
+        // down2, up2, up1: the stem and down1 keep whole tiles (96 % of their work is listed on a 1080p frame, and their listed launches
+        // measured no faster than the whole ones: DESIGN.md 4.13b)
+        for (int pr = NUNIF_SWIN_PRODUCER_DOWN2; pr <= NUNIF_SWIN_PRODUCER_UP1; ++pr) {
+            const int Sp = pr == NUNIF_SWIN_PRODUCER_UP1 ? S / 2 : S / 4;
+            const int64_t whole = (int64_t)B * Sp * Sp;
+            int64_t n = 0;
+            if ((rc = nunif_hip_swin_unet_producer_tokens(ext.data(), B, per_stage, shifts.data(), listed.data(), S, h->has_proj2 ? 1 : 0, pr, 0,
+                                                          0, nullptr, 0, &n)))
+                return fail(rc);
+            if (n <= 0 || n > whole) { set_error("internal: producer %d lists %lld of %lld", pr, (long long)n, (long long)whole); return fail(NUNIF_HIP_EINVAL); }
+            if (n == whole) continue;
+            const int64_t cap = (n + 31) / 32 * 32;
+            plan.host.resize((plan.host.size() + 7) / 8 * 8);
+            const size_t at = plan.host.size();
+            plan.host.resize(at + (size_t)cap);
+            if ((rc = nunif_hip_swin_unet_producer_tokens(ext.data(), B, per_stage, shifts.data(), listed.data(), S, h->has_proj2 ? 1 : 0, pr, 0,
+                                                          0, &plan.host[at], cap, &n)))
+                return fail(rc);
+            prods.push_back({pr, at, n});
+        }
+        plan.producers = true;
+    }
     // layout: all lists and group tables (one upload) | C = 96 token tables (36 ints per listed window), the tables 256-byte aligned
     const size_t list_bytes = (plan.host.size() * 4 + 255) / 256 * 256;
     size_t n_pix = 0;
@@ -652,6 +723,10 @@ int skip_plan(nunif_swin_unet *h, const nunif_tile_grid *g, int t0, int B, int l
         pix_at += pc.n * 36;
         if ((rc = launch_winmap_list_build(sb.pixmap, sb.list, sb.n_windows, S, S, pc.shift, s))) return fail(rc);
     }
+    for (const ProdPiece &pp : prods) {
+        plan.producer[pp.producer].list = (const unsigned *)plan.dev + pp.first;
+        plan.producer[pp.producer].n = (unsigned)pp.n;
+    }
     if (hipEventRecord(plan.ready, s) != hipSuccess) { set_error("hipEventRecord failed"); return fail(NUNIF_HIP_EHIP); }
     while (h->plans.size() > kMaxPlans || (h->plan_bytes > kMaxPlanBytes && h->plans.size() > 1)) h->drop_plan(std::prev(h->plans.end()));
     *out = &plan;
@@ -669,6 +744,16 @@ int forward_impl(nunif_swin_unet *h, const float *x, const float *frame, const n
     if (frame && skip_pad && (rc = skip_plan(h, grid, tile_begin, B, skip_pad, s, &h->plan))) return rc;
     auto skip_of = [&](int st) { return h->plan && !h->plan->stage[st].empty() ? &h->plan->stage[st] : nullptr; };
     f16 *s1 = (f16 *)h->s1.p, *f1 = (f16 *)h->f1.p, *f2 = (f16 *)h->f2.p, *f3 = (f16 *)h->f3.p;
+    // level 3: the producers' lists, all of them or none (skip_plan's INVARIANT) — none where a listed kernel is switched off
+    bool lp = h->plan && h->plan->producers;
+    if (lp) {
+        PatchDownArgs d1, d2;
+        d1.B = B; d1.Ho = d1.Wo = S / 4; d1.Cin = 2 * (int)C; d1.oy = 0; d1.rev = 0;
+        d2 = d1; d2.oy = 1; d2.acc = 1;
+        PatchUpArgs u2 = {f3, nullptr, nullptr, f2, f2, B, S / 4, S / 4, 2 * (int)C, 0}, u1 = {f2, nullptr, nullptr, f1, f1, B, S / 2, S / 2, h->top_dim, 0};
+        lp = patchdown_supported(d1) && patchdown_supported(d2) && patchup_supported(u2) && patchup_supported(u1);
+    }
+    auto prod_of = [&](int pr) { return lp ? &h->plan->producer[pr] : nullptr; };
 
     if (h->stemf_w2 && stem_fused_supported(h->C1, (int)C)) {
         StemFusedArgs sf;
@@ -703,21 +788,22 @@ int forward_impl(nunif_swin_unet *h, const float *x, const float *frame, const n
 stem_done:
     if ((rc = tap(h, "stem", f1, (size_t)B * S * S * C * 2, s))) return rc;
     if ((rc = run_stage(h, h->swin[0], f1, B, S, C, s, "swin1", nullptr, skip_of(0)))) return rc;                          // swin1 -> x3
-    if ((rc = run_patchdown(h->down1, f1, B, S / 2, S / 2, C, 0, f2, s, "gemm_down1", next_dir(h)))) return rc;
+    if ((rc = run_patchdown(h->down1, f1, B, S / 2, S / 2, C, 0, f2, s, "gemm_down1", next_dir(h), prod_of(NUNIF_SWIN_PRODUCER_DOWN1)))) return rc;
     if ((rc = tap(h, "down1", f2, (size_t)B * (S / 2) * (S / 2) * 2 * C * 2, s))) return rc;
     if ((rc = run_stage(h, h->swin[1], f2, B, S / 2, 2 * C, s, "swin2", nullptr, skip_of(1)))) return rc;                  // swin2 -> x4
     if (h->down2_split) {
-        if ((rc = run_patchdown(h->down2, f2, B, S / 4, S / 4, 2 * C, 0, f3, s, "gemm_down2", next_dir(h)))) return rc;
+        if ((rc = run_patchdown(h->down2, f2, B, S / 4, S / 4, 2 * C, 0, f3, s, "gemm_down2", next_dir(h), prod_of(NUNIF_SWIN_PRODUCER_DOWN2)))) return rc;
     } else if ((rc = run_gemm(h->down2, f2, B, S / 2, S / 2, 2 * C, S / 4, S / 4, 2, 0, 0, 2, 0, 0, 0.f, nullptr, f3,
                               2 * C, 1, s, "gemm_down2", next_dir(h))))
         return rc;
-    if (h->down2_split && (rc = run_gemm(h->down2b, f2, B, S / 2, S / 2, 2 * C, S / 4, S / 4, 2, 1, 0, 2, 0, 0, 0.f, f3, f3,
-                                         2 * C, 1, s, "gemm_down2b", next_dir(h))))
+    // the second tap row accumulates onto the first's output: the same listed tokens
+    if (h->down2_split && (rc = run_patchdown(h->down2b, f2, B, S / 4, S / 4, 2 * C, 1, f3, s, "gemm_down2b", next_dir(h),
+                                              prod_of(NUNIF_SWIN_PRODUCER_DOWN2), 1)))
         return rc;
     if ((rc = tap(h, "down2", f3, (size_t)B * (S / 4) * (S / 4) * 2 * C * 2, s))) return rc;
     if ((rc = run_stage(h, h->swin[2], f3, B, S / 4, 2 * C, s, "swin3", nullptr, skip_of(2)))) return rc;                  // swin3
     // x = up2(x5) + x4, written in place over x4 (each lane reads then writes its own 8 bytes)
-    if ((rc = run_patchup(h->up2, f3, B, S / 4, S / 4, 2 * C, f2, s, "gemm_up2", next_dir(h)))) return rc;
+    if ((rc = run_patchup(h->up2, f3, B, S / 4, S / 4, 2 * C, f2, s, "gemm_up2", next_dir(h), prod_of(NUNIF_SWIN_PRODUCER_UP2)))) return rc;
     if ((rc = tap(h, "up2", f2, (size_t)B * (S / 2) * (S / 2) * 2 * C * 2, s))) return rc;
     if ((rc = run_stage(h, h->swin[3], f2, B, S / 2, 2 * C, s, "swin4", nullptr, skip_of(3)))) return rc;                  // swin4
     f16 *top = f1;
@@ -726,7 +812,7 @@ stem_done:
         top = (f16 *)h->g1.p;
         if ((rc = run_linear(h->proj2, f1, B, S, S, 0, nullptr, top, s, "gemm_proj2", next_dir(h)))) return rc;
     }
-    if ((rc = run_patchup(h->up1, f2, B, S / 2, S / 2, h->top_dim, top, s, "gemm_up1", next_dir(h)))) return rc;
+    if ((rc = run_patchup(h->up1, f2, B, S / 2, S / 2, h->top_dim, top, s, "gemm_up1", next_dir(h), prod_of(NUNIF_SWIN_PRODUCER_UP1)))) return rc;
     if ((rc = tap(h, "up1", top, (size_t)B * S * S * h->top_dim * 2, s))) return rc;
     // to_image + pixel_shuffle + clamp(0,1) (ToImage.forward :110-116, wrapper eval clamp :225-226): fused into the
     // last block's tail kernel when that block runs on the resident C = 96 kernel (1x / 2x nets)
@@ -920,12 +1006,27 @@ extern "C" int nunif_hip_swin_unet_forward(nunif_swin_unet *h, const float *x, f
 }
 
 // NUNIF_SWIN_SKIP_PAD, read at call time: 0 = the frame entry points push whole tiles through every block, as the tile entry always
-// does; 1 = only the level-1 C = 96 blocks leave windows out (A/B runs against the C = 192 skipping); unset or >= 2 = every fast block
+// does; 1 = only the level-1 C = 96 blocks leave windows out (A/B runs against the C = 192 skipping); 2 = every fast block; unset or
+// >= 3 = the producers as well (down2, up2, up1 list; the stem and down1 keep whole tiles)
 static int skip_pad_level() {
     const char *v = getenv("NUNIF_SWIN_SKIP_PAD");
-    if (!v) return 2;
+    if (!v) return 3;
     const int l = atoi(v);
-    return l <= 0 ? 0 : (l == 1 ? 1 : 2);
+    return l <= 0 ? 0 : std::min(l, 3);
+}
+
+extern "C" int nunif_hip_swin_unet_down2_test(nunif_swin_unet *h, const void *a, void *out, int32_t B, int32_t Ho, int32_t Wo,
+                                              int32_t acc_form, void *stream) {
+    NUNIF_REQUIRE(h && a && out && B > 0 && Ho > 0 && Wo > 0 && h->down2_split, "down2_test: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if ((rc = run_patchdown(h->down2, (const f16 *)a, B, Ho, Wo, 2 * h->C, 0, (f16 *)out, s, "gemm_down2", 0))) return rc;
+    if (acc_form) {
+        NUNIF_REQUIRE(patchdown_acc_enabled(), "down2_test: the accumulating PatchDown form is switched off");
+        return run_patchdown(h->down2b, (const f16 *)a, B, Ho, Wo, 2 * h->C, 1, (f16 *)out, s, "gemm_down2b", 1, nullptr, 1);
+    }
+    return run_gemm(h->down2b, (const f16 *)a, B, 2 * Ho, 2 * Wo, 2 * h->C, Ho, Wo, 2, 1, 0, 2, 0, 0, 0.f, (const f16 *)out, out, 2 * h->C, 1, s,
+                    "gemm_down2b", 1);
 }
 
 extern "C" int nunif_hip_swin_unet_tail192_test(nunif_swin_unet *h, int32_t stage, int32_t block, const void *att, void *x,
