@@ -12,8 +12,7 @@
 
 #include "host_weights.h"
 #include "swin_kernels.h"
-#include "swin_producer_tokens_host.h"
-#include "swin_tail_groups_host.h"
+#include "swin_skip_plan_host.h"
 
 namespace nunif {
 
@@ -48,11 +47,7 @@ struct Block {
     float *b96_btab = nullptr;
 };
 
-// Windows of one block that a frame render runs (pad skipping), for one tile minibatch: `list` holds one
-// entry per active window, (tile in the minibatch << 16 | window row << 8 | window column), tile-major.  C = 96: the attention
-// kernel writes window i of the list at slot i of the window-major att map and the tail walks `pixmap` (token 36 i + t -> pixel).
-// C = 192: the attention kernel writes a listed window at its own pixels and the tail walks `groups`, the same tokens in pixel
-// order packed 16 to a group (nunif_hip_swin_unet_tail_groups).
+// A block's entry of a plan (SwinSkipEntry, swin_skip_plan_host.h) as device pointers; list == NULL: the block runs whole tiles
 struct SkipBlock {
     unsigned *list = nullptr;
     int *pixmap = nullptr;
@@ -61,101 +56,46 @@ struct SkipBlock {
     int n_windows = 0;
 };
 
-// What a producer launch of a frame render walks (level 3, nunif_hip_swin_unet_producer_tokens): `n` output tokens (PatchDown), input
-// tokens (PatchUp) or output patches (the stem).  list == NULL: the whole-tile launch.
+// A producer's entry of a plan as a device pointer: `n` output tokens (PatchDown) or input tokens (PatchUp).  list == NULL: the
+// whole-tile launch.
 struct ProducerList {
     const unsigned *list = nullptr;
     unsigned n = 0;
 };
 
-// One plan per (grid, tile minibatch).  Everything of a plan lives in ONE device allocation: the lists of its blocks (uploaded
-// once, `host` keeps the source alive for the asynchronous copy) and behind them the token tables, which a kernel builds from
-// the lists on the stream that first uses the plan (launch_winmap_list_build) — `ready` orders any other stream behind that.
+// One plan per (grid, tile minibatch, level).  Everything of a plan lives in ONE device allocation: the words the host builder laid out
+// (uploaded once, `host` keeps the source alive for the asynchronous copy) and behind them the token tables, which a kernel builds
+// from the lists on the stream that first uses the plan (launch_winmap_list_build) — `ready` orders any other stream behind that.
 struct SkipPlan {
     nunif_tile_grid grid = {};
     int tile_begin = 0, B = 0;
-    int level = 0;                        // NUNIF_SWIN_SKIP_PAD of the call that built it: 1 = level-1 C = 96 blocks only, 2 = all fast blocks,
-                                          // 3 = the producers as well
-    std::vector<SkipBlock> stage[5];      // empty where the stage runs whole
-    // level 3: indexed by NUNIF_SWIN_PRODUCER_*.  list == NULL: that producer runs whole tiles — the stem and down1 always (their lists
-    // measured no faster), the others where their set is the whole map.  That is safe in any mix: a whole-tile producer WRITES a superset,
-    // and what it READS is whole only behind producers that write whole maps too (the stem and down1 in front of everything; a whole set
-    // of up2 / up1 makes every set in front of it whole through the recurrence)
-    ProducerList producer[5];
-    bool producers = false;
+    int level = 0;                        // NUNIF_SWIN_SKIP_PAD of the call that built it
+    SwinSkipPlanHost host;
+    std::vector<SkipBlock> stage[5];      // host.entries resolved against `dev`; empty where the stage runs whole
+    ProducerList producer[5];             // indexed by NUNIF_SWIN_PRODUCER_*
     void *dev = nullptr;
     size_t bytes = 0;
-    std::vector<unsigned> host;
     hipStream_t built_on = nullptr;
     hipEvent_t ready = nullptr;
-};
-
-// One axis of one block, walking BACKWARDS: `e` = tokens [0, e) of the block's OUTPUT that a consumer needs (e >= 1).  Fills the
-// windows that must run and returns the prefix of the block's INPUT that those windows read as unmasked keys.
-int block_extent_back(int e, int S, int shift, int32_t *n_win, int32_t *wrap) {
-    const int nw = S / 6;
-    if (S <= 6) shift = 0;                 // torchvision disables the shift when one window covers the map
-    if (shift == 0) {
-        *n_win = std::min(nw, (e + 5) / 6);
-        *wrap = 0;
-        return std::min(S, 6 * *n_win);
+    void release() {
+        if (ready) (void)hipEventDestroy(ready);
+        (void)hipFree(dev);               // (synchronises the device: no launch that reads the plan is still in flight)
     }
-    // shifted by 3: window w < nw - 1 holds tokens [6 w + 3, 6 w + 9), the wrap window (nw - 1) holds [S - 3, S) and [0, 3) in two
-    // mask regions.  Tokens [0, 3) are always needed, so the wrap window always runs; its far half enters as masked keys only.
-    *n_win = std::min(nw - 1, (std::max(e - 3, 0) + 5) / 6);
-    *wrap = 1;
-    return *n_win == nw - 1 ? S : 3 + 6 * *n_win;
-}
+};
 
 }  // namespace
 }  // namespace nunif
 
 using namespace nunif;
 
-// Pure integer host function (declared in nunif_hip.h): see the header.  Everything is separable per axis — the stitch reads a
-// rectangle of a tile, a token needs the rectangle of its window, PatchDown / PatchUp are 2 x 2 per pixel — so each axis is walked
-// on its own from the stitch back to the stem.
+// Pure integer host functions (declared in nunif_hip.h): swin_skip_plan_host.h, swin_producer_tokens_host.h, swin_tail_groups_host.h
 extern "C" int nunif_hip_swin_unet_tile_extents(const nunif_tile_grid *g, int32_t tile_index, const int32_t *blocks_per_stage,
                                                 const int32_t *shifts, int32_t to_image_fused, nunif_swin_block_extent *out) {
-    (void)to_image_fused;      // fused or not, ToImage maps one token to scale x scale pixels: the extents are the same
-    NUNIF_REQUIRE(g && blocks_per_stage && shifts && out, "tile_extents: NULL argument");
-    NUNIF_REQUIRE(tile_index >= 0 && tile_index < g->h_blocks * g->w_blocks, "tile_extents: tile %d outside the grid", tile_index);
-    const int S = g->tile_size - 16;
-    NUNIF_REQUIRE(S > 0 && S % 24 == 0 && g->scale > 0 && g->out_tile_size == S * g->scale,
-                  "tile_extents: the grid is not a swin_unet grid (tile %d, output tile %d)", g->tile_size, g->out_tile_size);
-    int first[6] = {0};
-    for (int st = 0; st < 5; ++st) {
-        NUNIF_REQUIRE(blocks_per_stage[st] >= 0, "tile_extents: negative block count");
-        first[st + 1] = first[st] + blocks_per_stage[st];
-    }
-    const int size[5] = {S, S / 2, S / 4, S / 2, S};
-    const int ti[2] = {tile_index / g->w_blocks, tile_index % g->w_blocks};
-    const int y_len[2] = {g->y_h, g->y_w};
-    for (int ax = 0; ax < 2; ++ax) {
-        // stitch_kernel (stitch.hip) reads pixel t = Y - output_tile_step * i of tile i for every output row / column Y of the frame
-        // with 0 <= t < out_tile_size, blend margins included: the prefix [0, min(out_tile_size, y_len - output_tile_step * i))
-        const int n_px = std::min(g->out_tile_size, y_len[ax] - g->output_tile_step * ti[ax]);
-        auto stage_back = [&](int st, int e) {         // e: needed prefix of the stage's output -> of its input
-            for (int i = blocks_per_stage[st] - 1; i >= 0; --i) {
-                nunif_swin_block_extent &o = out[first[st] + i];
-                if (e <= 0) { o.n_win[ax] = 0; o.wrap[ax] = 0; continue; }
-                e = block_extent_back(e, size[st], shifts[first[st] + i], &o.n_win[ax], &o.wrap[ax]);
-            }
-            return std::max(e, 0);
-        };
-        const int e5 = n_px <= 0 ? 0 : std::min(S, (n_px + g->scale - 1) / g->scale);    // to_image: one token -> scale x scale pixels
-        const int top_in = stage_back(4, e5);                          // swin5 reads PatchUp(swin4) + the swin1 skip
-        const int e4_in = stage_back(3, (top_in + 1) / 2);             // PatchUp: token i of the fine map reads token i / 2
-        const int e3_in = stage_back(2, (e4_in + 1) / 2);
-        // a skip connection takes the larger of its two consumers; PatchDown: token j reads tokens 2 j and 2 j + 1
-        const int e2_in = stage_back(1, std::min(size[1], std::max(2 * e3_in, e4_in)));
-        (void)stage_back(0, std::min(size[0], std::max(2 * e2_in, top_in)));
-    }
+    const char *msg = swin_tile_extents_host(g, tile_index, blocks_per_stage, shifts, to_image_fused, out);
+    NUNIF_REQUIRE(!msg, "%s", msg);
     return NUNIF_HIP_OK;
 }
 
-// Pure integer host function (declared in nunif_hip.h): swin_tail_groups_host.h
-// Pure integer host function (declared in nunif_hip.h): swin_producer_tokens_host.h
 extern "C" int nunif_hip_swin_unet_producer_tokens(const nunif_swin_block_extent *ext, int32_t n_tiles, const int32_t *blocks_per_stage,
                                                    const int32_t *shifts, const int32_t *listed, int32_t S, int32_t f1_whole,
                                                    int32_t producer, int32_t patch_h, int32_t patch_w, uint32_t *out, int64_t cap,
@@ -201,8 +141,7 @@ struct nunif_swin_unet : DeviceOwner {       // owns every device allocation mad
     size_t plan_bytes = 0;
     const SkipPlan *plan = nullptr;   // the plan of the forward_impl call under way (NULL: whole tiles)
     void drop_plan(std::list<SkipPlan>::iterator it) {
-        if (it->ready) (void)hipEventDestroy(it->ready);
-        (void)hipFree(it->dev);           // (synchronises the device: no launch that reads the plan is still in flight)
+        it->release();
         plan_bytes -= it->bytes;
         plans.erase(it);
     }
@@ -246,6 +185,21 @@ int make_plain_linear(nunif_swin_unet *h, const TensorMap &m, const std::string 
     NUNIF_REQUIRE(w->numel == (int64_t)n_real * K && b->numel == n_real, "%s: unexpected shape", key.c_str());
     const float *wd = w->data;
     return make_linear(h, n_real, K, [=](int n, int k) { return wd[(size_t)n * K + k]; }, b->data, L, chained, keep);
+}
+
+// proj | mlp.0 | mlp.3 as one linear stream of 1-KiB fragments in the order proj_mlp_kernel (swin_block_tail.hip) and the block96
+// kernel consume them; returns the number of fragments written
+size_t put_tail_stream(const std::vector<f16> &proj, const std::vector<f16> &h0, const std::vector<f16> &h3, int dim, std::vector<f16> &stream) {
+    const int KS = dim / 32, NT = dim / 16, SH = 2 * dim / 32;
+    size_t fi = 0;
+    auto put = [&](const std::vector<f16> &src, int frag) { copy_frag(src, frag, stream, &fi); };
+    for (int sx = 0; sx < KS; ++sx)
+        for (int ks = 0; ks < KS; ++ks) { put(proj, (2 * sx) * KS + ks); put(proj, (2 * sx + 1) * KS + ks); }
+    for (int sx = 0; sx < SH; ++sx) {
+        for (int ks = 0; ks < KS; ++ks) { put(h0, (2 * sx) * KS + ks); put(h0, (2 * sx + 1) * KS + ks); }
+        for (int nt = 0; nt < NT; ++nt) put(h3, nt * SH + sx);
+    }
+    return fi;
 }
 
 int make_stage(nunif_swin_unet *h, const TensorMap &m, const std::string &key, int dim, int layers,
@@ -302,18 +256,11 @@ int make_stage(nunif_swin_unet *h, const TensorMap &m, const std::string &key, i
         if ((rc = make_plain_linear(h, m, p + "mlp.0", 2 * dim, dim, &bl.mlp0, true, &h0))) return rc;   // chained
         if ((rc = make_plain_linear(h, m, p + "mlp.3", dim, 2 * dim, &bl.mlp3, true, &h3))) return rc;   // chained
         }
-        if (bl.fast) {   // one linear stream of 1-KiB fragments in the order proj_mlp_kernel consumes them (swin_block_tail.hip)
-            const int KS = dim / 32, NT = dim / 16, SH = 2 * dim / 32;
+        if (bl.fast) {
+            const int KS = dim / 32, SH = 2 * dim / 32;
             const int nf = proj_mlp_stream_frags(dim);
             std::vector<f16> stream((size_t)(nf + 15) / 16 * 16 * 512, (f16)0.0f);     // whole 16-fragment chunks
-            size_t fi = 0;
-            auto put = [&](const std::vector<f16> &src, int frag) { copy_frag(src, frag, stream, &fi); };
-            for (int sx = 0; sx < KS; ++sx)
-                for (int ks = 0; ks < KS; ++ks) { put(hp, (2 * sx) * KS + ks); put(hp, (2 * sx + 1) * KS + ks); }
-            for (int sx = 0; sx < SH; ++sx) {
-                for (int ks = 0; ks < KS; ++ks) { put(h0, (2 * sx) * KS + ks); put(h0, (2 * sx + 1) * KS + ks); }
-                for (int nt = 0; nt < NT; ++nt) put(h3, nt * SH + sx);
-            }
+            const size_t fi = put_tail_stream(hp, h0, h3, dim, stream);
             NUNIF_REQUIRE((int)fi == nf, "internal: tail stream has %zu fragments, expected %d", fi, nf);
             if ((rc = h->upload(stream, &bl.tail_stream))) return rc;
             if (dim == 192) {
@@ -345,16 +292,8 @@ int make_stage(nunif_swin_unet *h, const TensorMap &m, const std::string &key, i
             if ((rc = find(m, p + "attn.proj.weight", &pw))) return rc;
             const float *pd = pw->data;
             std::vector<f16> hpc = pack_nt_ks(dim, dim, dim, [=](int n, int k) { return pd[(size_t)n * dim + k]; }, true);
-            const int KS = dim / 32, NT = dim / 16, SH = 2 * dim / 32;
             std::vector<f16> stream((size_t)swin_block96_tail_frags() * 512, (f16)0.0f);
-            size_t fi = 0;
-            auto put = [&](const std::vector<f16> &src, int frag) { copy_frag(src, frag, stream, &fi); };
-            for (int sx = 0; sx < KS; ++sx)
-                for (int ks = 0; ks < KS; ++ks) { put(hpc, (2 * sx) * KS + ks); put(hpc, (2 * sx + 1) * KS + ks); }
-            for (int sx = 0; sx < SH; ++sx) {
-                for (int ks = 0; ks < KS; ++ks) { put(h0, (2 * sx) * KS + ks); put(h0, (2 * sx + 1) * KS + ks); }
-                for (int nt = 0; nt < NT; ++nt) put(h3, nt * SH + sx);
-            }
+            const size_t fi = put_tail_stream(hpc, h0, h3, dim, stream);
             NUNIF_REQUIRE((int)fi == swin_block96_tail_frags(), "internal: block96 stream has %zu fragments", fi);
             if ((rc = h->upload(stream, &bl.b96_tail))) return rc;
             // R[h][i] = log2(e) * table[120 - i][h]: the keys of a 2 x 2 block are then at +0, +1, +11, +12 from the
@@ -566,31 +505,53 @@ int ensure_workspace(nunif_swin_unet *h, int B, int T) {
     return NUNIF_HIP_OK;
 }
 
-// The window lists of tile minibatch [t0, t0 + B) of grid g (frame entry points only).  What a tile runs depends on the grid and
-// the tile's index alone — never on the minibatch or the stream — so any split of a frame into minibatches computes the same bits.
-//
-// INVARIANT the skipping rests on: WRITTEN IS A SUPERSET OF READ — no launch of a frame render reads a token that no launch of the
-// same frame wrote before it, so nothing stale (a previous frame's or geometry's values, finite or not) is ever an operand.
-//   * Blocks.  A block that lists reads and updates, in place, exactly the tokens of its listed windows, the far half of a shifted
-//     block's wrap window included (read as masked keys).  A C = 96 tail walks the compact list through `pixmap`, and the compact att
-//     map is written in full before it is read; a C = 192 tail walks the tokens of exactly the windows its attention ran (`groups`).
-//     A block that does not list (the generic path, a stage that is not all `fast`, a minibatch with nothing to leave out) runs whole
-//     tiles and reads every token of its map.
-//   * Producers (the stem, PatchDown down1 / both passes of down2, PatchUp up2 / up1).  Level 3: down2, up2 and up1 list (the stem and
-//     down1 run whole tiles, a superset: their lists measured no faster); a producer that lists writes the tokens that anything
-//     behind it in the frame reads — the read set of the consuming stage, the 2 x 2 parents of what a PatchDown must produce, the
-//     inputs of a PatchUp whose children are read, and the skip tokens a PatchUp adds onto in place
-//     (nunif_hip_swin_unet_producer_tokens has the recurrence) — and reads only what the producer in front of it wrote.  The
-//     lists are used together or not at all; a block that runs whole tiles makes its stage's read set the whole map.  Levels 0 - 2,
-//     tile mode, taps: every producer processes whole tiles, which is a superset of everything.
-//   * The un-fused to_image and the 4x net's proj2 run whole tiles: proj2 reads the whole level-1 map, so the stem of that net writes
-//     all of it (f1_whole), and the whole top map it writes is what the un-fused to_image reads.
 // Plan bytes per tile of 256 whose every block lists: 4 C = 96 blocks x 1 600 windows x 148 B + 2 200 windows of the 10 C = 192 blocks
 // x (4 B + 36 / 16 groups x 32 B) = 0.95 + 0.17 MB, so kMaxPlanBytes holds about 950 tiles: 21 geometries of 1080p (a plan lists every
 // tile of its minibatch once one of them has windows to leave out).  The producer lists (down2, up2, up1) add 4 B per token: (14 400 + 2 x 3 600) x 4 B =
 // 0.09 MB per tile of 256.
 constexpr size_t kMaxPlans = 1024, kMaxPlanBytes = (size_t)1 << 30;
 
+// The device half of a plan with entries: one allocation, one upload of plan->host.words, the C = 96 token tables built behind them on
+// `s`, the entries resolved to device pointers.  On failure the caller releases what was made.
+int upload_plan(SkipPlan *plan, int S, hipStream_t s) {
+    const SwinSkipPlanHost &host = plan->host;
+    if (hipMalloc(&plan->dev, host.bytes()) != hipSuccess) {
+        set_error("hipMalloc(%zu) of the window lists failed", host.bytes());
+        return NUNIF_HIP_ENOMEM;
+    }
+    plan->bytes = host.bytes();
+    if (hipMemcpyAsync(plan->dev, host.words.data(), host.words.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipEventCreateWithFlags(&plan->ready, hipEventDisableTiming) != hipSuccess) {
+        set_error("upload of the window lists failed");
+        return NUNIF_HIP_EHIP;
+    }
+    unsigned *dev = (unsigned *)plan->dev;
+    for (const SwinSkipEntry &e : host.entries) {
+        if (e.kind == SWIN_SKIP_PRODUCER) {
+            plan->producer[e.stage] = {dev + e.list, (unsigned)e.n};
+            continue;
+        }
+        std::vector<SkipBlock> &blocks = plan->stage[e.stage];
+        if (blocks.size() <= (size_t)e.block) blocks.resize(e.block + 1);
+        SkipBlock &sb = blocks[e.block];
+        sb.list = dev + e.list;
+        sb.n_windows = (int)e.n;
+        sb.n_tokens = (long)e.n_tokens;
+        if (e.kind == SWIN_SKIP_BLOCK192) {
+            sb.groups = (const nunif_swin_tail_group *)(dev + e.groups);
+            sb.n_groups = (long)e.n_groups;
+            continue;
+        }
+        sb.pixmap = (int *)(dev + e.pixmap);
+        int rc = launch_winmap_list_build(sb.pixmap, sb.list, sb.n_windows, S, S, e.shift, s);
+        if (rc) return rc;
+    }
+    if (hipEventRecord(plan->ready, s) != hipSuccess) { set_error("hipEventRecord failed"); return NUNIF_HIP_EHIP; }
+    return NUNIF_HIP_OK;
+}
+
+// The plan of tile minibatch [t0, t0 + B) of grid g (frame entry points only; NULL: whole tiles): the cached one, or a new one from
+// swin_skip_plan_host (which has the INVARIANT the skipping rests on).  A plan enters the cache complete or not at all.
 int skip_plan(nunif_swin_unet *h, const nunif_tile_grid *g, int t0, int B, int level, hipStream_t s, const SkipPlan **out) {
     *out = nullptr;
     const int S = g->tile_size - 16, nw = S / 6;
@@ -604,133 +565,41 @@ int skip_plan(nunif_swin_unet *h, const nunif_tile_grid *g, int t0, int B, int l
             *out = &*it;
             return NUNIF_HIP_OK;
         }
-    int32_t per_stage[5], n_blocks = 0;
-    std::vector<int32_t> shifts;
+    SwinSkipNet net = {};
     for (int st = 0; st < 5; ++st) {
-        per_stage[st] = (int32_t)h->swin[st].size();
-        for (int i = 0; i < per_stage[st]; ++i) shifts.push_back(i % 2 == 1 ? 3 : 0);      // swin_unet.py:30
-        n_blocks += per_stage[st];
+        net.blocks[st] = (int32_t)h->swin[st].size();
+        net.dim[st] = st == 0 ? h->C : (st == 4 ? h->top_dim : 2 * h->C);
+        net.fast[st] = std::all_of(h->swin[st].begin(), h->swin[st].end(), [](const Block &bl) { return bl.fast; });
     }
-    std::vector<nunif_swin_block_extent> ext((size_t)B * n_blocks);          // [tile][block]
-    std::vector<int32_t> listed(n_blocks, 0);
-    int rc;
-    for (int b = 0; b < B; ++b)
-        if ((rc = nunif_hip_swin_unet_tile_extents(g, t0 + b, per_stage, shifts.data(), 0, &ext[(size_t)b * n_blocks]))) return rc;
-    h->plans.emplace_front();
-    SkipPlan &plan = h->plans.front();
-    auto fail = [&](int code) { h->drop_plan(h->plans.begin()); return code; };
+    net.has_proj2 = h->has_proj2;
+    net.producer_lists = h->C == 96 && h->down2_split;
+    SkipPlan plan;
     plan.grid = *g; plan.tile_begin = t0; plan.B = B; plan.level = level; plan.built_on = s;
-    struct Piece { int st, i, shift, dim; size_t first, n, gfirst; int64_t n_groups, n_tokens; };
-    std::vector<Piece> pieces;
-    int first = 0;
-    for (int st = 0; st < 5; first += per_stage[st], ++st) {
-        const int dim = st == 0 ? h->C : (st == 4 ? h->top_dim : 2 * h->C);
-        // level 1: level 1 of the 1x / 2x nets and swin1 of the 4x net; level 2: every stage of fast blocks
-        bool fast = level >= 2 ? dim == 96 || dim == 192 : (st == 0 || st == 4) && dim == 96;
-        for (const Block &bl : h->swin[st]) fast = fast && bl.fast;
-        if (!fast) continue;
-        const int Ss = st == 0 || st == 4 ? S : (st == 2 ? S / 4 : S / 2), nw = Ss / 6;       // this stage's token map
-        if (Ss <= 6) continue;
-        plan.stage[st].resize(per_stage[st]);
-        for (int i = 0; i < per_stage[st]; ++i) {
-            const size_t at = plan.host.size();
-            for (int b = 0; b < B; ++b) {
-                const nunif_swin_block_extent &e = ext[(size_t)b * n_blocks + first + i];
-                auto active = [&](int ax, int w) { return w < e.n_win[ax] || (e.wrap[ax] && w == nw - 1); };
-                for (int wy = 0; wy < nw; ++wy) {
-                    if (!active(0, wy)) continue;
-                    for (int wx = 0; wx < nw; ++wx)
-                        if (active(1, wx)) plan.host.push_back((unsigned)b << 16 | (unsigned)wy << 8 | (unsigned)wx);
-                }
-            }
-            const size_t n = plan.host.size() - at;
-            if (n == (size_t)B * nw * nw || n == 0) { plan.host.resize(at); continue; }   // nothing to leave out: the whole-tile path
-            Piece pc = {st, i, shifts[first + i], dim, at, n, 0, 0, 0};
-            if (dim == 192) {
-                // the same tokens in pixel order, 16 to a group: 8 words per group behind the list, 32-byte aligned
-                std::vector<nunif_swin_block_extent> eb(B);
-                for (int b = 0; b < B; ++b) eb[b] = ext[(size_t)b * n_blocks + first + i];
-                // (one pass: 36 n tokens fill ceil(36 n / 16) groups; the slack is for a group closed early, which the builder never needs)
-                const int64_t cap = (36 * (int64_t)n + 15) / 16 + 8;
-                plan.host.resize((plan.host.size() + 7) / 8 * 8);
-                pc.gfirst = plan.host.size();
-                plan.host.resize(pc.gfirst + 8 * (size_t)cap);
-                static_assert(sizeof(nunif_swin_tail_group) == 8 * sizeof(unsigned), "a group is 8 words of the plan");
-                if ((rc = nunif_hip_swin_unet_tail_groups(eb.data(), B, Ss, pc.shift, (nunif_swin_tail_group *)&plan.host[pc.gfirst], cap,
-                                                          &pc.n_groups, &pc.n_tokens)))
-                    return fail(rc);
-                plan.host.resize(pc.gfirst + 8 * (size_t)pc.n_groups);
-                if (pc.n_tokens != 36 * (int64_t)n) { set_error("internal: %lld grouped tokens for %zu windows", (long long)pc.n_tokens, n); return fail(NUNIF_HIP_EINVAL); }
-            }
-            pieces.push_back(pc);
-            listed[first + i] = 1;
-        }
-    }
-    if (pieces.empty()) { *out = &plan; return NUNIF_HIP_OK; }       // (cached all the same: the next frame finds it)
-    // level 3: what the producers write, behind the lists in the same upload.  A producer with nothing to leave out keeps list == NULL
-    struct ProdPiece { int producer; size_t first; int64_t n; };
-    std::vector<ProdPiece> prods;
-    if (level >= 3 && h->C == 96 && h->down2_split && S % 24 == 0) {
-        // down2, up2, up1: the stem and down1 keep whole tiles (96 % of their work is listed on a 1080p frame, and their listed launches
-        // measured no faster than the whole ones: DESIGN.md 4.13b)
-        for (int pr = NUNIF_SWIN_PRODUCER_DOWN2; pr <= NUNIF_SWIN_PRODUCER_UP1; ++pr) {
-            const int Sp = pr == NUNIF_SWIN_PRODUCER_UP1 ? S / 2 : S / 4;
-            const int64_t whole = (int64_t)B * Sp * Sp;
-            int64_t n = 0;
-            if ((rc = nunif_hip_swin_unet_producer_tokens(ext.data(), B, per_stage, shifts.data(), listed.data(), S, h->has_proj2 ? 1 : 0, pr, 0,
-                                                          0, nullptr, 0, &n)))
-                return fail(rc);
-            if (n <= 0 || n > whole) { set_error("internal: producer %d lists %lld of %lld", pr, (long long)n, (long long)whole); return fail(NUNIF_HIP_EINVAL); }
-            if (n == whole) continue;
-            const int64_t cap = (n + 31) / 32 * 32;
-            plan.host.resize((plan.host.size() + 7) / 8 * 8);
-            const size_t at = plan.host.size();
-            plan.host.resize(at + (size_t)cap);
-            if ((rc = nunif_hip_swin_unet_producer_tokens(ext.data(), B, per_stage, shifts.data(), listed.data(), S, h->has_proj2 ? 1 : 0, pr, 0,
-                                                          0, &plan.host[at], cap, &n)))
-                return fail(rc);
-            prods.push_back({pr, at, n});
-        }
-        plan.producers = true;
-    }
-    // layout: all lists and group tables (one upload) | C = 96 token tables (36 ints per listed window), the tables 256-byte aligned
-    const size_t list_bytes = (plan.host.size() * 4 + 255) / 256 * 256;
-    size_t n_pix = 0;
-    for (const Piece &pc : pieces) n_pix += pc.dim == 96 ? pc.n * 36 : 0;
-    plan.bytes = list_bytes + n_pix * 4;
-    if (hipMalloc(&plan.dev, plan.bytes) != hipSuccess) {
-        set_error("hipMalloc(%zu) of the window lists failed", plan.bytes);
-        plan.bytes = 0;
-        return fail(NUNIF_HIP_ENOMEM);
+    const char *msg = swin_skip_plan_host(g, t0, B, level, net, &plan.host);
+    NUNIF_REQUIRE(!msg, "%s", msg);
+    // (a plan without entries is cached all the same, with dev == NULL: the next frame finds it)
+    int rc = plan.host.entries.empty() ? NUNIF_HIP_OK : upload_plan(&plan, S, s);
+    if (rc) {
+        plan.release();
+        return rc;
     }
     h->plan_bytes += plan.bytes;
-    if (hipMemcpyAsync(plan.dev, plan.host.data(), plan.host.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipEventCreateWithFlags(&plan.ready, hipEventDisableTiming) != hipSuccess) {
-        set_error("upload of the window lists failed");
-        return fail(NUNIF_HIP_EHIP);
-    }
-    size_t pix_at = 0;
-    for (const Piece &pc : pieces) {
-        SkipBlock &sb = plan.stage[pc.st][pc.i];
-        sb.list = (unsigned *)plan.dev + pc.first;
-        sb.n_windows = (int)pc.n;
-        if (pc.dim == 192) {
-            sb.groups = (const nunif_swin_tail_group *)((unsigned *)plan.dev + pc.gfirst);
-            sb.n_groups = (long)pc.n_groups; sb.n_tokens = (long)pc.n_tokens;
-            continue;
-        }
-        sb.pixmap = (int *)((char *)plan.dev + list_bytes) + pix_at;
-        pix_at += pc.n * 36;
-        if ((rc = launch_winmap_list_build(sb.pixmap, sb.list, sb.n_windows, S, S, pc.shift, s))) return fail(rc);
-    }
-    for (const ProdPiece &pp : prods) {
-        plan.producer[pp.producer].list = (const unsigned *)plan.dev + pp.first;
-        plan.producer[pp.producer].n = (unsigned)pp.n;
-    }
-    if (hipEventRecord(plan.ready, s) != hipSuccess) { set_error("hipEventRecord failed"); return fail(NUNIF_HIP_EHIP); }
+    h->plans.push_front(std::move(plan));
     while (h->plans.size() > kMaxPlans || (h->plan_bytes > kMaxPlanBytes && h->plans.size() > 1)) h->drop_plan(std::prev(h->plans.end()));
-    *out = &plan;
+    *out = &h->plans.front();
     return NUNIF_HIP_OK;
+}
+
+// What both stems (Stem1Args, StemFusedArgs) read of their input: tiles, or the frame and where its tiles lie; the rest is zeroed
+template <typename Args>
+void stem_input(Args *a, const float *x, const float *frame, const nunif_tile_grid *grid, int tile_begin, int B, int T) {
+    memset(a, 0, sizeof(*a));
+    a->x = frame ? frame : x;
+    if (frame) {
+        a->frame_mode = 1; a->H = grid->x_h; a->W = grid->x_w; a->wb = grid->w_blocks;
+        a->istep = grid->input_tile_step; a->pad_t = grid->pad_t; a->pad_l = grid->pad_l; a->tile_begin = tile_begin;
+    }
+    a->B = B; a->T = T; a->slope = 0.1f;
 }
 
 // x: tile mode [B,3,T,T] or (frame != NULL) the frame + grid; z: [B,3,S*s,S*s]
@@ -744,8 +613,8 @@ int forward_impl(nunif_swin_unet *h, const float *x, const float *frame, const n
     if (frame && skip_pad && (rc = skip_plan(h, grid, tile_begin, B, skip_pad, s, &h->plan))) return rc;
     auto skip_of = [&](int st) { return h->plan && !h->plan->stage[st].empty() ? &h->plan->stage[st] : nullptr; };
     f16 *s1 = (f16 *)h->s1.p, *f1 = (f16 *)h->f1.p, *f2 = (f16 *)h->f2.p, *f3 = (f16 *)h->f3.p;
-    // level 3: the producers' lists, all of them or none (skip_plan's INVARIANT) — none where a listed kernel is switched off
-    bool lp = h->plan && h->plan->producers;
+    // level 3: the producers' lists, all of them or none (the INVARIANT of swin_skip_plan_host.h) — none where a listed kernel is switched off
+    bool lp = h->plan && h->plan->host.producers;
     if (lp) {
         PatchDownArgs d1, d2;
         d1.B = B; d1.Ho = d1.Wo = S / 4; d1.Cin = 2 * (int)C; d1.oy = 0; d1.rev = 0;
@@ -755,37 +624,22 @@ int forward_impl(nunif_swin_unet *h, const float *x, const float *frame, const n
     }
     auto prod_of = [&](int pr) { return lp ? &h->plan->producer[pr] : nullptr; };
 
+    h->dir = 1;                                    // the stem walks upwards; everything after it alternates
     if (h->stemf_w2 && stem_fused_supported(h->C1, (int)C)) {
         StemFusedArgs sf;
-        memset(&sf, 0, sizeof(sf));
-        if (frame) {
-            sf.x = frame; sf.frame_mode = 1; sf.H = grid->x_h; sf.W = grid->x_w; sf.wb = grid->w_blocks;
-            sf.istep = grid->input_tile_step; sf.pad_t = grid->pad_t; sf.pad_l = grid->pad_l; sf.tile_begin = tile_begin;
-        } else {
-            sf.x = x;
-        }
-        sf.B = B; sf.T = T; sf.w1 = h->stemf_w1; sf.w2 = h->stemf_w2; sf.b2 = h->stem2.bias; sf.out = f1; sf.slope = 0.1f;
-        h->dir = 1;
+        stem_input(&sf, x, frame, grid, tile_begin, B, T);
+        sf.w1 = h->stemf_w1; sf.w2 = h->stemf_w2; sf.b2 = h->stem2.bias; sf.out = f1;
         if ((rc = launch_stem_fused(sf, s))) return rc;
-        goto stem_done;
-    }
-    Stem1Args a1;
-    memset(&a1, 0, sizeof(a1));
-    if (frame) {
-        a1.x = frame; a1.frame_mode = 1; a1.H = grid->x_h; a1.W = grid->x_w; a1.wb = grid->w_blocks;
-        a1.istep = grid->input_tile_step; a1.pad_t = grid->pad_t; a1.pad_l = grid->pad_l; a1.tile_begin = tile_begin;
     } else {
-        a1.x = x;
+        Stem1Args a1;
+        stem_input(&a1, x, frame, grid, tile_begin, B, T);
+        a1.w = h->stem1_w; a1.bias = h->stem1_b; a1.C1 = h->C1; a1.C1P = h->C1P; a1.out = s1;
+        if ((rc = launch_stem1(a1, s))) return rc;
+        // conv2 3x3 VALID + LeakyReLU(0.1) + crop 6 (swin_unet.py:135-137,182): s1 already starts at conv1 row/col 6
+        if ((rc = run_gemm(h->stem2, s1, B, T - 14, T - 14, h->C1P, S, S, 1, 0, 0, 3, 0, 2, 0.1f, nullptr, f1, C, 1, s,
+                           "gemm_stem2", next_dir(h))))
+            return rc;
     }
-    a1.B = B; a1.T = T; a1.w = h->stem1_w; a1.bias = h->stem1_b; a1.C1 = h->C1; a1.C1P = h->C1P; a1.out = s1;
-    a1.slope = 0.1f;
-    h->dir = 1;                                    // stem1 walks upwards; everything after it alternates
-    if ((rc = launch_stem1(a1, s))) return rc;
-    // conv2 3x3 VALID + LeakyReLU(0.1) + crop 6 (swin_unet.py:135-137,182): s1 already starts at conv1 row/col 6
-    if ((rc = run_gemm(h->stem2, s1, B, T - 14, T - 14, h->C1P, S, S, 1, 0, 0, 3, 0, 2, 0.1f, nullptr, f1, C, 1, s,
-                              "gemm_stem2", next_dir(h))))
-        return rc;
-stem_done:
     if ((rc = tap(h, "stem", f1, (size_t)B * S * S * C * 2, s))) return rc;
     if ((rc = run_stage(h, h->swin[0], f1, B, S, C, s, "swin1", nullptr, skip_of(0)))) return rc;                          // swin1 -> x3
     if ((rc = run_patchdown(h->down1, f1, B, S / 2, S / 2, C, 0, f2, s, "gemm_down1", next_dir(h), prod_of(NUNIF_SWIN_PRODUCER_DOWN1)))) return rc;
@@ -1015,6 +869,19 @@ static int skip_pad_level() {
     return l <= 0 ? 0 : std::min(l, 3);
 }
 
+// tiles [t_begin, t_end) of the frame in minibatches of batch_size, into the handle's tile store ([tile][3][To][To])
+static int render_tiles(nunif_swin_unet *h, const float *x, const nunif_tile_grid &g, int t_begin, int t_end, int batch_size,
+                        int tile_size, hipStream_t s) {
+    const size_t To = g.out_tile_size;
+    const int skip_pad = skip_pad_level();
+    for (int t0 = t_begin; t0 < t_end; t0 += batch_size) {
+        const int rc = forward_impl(h, nullptr, x, &g, t0, (float *)h->tile_out.p + (size_t)t0 * 3 * To * To, std::min(batch_size, t_end - t0),
+                                    tile_size, s, skip_pad);
+        if (rc) return rc;
+    }
+    return NUNIF_HIP_OK;
+}
+
 extern "C" int nunif_hip_swin_unet_down2_test(nunif_swin_unet *h, const void *a, void *out, int32_t B, int32_t Ho, int32_t Wo,
                                               int32_t acc_form, void *stream) {
     NUNIF_REQUIRE(h && a && out && B > 0 && Ho > 0 && Wo > 0 && h->down2_split, "down2_test: bad argument");
@@ -1053,15 +920,8 @@ extern "C" int nunif_hip_swin_unet_render(nunif_swin_unet *h, const float *x, fl
     const int n_tiles = g.h_blocks * g.w_blocks;
     const size_t To = g.out_tile_size;
     if ((rc = h->tile_out.ensure((size_t)n_tiles * 3 * To * To * sizeof(float)))) return rc;
-    float *tile_out = (float *)h->tile_out.p;
-    hipStream_t st = (hipStream_t)stream;
-    const int skip_pad = skip_pad_level();
-    for (int t0 = 0; t0 < n_tiles; t0 += batch_size) {
-        const int nb = std::min(batch_size, n_tiles - t0);
-        if ((rc = forward_impl(h, nullptr, x, &g, t0, tile_out + (size_t)t0 * 3 * To * To, nb, tile_size, st, skip_pad)))
-            return rc;
-    }
-    return launch_stitch(tile_out, y, &g, 3, st);
+    if ((rc = render_tiles(h, x, g, 0, n_tiles, batch_size, tile_size, (hipStream_t)stream))) return rc;
+    return launch_stitch((const float *)h->tile_out.p, y, &g, 3, (hipStream_t)stream);
 }
 
 // ---- tile-ROW sharding of ONE huge image (SURVEY.md §8e fallback): a rank renders the tiles of its tile rows, neighbours
@@ -1086,16 +946,7 @@ extern "C" int nunif_hip_swin_unet_render_tile_rows(nunif_swin_unet *h, const fl
     if (rc) return rc;
     NUNIF_REQUIRE(0 <= row_begin && row_begin <= row_end && row_end <= g.h_blocks, "tile rows [%d, %d) outside the grid of %d rows",
                   row_begin, row_end, g.h_blocks);
-    const size_t To = g.out_tile_size;
-    float *tile_out = (float *)h->tile_out.p;
-    const int t_end = row_end * g.w_blocks;
-    const int skip_pad = skip_pad_level();
-    for (int t0 = row_begin * g.w_blocks; t0 < t_end; t0 += batch_size) {
-        const int nb = std::min(batch_size, t_end - t0);
-        if ((rc = forward_impl(h, nullptr, x, &g, t0, tile_out + (size_t)t0 * 3 * To * To, nb, tile_size, (hipStream_t)stream, skip_pad)))
-            return rc;
-    }
-    return NUNIF_HIP_OK;
+    return render_tiles(h, x, g, row_begin * g.w_blocks, row_end * g.w_blocks, batch_size, tile_size, (hipStream_t)stream);
 }
 
 // band: [w_blocks][3][n_rows][To] fp32 = output rows [row0, row0 + n_rows) of every tile of tile row `tile_row`
