@@ -918,6 +918,45 @@ int64_t nunif_hip_da3mono_workspace_bytes(int32_t B, int32_t H, int32_t W);
 int nunif_hip_da3mono_forward(nunif_da3mono *handle, const float *depth, int32_t B, int32_t H, int32_t W, const int64_t *ranks,
                               float *out, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* stlizer pass 2: the batch form of find_transform (nunif/utils/superpoint.py:233-327, with cosine_annealing :226-230), the
+ * reference's torch autograd loop of `iteration` Adam steps over translation [2], scale and rotation of every point pair set, as
+ * iteration + 1 launches of one kernel on `stream`, one workgroup per pair, without a host synchronisation.  Launch s finishes the
+ * Adam step s - 1 of its pair (betas 0.5 / 0.9, eps 1e-8, torch.optim.Adam's bias corrections :267; both learning rates follow
+ * CosineAnnealingWarmRestarts(T_0 = iteration, eta_min = lr_scale_rotation * 1e-3) at T_cur = s - 1, :268-269) and then runs the
+ * forward and the closed-form gradient of step s (:279-310); launch 0 centres and normalises the points first (:271-275: norm_scale
+ * is the largest |nan_to_num(xy1 - center)| over all N x 2 entries of the pair, padded ones included); launch `iteration` writes
+ * the outputs (:315-319).  The loss is a mean over the whole batch (:305, :309): every pair adds its selected-element count to the
+ * step's slot of the workspace with one integer atomicAdd, and the next launch divides the pair's gradient sums by that total.
+ * These are the only atomics, so the result is bit-equal across calls and streams and does not depend on the order of the pairs.
+ * With sigma or sigma_min given, steps s > 0 keep the masked elements with (loss - mean) / std < sigma (:294-305), mean and
+ * population standard deviation over the pair's masked losses of both coordinates; sigma follows cosine_annealing(sigma_min,
+ * sigma_max, s, iteration) when sigma_min is given.  A zero std, or a pair without a masked element, selects nothing.  Parameters
+ * are fp32 as in the reference; the mean, the deviation and the gradient sums are double sums in a fixed order.
+ *   xy1, xy2 [B][N][2] f32 (8-byte aligned), mask [B][N][2] bytes (non-zero = valid; 2-byte aligned) or NULL for all valid,
+ *   center [B][2] f32; shift_out [B][2] = translation * norm_scale, scale_out [B], angle_out [B] = rad2deg(atan2(sin r, cos r));
+ *   trace, if not NULL: (tx, ty, scale, rotation) of every pair after every Adam step, [iteration][B][4] f32 (tests).
+ *   flags: NUNIF_FIND_TRANSFORM_* below; sigma / sigma_min are read only when their flag is set.
+ *   1 <= B <= 4096, 1 <= N <= 8192, 1 <= iteration <= 1024; anything else is refused (workspace_bytes answers -1).
+ *   NaN or infinite masked points are out of contract.  In the reference the NaN loss of step 0 turns that pair's parameters NaN
+ *   for good (:309-311); here sign(NaN) counts as 0 at step 0, and from step 1 on a NaN loss makes the pair's mean and deviation
+ *   NaN, so the pair selects nothing and its parameters stay where step 0 left them.  Other pairs see only the changed count.
+ * workspace: caller-owned device bytes, 256-byte aligned, at least workspace_bytes(B, N, iteration) =
+ *   align256(4 * iteration) [the count slots, cleared by every call] + align256(96 * B) [per pair: 4 parameters, Adam m and v,
+ *   norm_scale, 4 double gradient sums] + 2 * align256(8 * B * N) [the normalised xy1, xy2]; a smaller one is refused.  Calls that
+ *   overlap on different streams need their own. */
+enum {
+    NUNIF_FIND_TRANSFORM_DISABLE_SHIFT = 1,
+    NUNIF_FIND_TRANSFORM_DISABLE_SCALE = 2,
+    NUNIF_FIND_TRANSFORM_DISABLE_ROTATE = 4,
+    NUNIF_FIND_TRANSFORM_SIGMA = 8,
+    NUNIF_FIND_TRANSFORM_SIGMA_MIN = 16
+};
+int64_t nunif_hip_find_transform_workspace_bytes(int32_t B, int32_t N, int32_t iteration);
+int nunif_hip_find_transform(const float *xy1, const float *xy2, const uint8_t *mask_or_null, const float *center, int32_t B,
+                             int32_t N, int32_t iteration, double lr_translation, double lr_scale_rotation, double sigma,
+                             double sigma_min, double sigma_max, int32_t flags, float *shift_out, float *scale_out,
+                             float *angle_out, void *workspace, int64_t workspace_bytes, float *trace_or_null, void *stream);
+
 /* Test hooks (tests/ only): snapshot every stage's NHWC fp16 output during the next forward calls, then read
  * them back one by one (returns 1 past the last tap).  Names match oracle.swin_unet.unet_forward(taps=...). */
 int nunif_hip_swin_unet_debug_taps(nunif_swin_unet *handle, int32_t enable);

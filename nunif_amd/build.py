@@ -36,7 +36,9 @@ EXTRA_FLAGS = {"stitch.hip": ["-ffp-contract=off"], "iw3_warp.hip": ["-ffp-contr
                # hdr_planes.hip: the gather of pixfmt.hip and the map of hdr.hip in one kernel, bit-equal to the two in a row
                "hdr_planes.hip": ["-ffp-contract=off"] + NO_SLP,
                # da3_disparity.hip: 1 / (depth + shift) * (1 - w) and the raw blend round once per operation, in the reference's order
-               "da3_disparity.hip": ["-ffp-contract=off"] + NO_SLP}
+               "da3_disparity.hip": ["-ffp-contract=off"] + NO_SLP,
+               # find_transform.hip: the point transform and the Adam step round once per operation, in the reference's order
+               "find_transform.hip": ["-ffp-contract=off"] + NO_SLP}
 
 
 def sources():
