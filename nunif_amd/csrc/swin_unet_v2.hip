@@ -21,6 +21,7 @@
 
 #include "host_weights.h"
 #include "swin_kernels.h"
+#include "wa_block_host.h"
 
 namespace nunif {
 
@@ -321,8 +322,6 @@ int make_conv3(nunif_swin_unet_v2 *h, const HostTensor *w, const HostTensor *b, 
     return rc ? rc : h->upload(bb, &cv->b);
 }
 
-double gelu_erf_d(double v) { return 0.5 * v * (1.0 + erf(v * 0.70710678118654752440)); }
-
 int make_wac(nunif_swin_unet_v2 *h, const TensorMap &m, const std::string &p, int C, int heads, int ws, int shift, WacBlock *bk) {
     const HostTensor *wqkv, *bqkv, *wp, *bp, *nw, *w1, *b1, *w2, *b2, *tw0, *tb0, *tw2, *tb2;
     int rc;
@@ -353,20 +352,8 @@ int make_wac(nunif_swin_unet_v2 *h, const TensorMap &m, const std::string &p, in
         if ((rc = h->upload(g, &bk->norm))) return rc;
     }
     {   // WindowScoreBias (attention.py:375-419): the to_bias MLP on the normalised relative offsets, evaluated once here
-        const int hidden = (int)tb0->numel, N = ws * ws;
-        NUNIF_REQUIRE(tw0->numel == hidden * 2 && tw2->numel == hidden && tb2->numel == 1, "%s: score-bias MLP shape", p.c_str());
-        const float dmax = (float)(ws - 1);
-        std::vector<float> tab((size_t)N * N);
-        for (int q = 0; q < N; ++q)
-            for (int k = 0; k < N; ++k) {
-                const float dy = (float)(q / ws - k / ws) / dmax, dx = (float)(q % ws - k % ws) / dmax;
-                double o = tb2->data[0];
-                for (int j = 0; j < hidden; ++j)
-                    o += (double)tw2->data[j] * gelu_erf_d((double)tw0->data[j * 2] * dy + (double)tw0->data[j * 2 + 1] * dx +
-                                                            (double)tb0->data[j]);
-                tab[(size_t)q * N + k] = (float)o * 1.4426950408889634f;
-            }
-        if ((rc = h->upload(tab, &bk->btab))) return rc;
+        std::vector<float> tab;
+        if ((rc = wa_score_bias_table(tw0, tb0, tw2, tb2, ws, ws * ws, p, &tab)) || (rc = h->upload(tab, &bk->btab))) return rc;
     }
     const int mid = (int)w1->shape[0];
     bk->mid = mid;

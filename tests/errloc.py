@@ -17,11 +17,12 @@ The CUNet family (``waifu2x.cunet`` / ``upcunet`` / ``vgg_7`` / ``upconv_7``, or
 conv workgroup, per 16 x 16 head tile, per 16-channel MFMA n-tile and per image (SE pooling, the scale table): its regions are the
 cells 8 / 16 / 32 / 64 of the level-1 map in output pixels (twice that for the 2x nets), with the same constants.
 
-The iw3 side nets (``sbs.row_flow_v3``, ``sbs.mlbw_*``, csrc/rowflow.hip) run one window of 4 x 4 or 3 x 3 tokens per wave and a token
+The iw3 side nets (``sbs.row_flow_v3``, ``sbs.mlbw_*``, csrc/rowflow.hip on the WABlock of csrc/wa_block.hip) run one window of 4 x 4 or 3 x 3 tokens per wave and a token
 is 1 row x 8 depth pixels: their regions are rectangular cells (cell_h, cell_w) with offsets (off_y, off_x), and since flows,
 softmax weights and logits are not clamped the floor is relative, tau = TAP_TAU_REL x the map's rms (``tests/sidenet_cases.py``).
 
-The iw3 depth path (``iw3.depth_anything``: csrc/depth_anything.hip, depth_mlp.hip, conv3_lds.hip; ``iw3.depth_aa``: csrc/depth_aa.hip)
+The iw3 depth path (``iw3.depth_anything``: csrc/depth_anything.hip, depth_mlp.hip, conv3_lds.hip; ``iw3.depth_aa``: csrc/depth_aa.hip on the WABlock of
+csrc/wa_block.hip)
 is pinned on its final outputs only, [B,1,h,w], with the side nets' constants and relative floor.  The depth engine goes wrong per
 token (14 x 14 pixels of the map), per 4 x 4 token block (the footprint of one ``layer4_rn`` pixel pair) and per 8 x 32 conv patch of
 ``output_conv2.0``; DepthAA per 8 x 8 window = 16 x 16 pixels behind its centred pad, shifted by 8 pixels in blocks 0 and 2
@@ -52,7 +53,7 @@ CUNET_SCALE = {"waifu2x.cunet": 1, "waifu2x.upcunet": 2, "waifu2x.vgg_7": 1, "wa
 CUNET_OFFSET = {"waifu2x.cunet": 28, "waifu2x.upcunet": 36, "waifu2x.vgg_7": 7, "waifu2x.upconv_7": 14}
 CUNET_CELLS = (8, 16, 32, 64)                   # kTH = 8, the 16 x 16 head tile, kTW = 32, and two patches side by side
 
-# the iw3 side nets (csrc/rowflow.hip): one window per wave, a token = 1 row x 8 depth pixels, so a window of WS x WS tokens is a
+# the iw3 side nets (csrc/rowflow.hip, wa_block.hip): one window per wave, a token = 1 row x 8 depth pixels, so a window of WS x WS tokens is a
 # cell of (WS, 8 WS) output pixels.  name -> (layers, small, hole mask) for the MLBW family
 ROW_FLOW = "sbs.row_flow_v3"
 ROW_FLOW_CELLS = ((4, 32), (3, 24), (12, 96))   # the 4 x 4 and the 3 x 3 window, and the pad unit (12 rows x 96 columns)

@@ -1,7 +1,8 @@
 """The cases of the side-net localised checks (helper module, not a conftest): shared by ``test_errloc_sidenet.py`` (CPU, the
 emulation standing in for the engine) and ``test_gpu_sidenet_errloc.py`` (the HIP engine), so that both run the same shapes.
 
-A case is (net, (B, h, w), flip, regime).  The shapes are the smallest at which ``csrc/rowflow.hip`` takes another path:
+A case is (net, (B, h, w), flip, regime).  The shapes are the smallest at which ``csrc/rowflow.hip`` or the WABlock it runs
+(``csrc/wa_block.hip``: ``wmha_kernel`` and the block loop) takes another path:
 
 row_flow_v3 (pad to multiples of 12 rows x 96 columns, bottom / right only and never zero; 8 pixels per token):
     (1, 58, 104)   the fixture's shape: 60 x 24 tokens

@@ -1,8 +1,8 @@
 """CPU: ``tests/errloc.py`` on the iw3 depth path (``iw3.depth_anything``, ``iw3.depth_aa``), the fp16-autocast emulation standing in
 for the engine.
 
-The counterpart of ``test_errloc_sidenet.py`` for ``csrc/depth_anything.hip`` / ``depth_mlp.hip`` / ``conv3_lds.hip`` / ``depth_aa.hip``,
-pinned on FINAL OUTPUTS only (``tests/depth_cases.py``: the cases and what each one meets).
+The counterpart of ``test_errloc_sidenet.py`` for ``csrc/depth_anything.hip`` / ``depth_mlp.hip`` / ``conv3_lds.hip`` / ``depth_aa.hip`` /
+``wa_block.hip``, pinned on FINAL OUTPUTS only (``tests/depth_cases.py``: the cases and what each one meets).
 
 (a) Conditions on the inputs.  The bound divides by the emulation's own error per region, so it needs that error to be a usable
 yardstick everywhere: for every depth-engine case and every partition ((14, 14) / (56, 56) / (8, 32), aligned and shifted by half

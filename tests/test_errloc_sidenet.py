@@ -1,7 +1,7 @@
 """CPU: ``tests/errloc.py`` on the iw3 side nets (``sbs.row_flow_v3``, ``sbs.mlbw_*``), the fp16-autocast emulation standing in for
 the engine.
 
-The counterpart of ``test_errloc.py`` / ``test_errloc_cunet.py`` for ``csrc/rowflow.hip``, whose kernels go wrong per window (one
+The counterpart of ``test_errloc.py`` / ``test_errloc_cunet.py`` for ``csrc/rowflow.hip`` and the WABlock it runs (``csrc/wa_block.hip``), whose kernels go wrong per window (one
 window per wave) and per edge.  (a) The clean emulation passes every case of ``test_gpu_sidenet_errloc.py`` with ratio <= 1.  (b)
 Six mutations of the forward, each one a way ``wmha_kernel`` / ``rf_input_kernel`` / ``mlbw_in_kernel`` could be wrong, are applied
 to a restatement of the oracle path (``_row_flow`` / ``_mlbw`` below, bit-equal to the oracle without a mutation) and run under the

@@ -1,5 +1,6 @@
 """The iw3 depth path on the HIP engine held cell by cell to a float64 oracle: the Depth-Anything encoder + DPT head
-(``csrc/depth_anything.hip``, ``depth_mlp.hip``, ``conv3_lds.hip``) and the DepthAA net that runs on its output (``csrc/depth_aa.hip``).
+(``csrc/depth_anything.hip``, ``depth_mlp.hip``, ``conv3_lds.hip``) and the DepthAA net that runs on its output
+(``csrc/depth_aa.hip``; its blocks: ``wmha8_kernel`` of ``csrc/wa_block.hip``).
 
 ``tests/errloc.py``: per image, max|y - y64| <= A_SIDE * max|emu - y64| and, in every cell of (14, 14) / (56, 56) / (8, 32) output
 pixels (the depth engine: one token, a 4 x 4 token block, the conv patch of ``output_conv2.0``; aligned and shifted by half a cell) or

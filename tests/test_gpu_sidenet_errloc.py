@@ -1,6 +1,6 @@
 """The iw3 side nets (``sbs.row_flow_v3``, ``sbs.mlbw_*``) and the delta warp held window by window to a float64 oracle.
 
-``csrc/rowflow.hip`` goes wrong per window and per edge (``wmha_kernel`` runs one window per wave: 9 of 16 MFMA rows for the 3 x 3
+``csrc/rowflow.hip`` goes wrong per window and per edge (``wmha_kernel`` of ``csrc/wa_block.hip`` runs one window per wave: 9 of 16 MFMA rows for the 3 x 3
 window, masked padded keys, clamped padded queries, guarded stores, a [query][key] bias table, zero-padded tokens that attend as
 bias-only tokens in MLBW's shifted blocks, a grid-stride loop and a wave tail; the entry / leave kernels pad, mirror and (un)shuffle).
 ``tests/errloc.py``: per image, max|y - y64| <= A_SIDE * max|emu - y64| and, in every cell of (4, 32) / (3, 24) / (12, 96) output
