@@ -8,8 +8,7 @@
 #include <string>
 #include <vector>
 
-#include "host_weights.h"
-#include "swin_kernels.h"
+#include "packed_layers.h"
 
 namespace nunif {
 int launch_stitch(const float *tile_out, float *y, const nunif_tile_grid *g, int C, hipStream_t s, int y0 = 0, int rows = -1,
@@ -20,14 +19,14 @@ using namespace nunif;
 
 namespace {
 
-struct ConvW { f16 *stream = nullptr; float *bias = nullptr; int N = 0, n_real = 0, Cin = 0, k = 3, stride = 1;
-               f16 *gemm_w = nullptr;           // 2x2 stride-2 convs: the same weights in gemm_kernel's [n-tile][k-step] order
+struct ConvW : PackedConv { int stride = 1;
+               PackedLinear gemm;               // 2x2 stride-2 convs: the same weights in gemm_kernel's [n-tile][k-step] order (K = 4 Cin)
                // 3x3 convs with 128 / 256 inputs and more than 64 outputs (the two bottom convs of unet2): the SAME weights as
                // streams of 64 output channels each, so that every slice runs on the LDS-DMA conv with K halves
                // (conv3_dma_kernel<4, 64, ., 1, 2, KS>), writing its channels of the NHWC map through ConvArgs::ldo
-               std::vector<f16 *> slice;
+               std::vector<ConvSlice> slice;
                f16 *head_w = nullptr; };        // 64 -> 3 image heads: the tap-scatter form's fragments (cunet_head.hip), row n = 3 tap + c
-struct UpW { f16 *w = nullptr; float *bias = nullptr; int N = 0, K = 0, cq = 0; };       // ConvTranspose2d 2x2 s2
+struct UpW : PackedLinear { int cq = 0; };       // ConvTranspose2d 2x2 s2
 struct SEW { float *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr; int C = 0; };
 struct C3W { float *w = nullptr, *b = nullptr; int C = 0; f16 *frag = nullptr; };   // frag: MFMA A fragments of the fused stem (K = 27 taps + bias)
 
@@ -61,41 +60,28 @@ namespace {
 // cin_real < cin: the producer stores its cin_real channels padded with zeros to cin (a multiple of 32)
 int make_conv(nunif_cunet *h, const TensorMap &m, const std::string &key, int cin, int cout, int k, int stride, ConvW *c,
               int cin_real = 0) {
-    const HostTensor *w, *b;
-    int rc;
     if (cin_real <= 0) cin_real = cin;
-    if ((rc = find(m, key + ".weight", &w)) || (rc = find(m, key + ".bias", &b))) return rc;
-    NUNIF_REQUIRE(w->numel == (int64_t)cout * cin_real * k * k && b->numel == cout, "%s: unexpected shape", key.c_str());
-    NUNIF_REQUIRE(cin % 32 == 0, "%s: Cin=%d must be a multiple of 32", key.c_str(), cin);
-    const int N = (cout + 15) / 16 * 16, NT = N / 16, KS = k * k * cin / 32;
-    const float *wd = w->data;
-    std::vector<f16> stream = pack_ks_nt(cout, N, k * k * cin, [=](int n, int kk) {
-        const int tap = kk / cin, ci = kk % cin;
-        return ci < cin_real ? wd[((size_t)n * cin_real + ci) * k * k + tap] : 0.0f;
-    });
-    std::vector<float> bias(N, 0.0f);
-    for (int n = 0; n < cout; ++n) bias[n] = b->data[n];
-    c->N = N; c->n_real = cout; c->Cin = cin; c->k = k; c->stride = stride;
-    if ((rc = h->upload(stream, &c->stream))) return rc;
-    if (k == 3 && stride == 1 && cin_real == cin && (cin == 128 || cin == 256) && cout > 64 && cout % 64 == 0) {
-        for (int sl = 0; sl < cout / 64; ++sl) {
-            f16 *dev = nullptr;
-            if ((rc = h->upload(stream_slice(stream, KS, NT, 4 * sl, 4), &dev))) return rc;
-            c->slice.push_back(dev);
-        }
-    }
+    ConvHost host;
+    int rc;
+    if ((rc = conv_from(h, m, key, cout, 16, cin_real, cin, k, c, true, 0, &host))) return rc;
+    c->stride = stride;
+    if (k == 3 && stride == 1 && cin_real == cin && (cin == 128 || cin == 256) && cout > 64 && cout % 64 == 0 &&
+        (rc = upload_slices(h, host, std::vector<int>(cout / 64, 4), &c->slice)))
+        return rc;
     if (k == 3 && stride == 1 && cin_real == 64 && cin == 64 && cout == 3) {
         // tap-scatter head: row n = 3 tap + co over the 64 input channels
+        const float *wd = m.at(key + ".weight").data;
         if ((rc = h->upload(pack_nt_ks(27, 32, 64, [=](int n, int ci) { return wd[((size_t)(n % 3) * 64 + ci) * 9 + n / 3]; }),
                             &c->head_w)))
             return rc;
     }
-    if (k == 2 && stride == 2 && cin_real == cin && N == cout && N % 32 == 0) {
+    if (k == 2 && stride == 2 && cin_real == cin && c->N == cout && c->N % 32 == 0) {
         // k = stride: a 2 x 2 gather GEMM (the PatchDown form of gemm_kernel: every input pixel is read exactly once, the token
         // tile's whole K extent sits in registers) instead of the K-looped conv_kernel with its nine-tap machinery
-        if ((rc = h->upload(ks_nt_to_nt_ks(stream, KS, NT), &c->gemm_w))) return rc;
+        c->gemm.bias = c->bias; c->gemm.N = c->gemm.n_real = c->N; c->gemm.K = 4 * cin;
+        return h->upload(ks_nt_to_nt_ks(host.stream, 4 * cin / 32, c->N / 16), &c->gemm.w);
     }
-    return h->upload(bias, &c->bias);
+    return NUNIF_HIP_OK;
 }
 
 // ConvTranspose2d(cin, cout, 2, 2) weight [cin][cout][2][2] -> Linear cin -> 4*cout with pixel-shuffle column order
@@ -105,14 +91,10 @@ int make_up(nunif_cunet *h, const TensorMap &m, const std::string &key, int cin,
     int rc;
     if ((rc = find(m, key + ".weight", &w)) || (rc = find(m, key + ".bias", &b))) return rc;
     NUNIF_REQUIRE(w->numel == (int64_t)cin * cout * 4 && b->numel == cout, "%s: unexpected shape", key.c_str());
-    const int N = 4 * cout;
-    const float *wd = w->data;
-    std::vector<f16> packed = pack_nt_ks(N, N, cin, [=](int n, int ci) { return wd[((size_t)ci * cout + n % cout) * 4 + n / cout]; });
-    std::vector<float> bias(N);
-    for (int n = 0; n < N; ++n) bias[n] = b->data[n % cout];
-    u->N = N; u->K = cin; u->cq = cout;
-    if ((rc = h->upload(packed, &u->w))) return rc;
-    return h->upload(bias, &u->bias);
+    const float *wd = w->data, *bd = b->data;
+    u->cq = cout;
+    return make_linear(h, 4 * cout, 16, cin, [=](int n, int ci) { return wd[((size_t)ci * cout + n % cout) * 4 + n / cout]; },
+                       [=](int n) { return bd[n % cout]; }, u);
 }
 
 // ConvTranspose2d(cin, cout, 4, 2, 3), weight [cin][cout][4][4]:  out[oy][ox] = b + sum in[iy][ix] W[ky][kx] over
@@ -125,19 +107,14 @@ int make_deconv4(nunif_cunet *h, const TensorMap &m, const std::string &key, int
     int rc;
     if ((rc = find(m, key + ".weight", &w)) || (rc = find(m, key + ".bias", &b))) return rc;
     NUNIF_REQUIRE(w->numel == (int64_t)cin * cout * 16 && b->numel == cout, "%s: unexpected shape", key.c_str());
-    const int n_real = 4 * cout, N = (n_real + 15) / 16 * 16, K = 4 * cin;
-    const float *wd = w->data;
-    std::vector<f16> packed = pack_nt_ks(n_real, N, K, [=](int n, int k) {
+    const float *wd = w->data, *bd = b->data;
+    u->cq = cout;
+    return make_linear(h, 4 * cout, 16, 4 * cin, [=](int n, int k) {
         const int co = n / 4, a = (n >> 1) & 1, bb = n & 1;
         const int tap = k / cin, ci = k % cin, dy = tap >> 1, dx = tap & 1;
         const int ky = a + 2 * (1 - dy), kx = bb + 2 * (1 - dx);
         return wd[(((size_t)ci * cout + co) * 4 + ky) * 4 + kx];
-    });
-    std::vector<float> bias(N, 0.0f);
-    for (int n = 0; n < n_real; ++n) bias[n] = b->data[n / 4];
-    u->N = N; u->K = K; u->cq = cout;
-    if ((rc = h->upload(packed, &u->w))) return rc;
-    return h->upload(bias, &u->bias);
+    }, [=](int n) { return bd[n / 4]; }, u);
 }
 
 // cout_pad > cout: the extra output channels get zero weights / bias (LeakyReLU(0) = 0), so the next conv sees Cin % 32 == 0
@@ -195,14 +172,10 @@ int tap_copy(nunif_cunet *h, const char *name, const void *src, size_t bytes, hi
 
 int run_conv(const ConvW &c, const f16 *a, const f16 *a2, int H2, int crop2, int B, int Hi, f16 *out, float *out32,
              const float *add32, int addH, int add_crop, int clamp01, int act, hipStream_t s) {
-    ConvArgs g;
-    memset(&g, 0, sizeof(g));
-    g.a = a; g.a2 = a2; g.H2 = H2; g.W2 = H2; g.crop2 = crop2;
-    g.B = B; g.Hi = Hi; g.Wi = Hi; g.Cin = c.Cin; g.stride = c.stride; g.kh = c.k; g.kw = c.k;
-    g.Ho = (Hi - c.k) / c.stride + 1; g.Wo = g.Ho;
-    g.wstream = c.stream; g.bias = c.bias; g.N = c.N; g.n_real = c.n_real;
+    ConvArgs g = conv_args(c, a, B, Hi, Hi, out, c.stride);
+    g.a2 = a2; g.H2 = H2; g.W2 = H2; g.crop2 = crop2;
     g.act = act; g.slope = 0.1f;
-    g.out = out; g.out32 = out32; g.add32 = add32; g.addH = addH; g.addW = addH; g.add_crop = add_crop;
+    g.out32 = out32; g.add32 = add32; g.addH = addH; g.addW = addH; g.add_crop = add_crop;
     g.clamp01 = clamp01;
     if (c.head_w && out32 && !out && !a2 && act == 0) {
         // the 64 -> 3 image heads in tap-scatter form (cunet_head.hip), every launch of that shape
@@ -211,16 +184,7 @@ int run_conv(const ConvW &c, const f16 *a, const f16 *a2, int H2, int crop2, int
     }
     // (every launch of such a conv takes the sliced form or none does: a result must not depend on the tile minibatch)
     static const bool sliced = !(getenv("NUNIF_CUNET_SLICED") && atoi(getenv("NUNIF_CUNET_SLICED")) == 0);
-    if (sliced && !c.slice.empty() && out && !out32 && !a2) {
-        for (size_t sl = 0; sl < c.slice.size(); ++sl) {
-            ConvArgs q = g;
-            q.wstream = c.slice[sl]; q.bias = c.bias + 64 * sl; q.N = 64; q.n_real = 64;
-            q.out = out + 64 * sl; q.ldo = c.n_real;
-            int rc = launch_conv(q, s);
-            if (rc) return rc;
-        }
-        return NUNIF_HIP_OK;
-    }
+    if (sliced && !c.slice.empty() && out && !out32 && !a2) return launch_conv_sliced(g, c.slice, s);
     return launch_conv(g, s);
 }
 
@@ -228,18 +192,15 @@ static inline bool down_gemm_enabled() { const char *e = getenv("NUNIF_CUNET_DOW
 
 // Conv2d(k = stride = 2) + LeakyReLU (cunet.py:37,78,81) as a gather GEMM
 int run_down(const ConvW &c, const f16 *a, int B, int Hi, f16 *out, hipStream_t s) {
-    if (!c.gemm_w || !down_gemm_enabled()) return run_conv(c, a, nullptr, 0, 0, B, Hi, out, nullptr, nullptr, 0, 0, 0, 2, s);
+    if (!c.gemm.w || !down_gemm_enabled()) return run_conv(c, a, nullptr, 0, 0, B, Hi, out, nullptr, nullptr, 0, 0, 0, 2, s);
     {   // 64 -> 64: the K-outer prefetching kernel of the swin PatchDown (swin_patchdown.hip), every launch of that shape
         PatchDownArgs p;
-        p.a = a; p.w = c.gemm_w; p.bias = c.bias; p.out = out; p.B = B; p.Ho = Hi / 2; p.Wo = Hi / 2; p.Cin = c.Cin; p.oy = 0;
+        p.a = a; p.w = c.gemm.w; p.bias = c.bias; p.out = out; p.B = B; p.Ho = Hi / 2; p.Wo = Hi / 2; p.Cin = c.Cin; p.oy = 0;
         p.rev = 0; p.N = c.N; p.act = 2; p.slope = 0.1f;
         if (Hi % 2 == 0 && patchdown_supported(p)) return launch_patchdown(p, s);
     }
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.a = a; g.B = B; g.Hi = Hi; g.Wi = Hi; g.Cin = c.Cin; g.Ho = Hi / 2; g.Wo = Hi / 2; g.stride = 2; g.kw = 2;
-    g.K = 4 * c.Cin; g.w = c.gemm_w; g.bias = c.bias; g.N = c.N; g.mode = 0; g.act = 2; g.slope = 0.1f;
-    g.out = out; g.ldo = c.N; g.n_real = c.N; g.ps = 1;
+    GemmArgs g = gemm_map_args(c.gemm, a, B, Hi, Hi, c.Cin, Hi / 2, Hi / 2, out, 2, 2);
+    g.act = 2; g.slope = 0.1f;
     return launch_gemm(g, s, "cunet_down");
 }
 
@@ -269,22 +230,16 @@ int run_up(const UpW &u, const f16 *a, int B, int Hi, f16 *out, hipStream_t s, c
             return NUNIF_HIP_OK;
         }
     }
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.a = a; g.B = B; g.Hi = Hi; g.Wi = Hi; g.Cin = u.K; g.Ho = Hi; g.Wo = Hi; g.stride = 1; g.kw = 1;
-    g.K = u.K; g.w = u.w; g.bias = u.bias; g.N = u.N; g.mode = 1; g.act = 2; g.slope = 0.1f;
-    g.out = out; g.ldo = u.cq; g.n_real = u.N; g.ps = 1;
+    GemmArgs g = gemm_map_args(u, a, B, Hi, Hi, u.K, Hi, Hi, out);
+    g.mode = 1; g.act = 2; g.slope = 0.1f; g.ldo = u.cq;
     if (skip) { g.res = skip; g.res_H = skip_side; g.res_W = skip_side; g.res_crop = crop; }
     g.in_scale = in_scale;                // the squeeze-excitation scale of `a`, applied as the fragments are loaded
     return launch_gemm(g, s, "cunet_up");
 }
 
 int run_deconv4(const UpW &u, const f16 *a, int B, int Hi, float *out, int no_clamp, hipStream_t s) {
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.a = a; g.B = B; g.Hi = Hi; g.Wi = Hi; g.Cin = u.K / 4; g.Ho = Hi - 1; g.Wo = Hi - 1; g.stride = 1; g.kw = 2;
-    g.K = u.K; g.w = u.w; g.bias = u.bias; g.N = u.N; g.mode = 2; g.act = 0;
-    g.out = out; g.n_real = 4 * u.cq; g.ps = 2; g.oshift = -1; g.OH = 2 * Hi - 4; g.OW = 2 * Hi - 4; g.no_clamp = no_clamp;
+    GemmArgs g = gemm_map_args(u, a, B, Hi, Hi, u.K / 4, Hi - 1, Hi - 1, out, 1, 2);
+    g.mode = 2; g.ldo = 0; g.ps = 2; g.oshift = -1; g.OH = 2 * Hi - 4; g.OW = 2 * Hi - 4; g.no_clamp = no_clamp;
     return launch_gemm(g, s, "upcunet_bottom");
 }
 

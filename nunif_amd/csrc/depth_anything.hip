@@ -34,8 +34,7 @@
 #include <string>
 #include <vector>
 
-#include "host_weights.h"
-#include "swin_kernels.h"
+#include "packed_layers.h"
 
 namespace nunif {
 
@@ -341,8 +340,8 @@ using namespace nunif;
 
 // =====================================================================================================================
 namespace {
-struct Lin { f16 *w = nullptr; float *b = nullptr; int N = 0, K = 0; float *ws = nullptr; };     // gemm_kernel packing [nt][ks]; ws: row sums (LayerNorm-folded Linears)
-struct Cnv { f16 *w = nullptr; float *b = nullptr; int N = 0, Cin = 0, k = 3, cmaj = 0; };     // conv_kernel stream [ks][nt]
+struct Lin : PackedLinear { float *ws = nullptr; };     // ws: row sums (LayerNorm-folded Linears).  N and K arrive padded: n_real = N
+typedef PackedConv Cnv;
 struct Blk { float *g1, *b1, *g2, *b2; Lin qkv, proj, fc1, fc2[4], fc2_full, qkv_ln, fc1_ln; int n_fc2; f16 *fc2c = nullptr; };   // fc2c: fc2_full in the chained k order (depth_mlp.hip)   // *_ln: norm1 / norm2 folded in (ViT-S)   // fc2 (K = 4 D) = 2 or 4 GEMMs of K = 768 / 1024
 struct Rcu { Cnv c1, c2; };
 struct Fus { Rcu r1, r2; Lin out; };
@@ -418,67 +417,20 @@ struct nunif_depth_anything : DeviceOwner {
 };
 
 namespace {
-// Linear / 1x1 / pixel-shuffle GEMM: W'(n, k) given by wt (zero outside the real range), N and K already padded
-template <typename F, typename G>
-int make_lin(nunif_depth_anything *h, int N, int K, F wt, G bias, Lin *L) {
-    std::vector<f16> packed = pack_nt_ks(N, N, K, wt);
-    std::vector<float> b(N);
-    for (int n = 0; n < N; ++n) b[n] = bias(n);
-    L->N = N; L->K = K;
-    int rc = h->upload(packed, &L->w);
-    return rc ? rc : h->upload(b, &L->b);
-}
-// k x k conv, stream [ks][nt], reduction index = tap*Cin + ci (Cin padded), wt(n, tap, ci)
-template <typename F, typename G>
-int make_cnv(nunif_depth_anything *h, int N, int Cin, int k, F wt, G bias, Cnv *C, int cmaj = 0) {
-    const int NT = N / 16, KS = k * k * Cin / 32;
-    std::vector<f16> stream;
-    if (cmaj) {
-        // chunk-major (conv3_lds_cm_kernel): [chunk of `cmaj` channels][tap][32-channel half][n-tile]
-        stream.assign((size_t)KS * NT * kFragHalfs + kRingPadHalfs, (f16)0.f);
-        size_t frag = 0;
-        for (int q = 0; q < Cin / cmaj; ++q)
-            for (int tap = 0; tap < k * k; ++tap)
-                for (int c = 0; c < cmaj / 32; ++c)
-                    for (int nt = 0; nt < NT; ++nt, ++frag)
-                        put_frag(stream, frag, nt, c, false, [&](int n, int kk) { return wt(n, tap, q * cmaj + kk); });
-    } else {
-        stream = pack_ks_nt(N, N, k * k * Cin, [&](int n, int kk) { return wt(n, kk / Cin, kk % Cin); });
-    }
-    std::vector<float> b(N);
-    for (int n = 0; n < N; ++n) b[n] = bias(n);
-    C->N = N; C->Cin = Cin; C->k = k; C->cmaj = cmaj;
-    int rc = h->upload(stream, &C->w);
-    return rc ? rc : h->upload(b, &C->b);
-}
-int conv_from(nunif_depth_anything *h, const TensorMap &m, const std::string &key, int cout, int cin, int cin_pad, int k, bool has_bias,
-              Cnv *C, int cmaj = 0) {
-    const HostTensor *w, *b = nullptr;
-    int rc;
-    if ((rc = find(m, key + ".weight", &w)) || (has_bias && (rc = find(m, key + ".bias", &b)))) return rc;
-    NUNIF_REQUIRE(w->numel == (int64_t)cout * cin * k * k, "%s: unexpected shape", key.c_str());
-    const float *wd = w->data, *bd = b ? b->data : nullptr;
-    return make_cnv(h, cout, cin_pad, k, [=](int n, int tap, int ci) { return ci < cin ? wd[((size_t)n * cin + ci) * k * k + tap] : 0.f; },
-                    [=](int n) { return bd ? bd[n] : 0.f; }, C, cmaj);
-}
-
 int run_lin(const Lin &L, const f16 *a, int B, int Wi, int Wo, int ox, int act, const f16 *res, f16 *out, hipStream_t s,
             const char *tag, int mode = 0, int ldo = 0, int ps = 1, int Hi = 1, int lda = 0) {
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.a = a; g.B = B; g.Hi = Hi; g.Wi = Wi; g.Cin = L.K; g.Ho = Hi; g.Wo = Wo; g.stride = 1; g.ox = ox; g.kw = 1;
-    g.K = L.K; g.w = L.w; g.bias = L.b; g.N = L.N; g.mode = mode; g.act = act; g.res = res; g.out = out;
-    g.ldo = ldo ? ldo : L.N; g.n_real = L.N; g.ps = ps; g.lda = lda;
+    GemmArgs g = gemm_map_args(L, a, B, Hi, Wi, L.K, Hi, Wo, out, 1, 1, 0, ox);
+    g.mode = mode; g.act = act; g.res = res; g.ps = ps; g.lda = lda;
+    if (ldo) g.ldo = ldo;
     return launch_gemm(g, s, tag);
 }
 // token-matrix Linear [T][K] -> [T][N]: the output-stationary kernel when the shape allows, else gemm_kernel
 int run_tok(const Lin &L, const f16 *a, long T, int act, const f16 *res, f16 *out, hipStream_t s, const char *tag,
             float2 *stats_out = nullptr, const float2 *stats_in = nullptr) {
     if (gemm_os_supported(T, L.N, L.K)) {
-        GemmOsArgs g;
-        memset(&g, 0, sizeof(g));
-        g.a = a; g.M = T; g.lda = L.K; g.K = L.K; g.w = L.w; g.bias = L.b; g.N = L.N; g.act = act; g.res = res; g.out = out;
-        g.ldo = L.N; g.stats_out = stats_out; g.stats_in = stats_in; g.stats_parts = 12; g.wsum = L.ws; g.ln_eps = 1e-6f;
+        GemmOsArgs g = gemm_os_args(L, a, T, out);
+        g.act = act; g.res = res;
+        g.stats_out = stats_out; g.stats_in = stats_in; g.stats_parts = 12; g.wsum = L.ws; g.ln_eps = 1e-6f;
         return launch_gemm_os(g, s, tag);
     }
     NUNIF_REQUIRE(!stats_out && !stats_in, "%s: LayerNorm statistics need the output-stationary Linear", tag);
@@ -486,12 +438,8 @@ int run_tok(const Lin &L, const f16 *a, long T, int act, const f16 *res, f16 *ou
 }
 int run_cnv(const Cnv &C, const f16 *a, int B, int Hi, int Wi, int stride, int zpad, int relu_in, int act, const f16 *res,
             const f16 *res2, f16 *out, hipStream_t s, int ldo = 0, float *part32 = nullptr) {
-    ConvArgs c;
-    memset(&c, 0, sizeof(c));
-    c.a = a; c.B = B; c.Hi = Hi; c.Wi = Wi; c.Cin = C.Cin; c.stride = stride; c.kh = C.k; c.kw = C.k;
-    c.Ho = (Hi + 2 * zpad - C.k) / stride + 1; c.Wo = (Wi + 2 * zpad - C.k) / stride + 1;
-    c.wstream = C.w; c.bias = C.b; c.N = C.N; c.n_real = C.N; c.act = act; c.out = out; c.zpad = zpad; c.relu_in = relu_in;
-    c.res = res; c.res2 = res2; c.ldo = ldo; c.cmaj = C.cmaj; c.part32 = part32;
+    ConvArgs c = conv_args(C, a, B, Hi, Wi, out, stride, zpad);
+    c.act = act; c.relu_in = relu_in; c.res = res; c.res2 = res2; c.ldo = ldo; c.part32 = part32;
     return launch_conv(c, s);
 }
 }  // namespace
@@ -542,7 +490,7 @@ extern "C" int nunif_hip_depth_anything_create_ex(const nunif_tensor_desc *tenso
         if (rc) break;
         {
             const float *wd = w->data, *bd = b->data;
-            if ((rc = make_lin(h, kD, kKp, [=](int n, int k) { return k < 588 ? wd[(size_t)n * 588 + k] : 0.f; },
+            if ((rc = make_linear(h, kD, 16, kKp, [=](int n, int k) { return k < 588 ? wd[(size_t)n * 588 + k] : 0.f; },
                                [=](int n) { return bd[n]; }, &h->patch))) break;
         }
         if ((rc = find(m, P + "cls_token", &t1)) || (rc = h->upload_f32(t1, &h->cls))) break;
@@ -573,20 +521,20 @@ extern "C" int nunif_hip_depth_anything_create_ex(const nunif_tensor_desc *tenso
             const float *d;
             const float *e;
             d = wq->data; e = bq->data;
-            if ((rc = make_lin(h, 3 * kD, kD, [=](int n, int k) { return d[(size_t)n * kD + k] * (n < kD ? qs : 1.f); },
+            if ((rc = make_linear(h, 3 * kD, 16, kD, [=](int n, int k) { return d[(size_t)n * kD + k] * (n < kD ? qs : 1.f); },
                                [=](int n) { return e[n] * (n < kD ? qs : 1.f); }, &bk.qkv))) break;
             {   // LayerScale folded: ls * (W x + b)
                 const float *wd = wp->data, *bd = bpj->data, *ls = ls1->data;
-                if ((rc = make_lin(h, kD, kD, [=](int n, int k) { return wd[(size_t)n * kD + k] * ls[n]; },
+                if ((rc = make_linear(h, kD, 16, kD, [=](int n, int k) { return wd[(size_t)n * kD + k] * ls[n]; },
                                    [=](int n) { return bd[n] * ls[n]; }, &bk.proj))) break;
             }
             d = w1->data; e = bb1->data;
-            if ((rc = make_lin(h, 4 * kD, kD, [=](int n, int k) { return d[(size_t)n * kD + k]; }, [=](int n) { return e[n]; }, &bk.fc1))) break;
+            if ((rc = make_linear(h, 4 * kD, 16, kD, [=](int n, int k) { return d[(size_t)n * kD + k]; }, [=](int n) { return e[n]; }, &bk.fc1))) break;
             if (gemm_os_consumes_stats(1, 3 * kD, kD) && kD / 32 == 12) {
                 // norm1 / norm2 folded into their consumers: W (gamma xhat + beta) + b = (W diag(gamma)) xhat + (W beta + b), and
                 // xhat = (x - mu) r enters as r (W' x) - r mu wsum with wsum[n] = sum_k of the fp16 weights the MFMA really uses
                 auto fold = [&](const float *w, const float *b, const float *ga, const float *be, int N, float scale_upto, Lin *L) -> int {
-                    int rc2 = make_lin(h, N, kD, [=](int n, int k) { return w[(size_t)n * kD + k] * ga[k] * (n < kD ? scale_upto : 1.f); },
+                    int rc2 = make_linear(h, N, 16, kD, [=](int n, int k) { return w[(size_t)n * kD + k] * ga[k] * (n < kD ? scale_upto : 1.f); },
                                        [=](int n) {
                                            double acc = b[n];
                                            for (int k = 0; k < kD; ++k) acc += (double)(float)(f16)w[(size_t)n * kD + k] * be[k];
@@ -609,7 +557,7 @@ extern "C" int nunif_hip_depth_anything_create_ex(const nunif_tensor_desc *tenso
                 bk.n_fc2 = npiece;
                 if (gemm_os_supported(1, kD, 4 * kD)) {     // output-stationary GEMM: the whole K = 4 D contraction in one launch
                     bk.n_fc2 = 0;
-                    rc = make_lin(h, kD, 4 * kD, [=](int n, int k) { return wd[(size_t)n * 4 * kD + k] * ls[n]; },
+                    rc = make_linear(h, kD, 16, 4 * kD, [=](int n, int k) { return wd[(size_t)n * 4 * kD + k] * ls[n]; },
                                   [=](int n) { return bd[n] * ls[n]; }, &bk.fc2_full);
                     if (!rc && da_mlp_supported(kD, 4 * kD) && bk.fc1_ln.w) {
                         // the same matrix for the fused MLP kernel: its B operand is the hidden tile PAIR taken straight from
@@ -626,7 +574,7 @@ extern "C" int nunif_hip_depth_anything_create_ex(const nunif_tensor_desc *tenso
                     }
                 }
                 for (int q = 0; q < bk.n_fc2 && !rc; ++q)
-                    rc = make_lin(h, kD, kpiece, [=](int n, int k) { return wd[(size_t)n * 4 * kD + (size_t)q * kpiece + k] * ls[n]; },
+                    rc = make_linear(h, kD, 16, kpiece, [=](int n, int k) { return wd[(size_t)n * 4 * kD + (size_t)q * kpiece + k] * ls[n]; },
                                   [=](int n) { return q == 0 ? bd[n] * ls[n] : 0.f; }, &bk.fc2[q]);
                 if (rc) break;
             }
@@ -644,10 +592,10 @@ extern "C" int nunif_hip_depth_anything_create_ex(const nunif_tensor_desc *tenso
                 (rc = find(m, H + "projects." + std::to_string(i) + ".bias", &pb)))
                 break;
             const float *wd = pw->data, *bd = pb->data;
-            const int oc = (int)pb->numel, ocp = (oc + 31) / 32 * 32;
+            const int oc = (int)pb->numel, ocp = pad_to(oc, 32);
             if (pw->numel != (int64_t)oc * kD) { set_error("depth_head.projects.%d: unexpected shape", i); rc = NUNIF_HIP_EINVAL; break; }
             h->OC[i] = oc; h->OCP[i] = ocp;
-            if ((rc = make_lin(h, ocp, kD, [=](int n, int k) { return n < oc ? wd[(size_t)n * kD + k] : 0.f; },
+            if ((rc = make_linear(h, ocp, 16, kD, [=](int n, int k) { return n < oc ? wd[(size_t)n * kD + k] : 0.f; },
                                [=](int n) { return n < oc ? bd[n] : 0.f; }, &h->proj[i])))
                 break;
             // wide inputs (> 128 channels, a multiple of 64): chunk-major stream for conv3_lds_cm_kernel
@@ -655,7 +603,7 @@ extern "C" int nunif_hip_depth_anything_create_ex(const nunif_tensor_desc *tenso
                                 (getenv("NUNIF_CONV3_CM") && atoi(getenv("NUNIF_CONV3_CM")) == 0);      // read per engine (tests)
             // (chunks of 64 channels; 32 for the 128-wide fusion maps: 72 KiB of weights per workgroup either way)
             const int cmaj = (!cm_off && ocp > 128 && ocp % 64 == 0 && (F == 64 || F == 128)) ? (F == 128 ? 32 : 64) : 0;
-            rc = conv_from(h, m, H + "scratch.layer" + std::to_string(i + 1) + "_rn", F, oc, ocp, 3, false, &h->rn[i], cmaj);
+            rc = conv_from(h, m, H + "scratch.layer" + std::to_string(i + 1) + "_rn", F, 16, oc, ocp, 3, &h->rn[i], false, cmaj);
         }
         if (rc) break;
         {   // resize_layers.0: ConvTranspose2d(oc0, oc0, 4, 4): N = (i*4+j)*ocp0 + co, K = ci (padded); weight [ci][co][4][4]
@@ -663,7 +611,7 @@ extern "C" int nunif_hip_depth_anything_create_ex(const nunif_tensor_desc *tenso
             const float *wd = w->data, *bd = b->data;
             const int o0 = h->OC[0], p0 = h->OCP[0];
             if (w->numel != (int64_t)o0 * o0 * 16) { set_error("depth_head.resize_layers.0: unexpected shape"); rc = NUNIF_HIP_EINVAL; break; }
-            if ((rc = make_lin(h, 16 * p0, p0, [=](int n, int k) {
+            if ((rc = make_linear(h, 16 * p0, 16, p0, [=](int n, int k) {
                     const int q = n / p0, co = n % p0;
                     return (co < o0 && k < o0) ? wd[((size_t)k * o0 + co) * 16 + q] : 0.f; },
                     [=](int n) { return n % p0 < o0 ? bd[n % p0] : 0.f; }, &h->rs0))) break;
@@ -672,7 +620,7 @@ extern "C" int nunif_hip_depth_anything_create_ex(const nunif_tensor_desc *tenso
             const float *w1d = w->data, *b1d = b->data;
             const int o1 = h->OC[1];
             if (o1 % 32 || w->numel != (int64_t)o1 * o1 * 4) { set_error("depth_head.resize_layers.1: unexpected shape"); rc = NUNIF_HIP_EINVAL; break; }
-            if ((rc = make_lin(h, 4 * o1, o1, [=](int n, int k) { return w1d[((size_t)k * o1 + n % o1) * 4 + n / o1]; },
+            if ((rc = make_linear(h, 4 * o1, 16, o1, [=](int n, int k) { return w1d[((size_t)k * o1 + n % o1) * 4 + n / o1]; },
                                [=](int n) { return b1d[n % o1]; }, &h->rs1))) break;
             // resize_layers.3: Conv2d(oc3, oc3, 3, stride 2, pad 1); conv_kernel holds <= 384 output channels per launch: chunks
             if ((rc = find(m, H + "resize_layers.3.weight", &w)) || (rc = find(m, H + "resize_layers.3.bias", &b))) break;
@@ -680,7 +628,7 @@ extern "C" int nunif_hip_depth_anything_create_ex(const nunif_tensor_desc *tenso
             if (o3 % 32 || h->OC[2] % 32 || w->numel != (int64_t)o3 * o3 * 9) { set_error("depth_head.resize_layers.3: unexpected shape"); rc = NUNIF_HIP_EINVAL; break; }
             if (gemm_os_supported(1, o3, 9 * o3)) {         // im2col + output-stationary Linear (k = tap * C + ci)
                 const float *w3g = w->data, *b3g = b->data;
-                if ((rc = make_lin(h, o3, 9 * o3, [=](int n, int k) { const int tap = k / o3, ci = k % o3; return w3g[((size_t)n * o3 + ci) * 9 + tap]; },
+                if ((rc = make_linear(h, o3, 16, 9 * o3, [=](int n, int k) { const int tap = k / o3, ci = k % o3; return w3g[((size_t)n * o3 + ci) * 9 + tap]; },
                                    [=](int n) { return b3g[n]; }, &h->rs3g))) break;
             }
             const int chunk = o3 <= 384 ? o3 : 256;
@@ -688,26 +636,26 @@ extern "C" int nunif_hip_depth_anything_create_ex(const nunif_tensor_desc *tenso
             if (!h->rs3g.w) h->rs3.resize(o3 / chunk);
             const float *w3 = w->data, *b3 = b->data;
             for (int c = 0; c < (int)h->rs3.size() && !rc; ++c)
-                rc = make_cnv(h, chunk, o3, 3, [=](int n, int tap, int ci) { return w3[((size_t)(c * chunk + n) * o3 + ci) * 9 + tap]; },
-                              [=](int n) { return b3[c * chunk + n]; }, &h->rs3[c]);
+                rc = upload(h, pack_conv(chunk, 16, o3, o3, 3, 0, [=](int n, int tap, int ci) { return w3[((size_t)(c * chunk + n) * o3 + ci) * 9 + tap]; },
+                                         [=](int n) { return b3[c * chunk + n]; }), &h->rs3[c]);
             if (rc) break;
         }
         for (int k = 0; k < 4 && !rc; ++k) {
             const std::string r = H + "scratch.refinenet" + std::to_string(k + 1) + ".";
             Fus &f = h->fus[k];
-            if ((rc = conv_from(h, m, r + "resConfUnit1.conv1", F, F, F, 3, true, &f.r1.c1)) ||
-                (rc = conv_from(h, m, r + "resConfUnit1.conv2", F, F, F, 3, true, &f.r1.c2)) ||
-                (rc = conv_from(h, m, r + "resConfUnit2.conv1", F, F, F, 3, true, &f.r2.c1)) ||
-                (rc = conv_from(h, m, r + "resConfUnit2.conv2", F, F, F, 3, true, &f.r2.c2)))
+            if ((rc = conv_from(h, m, r + "resConfUnit1.conv1", F, 16, F, F, 3, &f.r1.c1)) ||
+                (rc = conv_from(h, m, r + "resConfUnit1.conv2", F, 16, F, F, 3, &f.r1.c2)) ||
+                (rc = conv_from(h, m, r + "resConfUnit2.conv1", F, 16, F, F, 3, &f.r2.c1)) ||
+                (rc = conv_from(h, m, r + "resConfUnit2.conv2", F, 16, F, F, 3, &f.r2.c2)))
                 break;
             const HostTensor *ow, *ob;
             if ((rc = find(m, r + "out_conv.weight", &ow)) || (rc = find(m, r + "out_conv.bias", &ob))) break;
             const float *wd = ow->data, *bd = ob->data;
-            rc = make_lin(h, F, F, [=](int n, int kk) { return wd[(size_t)n * F + kk]; }, [=](int n) { return bd[n]; }, &f.out);
+            rc = make_linear(h, F, 16, F, [=](int n, int kk) { return wd[(size_t)n * F + kk]; }, [=](int n) { return bd[n]; }, &f.out);
         }
         if (rc) break;
-        if ((rc = conv_from(h, m, H + "scratch.output_conv1", F / 2, F, F, 3, true, &h->oc1)) ||
-            (rc = conv_from(h, m, H + "scratch.output_conv2.0", 32, F / 2, F / 2, 3, true, &h->oc2)))
+        if ((rc = conv_from(h, m, H + "scratch.output_conv1", F / 2, 16, F, F, 3, &h->oc1)) ||
+            (rc = conv_from(h, m, H + "scratch.output_conv2.0", 32, 16, F / 2, F / 2, 3, &h->oc2)))
             break;
         if ((rc = find(m, H + "scratch.output_conv2.2.weight", &w)) || (rc = find(m, H + "scratch.output_conv2.2.bias", &b))) break;
         std::vector<float> wf(33);
@@ -741,7 +689,7 @@ extern "C" int nunif_hip_depth_anything_create_ex(const nunif_tensor_desc *tenso
                 break;
             auto plain = [&](const HostTensor *w, const HostTensor *b, int N, int K, Lin *L) {
                 const float *wd = w->data, *bd = b ? b->data : nullptr;
-                return make_lin(h, N, K, [=](int n, int k) { return wd[(size_t)n * K + k]; }, [=](int n) { return bd ? bd[n] : 0.f; }, L);
+                return make_linear(h, N, 16, K, [=](int n, int k) { return wd[(size_t)n * K + k]; }, bias_at(bd), L);
             };
             if ((rc = plain(wi, bi, C, C, &tmod.proj_in)) || (rc = plain(wo, bo, C, C, &tmod.proj_out)) ||
                 (rc = plain(w1, bb1, 8 * C, C, &tmod.ff1)) || (rc = plain(w2, bb2, C, 4 * C, &tmod.ff2)))
@@ -761,7 +709,7 @@ extern "C" int nunif_hip_depth_anything_create_ex(const nunif_tensor_desc *tenso
                 }
                 if ((rc = h->upload_f32(ng, &at.g)) || (rc = h->upload_f32(nb, &at.b)) || (rc = plain(wo2, bo2, C, C, &at.out))) break;
                 const float *q = wq->data, *k = wk->data, *v = wv->data;
-                if ((rc = make_lin(h, 3 * C, C, [=](int n, int kk) {
+                if ((rc = make_linear(h, 3 * C, 16, C, [=](int n, int kk) {
                         return n < C ? q[(size_t)n * C + kk] * qs : n < 2 * C ? k[(size_t)(n - C) * C + kk] : v[(size_t)(n - 2 * C) * C + kk]; },
                         [](int) { return 0.f; }, &at.qkv)))
                     break;
@@ -1068,7 +1016,7 @@ static int da_forward(nunif_depth_anything *h, const float *x, const float *pos,
             // fc1 + GELU + fc2 + residual (+ the next norm1's statistics) in one kernel: the hidden rows never leave the CU
             DaMlpArgs ma;
             memset(&ma, 0, sizeof(ma));
-            ma.t = t; ma.M = T; ma.w1 = bk.fc1_ln.w; ma.b1 = bk.fc1_ln.b; ma.ws1 = bk.fc1_ln.ws; ma.w2c = bk.fc2c; ma.b2 = bk.fc2_full.b;
+            ma.t = t; ma.M = T; ma.w1 = bk.fc1_ln.w; ma.b1 = bk.fc1_ln.bias; ma.ws1 = bk.fc1_ln.ws; ma.w2c = bk.fc2c; ma.b2 = bk.fc2_full.bias;
             ma.stats_in = lnstats; ma.stats_out = ln1_next ? lnstats : nullptr; ma.ln_eps = 1e-6f;
             // the split form needs BOTH blocks of a pair resident; that holds while it is the only spin-waiting grid on the
             // device (depth_mlp.hip launch_da_mlp) — `lease`, above

@@ -19,8 +19,7 @@
 #include <string>
 #include <vector>
 
-#include "host_weights.h"
-#include "swin_kernels.h"
+#include "packed_layers.h"
 
 namespace nunif {
 
@@ -423,19 +422,17 @@ using namespace nunif;
 // =====================================================================================================================
 namespace {
 
-struct Lin { f16 *w = nullptr; float *bias = nullptr; int N = 0, K = 0; };                 // gemm_kernel packing [nt][ks]
-struct Conv3 {                                                  // conv_kernel stream [ks][nt]
-    f16 *stream = nullptr; float *bias = nullptr; int N = 0, n_real = 0, Cin = 0;
+struct Conv3 : PackedConv {
     // the same weights as streams of OUTPUT-CHANNEL SLICES whose tile counts the LDS-staged convs take (conv3_dma: Cin 32 / 64,
     // 1 / 2 / 4 / 8 tiles; conv3_lds: Cin <= 128, the same counts): 96 = 64 + 32, 192 = 128 + 64.  A slice writes its channels
     // of the NHWC map through ConvArgs::ldo; the input patch is staged once per slice.
-    f16 *slice_stream[2] = {nullptr, nullptr}; int slice_nt[2] = {0, 0}, n_slices = 0;
+    std::vector<ConvSlice> slices;
 };
 struct GBlock {
     int C = 0, V = 0, ws = 0, shift = 0, temporal = 0;      // V = gate / value width (mlp_ratio * C); temporal: window (12,1,1)
     TMix tmix;
     float *ln1 = nullptr, *ln2 = nullptr;
-    Lin proj_in, spatial, proj_out, w1;
+    PackedLinear proj_in, spatial, proj_out, w1;
     Conv3 w2;
 };
 
@@ -443,70 +440,28 @@ struct GBlock {
 
 struct nunif_light_inpaint : DeviceOwner {
     f16 *mask_bias = nullptr;
-    Lin patch, down, up;
+    PackedLinear patch, down, up;
     // video = inpaint.light_video_inpaint_v1: patch slope 0.1, enc1 unshifted, enc2 = [2-D, temporal, 2-D, temporal, 2-D] with
     // mlp_ratio 1 in the 2-D blocks, 1x1 to_image; exactly 12 frames per call
     int video = 0, n_enc2 = 4;
     int C = 96;               // base_dim: 96 (image net, video small), 128 (video medium), 192 (video large)
     GBlock enc1, enc2[5], dec1;
     Conv3 to_image;
-    Lin to_image1;
+    PackedLinear to_image1;
     Gauss15 gauss;
     DeviceBuf x1, x2, a, pi, vt, st, g, po, y, z, ti, mtok, mf0, mf1, mf2, hard, soft;
 };
 
 namespace {
 
-// W[n][k] (n < n_real, k < K) -> MFMA A fragments in [n-tile][k-step] order
-template <typename F>
-int make_lin(nunif_light_inpaint *h, int n_real, int K, F wt, const std::vector<float> &bias, Lin *L) {
-    const int N = (n_real + 31) / 32 * 32;
-    std::vector<f16> packed = pack_nt_ks(n_real, N, K, wt);
-    std::vector<float> b(N, 0.f);
-    std::copy(bias.begin(), bias.end(), b.begin());
-    L->N = N; L->K = K;
-    int rc = h->upload(packed, &L->w);
-    return rc ? rc : h->upload(b, &L->bias);
-}
-
-// 3x3 conv weight [cout][cin_real][3][3] -> conv_kernel stream [k-step][n-tile], k = tap * cin + ci (cin = cin_real padded)
+// 3x3 conv weight [cout][cin_real][3][3] -> conv_kernel stream, cin = cin_real padded; N padded to 32
 int make_conv3(nunif_light_inpaint *h, const TensorMap &m, const std::string &key, int cin_real, int cin, int cout, Conv3 *c) {
-    const HostTensor *w, *b;
+    ConvHost host;
     int rc;
-    if ((rc = find(m, key + ".weight", &w)) || (rc = find(m, key + ".bias", &b))) return rc;
-    NUNIF_REQUIRE(w->numel == (int64_t)cout * cin_real * 9 && b->numel == cout, "%s: unexpected shape", key.c_str());
-    const int N = (cout + 31) / 32 * 32, NT = N / 16, KS = 9 * cin / 32;
-    const float *wd = w->data;
-    std::vector<f16> stream = pack_ks_nt(cout, N, 9 * cin, [=](int n, int kk) {
-        const int tap = kk / cin, ci = kk % cin;
-        return ci < cin_real ? wd[((size_t)n * cin_real + ci) * 9 + tap] : 0.f;
-    });
-    std::vector<float> bias(N, 0.f);
-    std::copy(b->data, b->data + cout, bias.begin());
-    c->N = N; c->n_real = cout; c->Cin = cin;
-    if ((rc = h->upload(stream, &c->stream))) return rc;
-    if ((NT == 6 || NT == 12) && cout == N && cin <= 128) {
-        const int parts[2] = {NT == 6 ? 4 : 8, NT == 6 ? 2 : 4};
-        int nt0 = 0;
-        for (int q = 0; q < 2; ++q) {
-            const int nts = parts[q];
-            if ((rc = h->upload(stream_slice(stream, KS, NT, nt0, nts), &c->slice_stream[q]))) return rc;
-            c->slice_nt[q] = nts;
-            nt0 += nts;
-        }
-        c->n_slices = 2;
-    }
-    return h->upload(bias, &c->bias);
-}
-
-int make_plain(nunif_light_inpaint *h, const TensorMap &m, const std::string &key, int n_real, int K, Lin *L) {
-    const HostTensor *w, *b;
-    int rc;
-    if ((rc = find(m, key + ".weight", &w)) || (rc = find(m, key + ".bias", &b))) return rc;
-    NUNIF_REQUIRE(w->numel == (int64_t)n_real * K && b->numel == n_real, "%s: unexpected shape", key.c_str());
-    const float *wd = w->data;
-    return make_lin(h, n_real, K, [=](int n, int k) { return wd[(size_t)n * K + k]; },
-                    std::vector<float>(b->data, b->data + n_real), L);
+    if ((rc = conv_from(h, m, key, cout, 32, cin_real, cin, 3, c, true, 0, &host))) return rc;
+    const int NT = c->N / 16;
+    if ((NT == 6 || NT == 12) && cout == c->N && cin <= 128) return upload_slices(h, host, {NT == 6 ? 4 : 8, NT == 6 ? 2 : 4}, &c->slices);
+    return NUNIF_HIP_OK;
 }
 
 int make_gblock(nunif_light_inpaint *h, const TensorMap &m, const std::string &p, int C, int ws, int shift, GBlock *g,
@@ -531,44 +486,30 @@ int make_gblock(nunif_light_inpaint *h, const TensorMap &m, const std::string &p
             g->tmix.b[t] = sb->data[t];
             for (int s2 = 0; s2 < 12; ++s2) g->tmix.w[t][s2] = sw->data[t * 12 + s2];
         }
-    } else if ((rc = make_plain(h, m, p + "gmlp.gmlp.proj_spatial", N, N, &g->spatial))) {   // Conv1d(N, N, 1): weight [N][N][1]
+    } else if ((rc = linear_from(h, m, p + "gmlp.gmlp.proj_spatial", N, N, 32, &g->spatial))) {   // Conv1d(N, N, 1): weight [N][N][1]
         return rc;
     }
-    if ((rc = make_plain(h, m, p + "gmlp.gmlp.proj_in", 2 * V, C, &g->proj_in)) ||
-        (rc = make_plain(h, m, p + "gmlp.gmlp.proj_out", C, V, &g->proj_out)) ||
-        (rc = make_plain(h, m, p + "glu_conv.w1", C, C, &g->w1)))
+    if ((rc = linear_from(h, m, p + "gmlp.gmlp.proj_in", 2 * V, C, 32, &g->proj_in)) ||
+        (rc = linear_from(h, m, p + "gmlp.gmlp.proj_out", C, V, 32, &g->proj_out)) ||
+        (rc = linear_from(h, m, p + "glu_conv.w1", C, C, 32, &g->w1)))
         return rc;
-    return make_conv3(h, m, p + "glu_conv.w2", C / 2, (C / 2 + 31) / 32 * 32, C, &g->w2);
+    return make_conv3(h, m, p + "glu_conv.w2", C / 2, pad_to(C / 2, 32), C, &g->w2);
 }
 
 // A 3x3 conv whose output width is not a tile count the LDS-staged convs take, as two launches over channel slices (Conv3).
 static inline int li_conv_slices() { const char *e = getenv("NUNIF_LI_CONV_SLICES"); return e ? atoi(e) : 1; }
 int launch_conv3_sliced(const Conv3 &c, const ConvArgs &cv, hipStream_t s) {
-    if (!c.n_slices || !li_conv_slices() || cv.n_real != c.N) return launch_conv(cv, s);
-    ConvArgs t = cv;
-    t.N = c.slice_nt[0] * 16; t.n_real = t.N; t.wstream = c.slice_stream[0];
+    if (c.slices.empty() || !li_conv_slices() || cv.n_real != c.N) return launch_conv(cv, s);
+    const ConvArgs t = conv_slice_args(cv, c.slices[0], 0);
     if (!conv3_dma_applies(t) && !conv3_lds_applies(t)) return launch_conv(cv, s);
-    int n0 = 0, rc;
-    for (int q = 0; q < c.n_slices; ++q) {
-        t = cv;
-        t.N = c.slice_nt[q] * 16; t.n_real = t.N; t.wstream = c.slice_stream[q]; t.bias = cv.bias + n0;
-        t.ldo = cv.ldo > 0 ? cv.ldo : cv.n_real;
-        t.out = cv.out + n0;
-        if (cv.res) t.res = cv.res + n0;
-        if (cv.res2) t.res2 = cv.res2 + n0;
-        if ((rc = launch_conv(t, s))) return rc;
-        n0 += t.N;
-    }
-    return NUNIF_HIP_OK;
+    return launch_conv_sliced(cv, c.slices, s);
 }
 
-int lin(const Lin &L, const f16 *a, long rows, int n_real, int act, float slope, const f16 *res, f16 *out, hipStream_t s,
+// token Linear [rows][K] -> [rows][n_real]; n_real may be less than the layer's (the temporal blocks' narrower gate)
+int lin(const PackedLinear &L, const f16 *a, long rows, int n_real, int act, float slope, const f16 *res, f16 *out, hipStream_t s,
         const char *tag) {
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.a = a; g.B = 1; g.Hi = 1; g.Wi = (int)rows; g.Cin = L.K; g.Ho = 1; g.Wo = (int)rows; g.stride = 1; g.kw = 1;
-    g.K = L.K; g.w = L.w; g.bias = L.bias; g.N = L.N; g.mode = 0; g.act = act; g.slope = slope; g.res = res; g.out = out;
-    g.ldo = n_real; g.n_real = n_real; g.ps = 1;
+    GemmArgs g = gemm_token_args(L, a, rows, out);
+    g.act = act; g.slope = slope; g.res = res; g.ldo = n_real; g.n_real = n_real;
     // K = 192 -> 768 over millions of tokens (proj_in of the 1/8-resolution blocks at 4K): 288 KiB of weights do not fit the
     // resident-weight GEMM's LDS, and the ring form runs it at 1.1 TB/s (2.8 ms).  Two launches over the output halves (the packed
     // weights are n-tile major: the second half is an offset) read the rows twice and still finish in less than half the time.
@@ -630,10 +571,8 @@ int run_gblock(nunif_light_inpaint *h, const GBlock &g, f16 *x, int B, int hh, i
         ProfScope ps("li_glu_kernel", s, 0.0, (double)tok * C * 3.0);
         li_glu_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(y, z, tok, C, g.w2.Cin);
     }
-    ConvArgs cv;
-    memset(&cv, 0, sizeof(cv));
-    cv.a = z; cv.B = B; cv.Hi = hh; cv.Wi = ww; cv.Cin = g.w2.Cin; cv.Ho = hh; cv.Wo = ww; cv.stride = 1; cv.kh = 3; cv.kw = 3;
-    cv.wstream = g.w2.stream; cv.bias = g.w2.bias; cv.N = g.w2.N; cv.n_real = C; cv.act = 0; cv.out = x; cv.rpad = 1; cv.res = x;
+    ConvArgs cv = conv_args(g.w2, z, B, hh, ww, x, 1, 0, 1);
+    cv.res = x;
     if ((rc = launch_conv3_sliced(g.w2, cv, s))) return rc;
     NUNIF_LAUNCH_CHECK();
     return NUNIF_HIP_OK;
@@ -686,21 +625,20 @@ extern "C" int nunif_hip_light_inpaint_create(const nunif_tensor_desc *tensors, 
         if ((rc = h->upload(mbh, &h->mask_bias))) break;
         {   // patch: 1x1 conv 48 -> C on the pixel_unshuffle(4) channels (input padded to 64)
             const float *wd = pw->data;
-            if ((rc = make_lin(h, C, 64, [=](int n, int k) { return k < 48 ? wd[(size_t)n * 48 + k] : 0.f; },
-                               std::vector<float>(pb->data, pb->data + C), &h->patch)))
+            if ((rc = make_linear(h, C, 32, 48, [=](int n, int k) { return wd[(size_t)n * 48 + k]; }, bias_at(pb->data), &h->patch)))
                 break;
         }
         {   // down: Conv2d(C, 2C, 2, 2): weight [2C][C][2][2] -> k = (i*2 + j) * C + ci
             const float *wd = dw->data;
-            if ((rc = make_lin(h, C2, 4 * C, [=](int n, int k) { return wd[((size_t)n * C + k % C) * 4 + k / C]; },
-                               std::vector<float>(db->data, db->data + C2), &h->down)))
+            if ((rc = make_linear(h, C2, 32, 4 * C, [=](int n, int k) { return wd[((size_t)n * C + k % C) * 4 + k / C]; },
+                                  bias_at(db->data), &h->down)))
                 break;
         }
         {   // up: 1x1 conv 2C -> 4C + F.pixel_shuffle(2): rows c*4 + q -> q*C + c (gemm mode 1 column order)
             const float *wd = uw->data;
-            std::vector<float> bb(4 * C);
-            for (int n = 0; n < 4 * C; ++n) bb[n] = ub->data[(n % C) * 4 + n / C];
-            if ((rc = make_lin(h, 4 * C, C2, [=](int n, int k) { return wd[(size_t)((n % C) * 4 + n / C) * C2 + k]; }, bb, &h->up)))
+            const float *bd = ub->data;
+            if ((rc = make_linear(h, 4 * C, 32, C2, [=](int n, int k) { return wd[(size_t)((n % C) * 4 + n / C) * C2 + k]; },
+                                  [=](int n) { return bd[(n % C) * 4 + n / C]; }, &h->up)))
                 break;
         }
         if (h->video) {
@@ -713,14 +651,7 @@ extern "C" int nunif_hip_light_inpaint_create(const nunif_tensor_desc *tensors, 
                                  temporal[i]);
             if (rc) break;
             if ((rc = make_gblock(h, m, "dec1.", C, 16, 0, &h->dec1))) break;
-            const HostTensor *tw, *tb;
-            if ((rc = find(m, "to_image.weight", &tw)) || (rc = find(m, "to_image.bias", &tb))) break;
-            NUNIF_REQUIRE(tw->numel == (int64_t)48 * C && tb->numel == 48, "to_image: unexpected shape");
-            const float *wd = tw->data;
-            std::vector<float> bb(64, 0.f);
-            std::copy(tb->data, tb->data + 48, bb.begin());
-            if ((rc = make_lin(h, 64, C, [=](int n, int k) { return n < 48 ? wd[(size_t)n * C + k] : 0.f; }, bb, &h->to_image1)))
-                break;
+            if ((rc = linear_from(h, m, "to_image", 48, C, 32, &h->to_image1))) break;
         } else {
             if ((rc = make_gblock(h, m, "enc1.", 96, 16, 1, &h->enc1))) break;
             for (int i = 0; i < 4 && !rc; ++i) rc = make_gblock(h, m, "enc2." + std::to_string(i) + ".", 192, 8, i & 1, &h->enc2[i]);
@@ -810,22 +741,15 @@ extern "C" int nunif_hip_light_inpaint_infer_ex(nunif_light_inpaint *h, const fl
     }
     if ((rc = run_gblock_any(h, h->enc1, x1, B, h1, w1, s))) return rc;
     {   // down: 2x2 stride-2 conv as a gather GEMM
-        GemmArgs g;
-        memset(&g, 0, sizeof(g));
-        g.a = x1; g.B = B; g.Hi = h1; g.Wi = w1; g.Cin = C; g.Ho = h2; g.Wo = w2; g.stride = 2; g.kw = 2;
-        g.K = 4 * C; g.w = h->down.w; g.bias = h->down.bias; g.N = h->down.N; g.mode = 0; g.out = x2; g.ldo = C2; g.n_real = C2;
-        g.ps = 1;
+        GemmArgs g = gemm_map_args(h->down, x1, B, h1, w1, C, h2, w2, x2, 2, 2);
         if ((rc = launch_gemm(g, s, "li_down"))) return rc;
     }
     for (int i = 0; i < h->n_enc2; ++i) {
         if ((rc = run_gblock_any(h, h->enc2[i], x2, B, h2, w2, s))) return rc;
     }
     {   // x = x1 + pixel_shuffle(up(x2), 2), written over x1
-        GemmArgs g;
-        memset(&g, 0, sizeof(g));
-        g.a = x2; g.B = B; g.Hi = h2; g.Wi = w2; g.Cin = C2; g.Ho = h2; g.Wo = w2; g.stride = 1; g.kw = 1;
-        g.K = C2; g.w = h->up.w; g.bias = h->up.bias; g.N = h->up.N; g.mode = 1; g.res = x1; g.out = x1; g.ldo = C; g.n_real = 4 * C;
-        g.ps = 1;
+        GemmArgs g = gemm_map_args(h->up, x2, B, h2, w2, C2, h2, w2, x1);
+        g.mode = 1; g.res = x1; g.ldo = C;
         // K = 192 -> 4 x 96 / 4 x 192 with the skip map as residual is the swin PatchUp's shape: its resident-weight kernel with
         // the skip tiles four trips ahead (swin_patchup.hip) takes it — every launch of that shape
         PatchUpArgs pu = {x2, h->up.w, h->up.bias, x1, x1, B, h2, w2, C, 0};
@@ -837,11 +761,7 @@ extern "C" int nunif_hip_light_inpaint_infer_ex(nunif_light_inpaint *h, const fl
     if (h->video) {
         if ((rc = lin(h->to_image1, x1, t1, 64, 0, 0.f, nullptr, ti, s, "li_to_image"))) return rc;
     } else {
-        ConvArgs cv;
-        memset(&cv, 0, sizeof(cv));
-        cv.a = x1; cv.B = B; cv.Hi = h1; cv.Wi = w1; cv.Cin = 96; cv.Ho = h1; cv.Wo = w1; cv.stride = 1; cv.kh = 3; cv.kw = 3;
-        cv.wstream = h->to_image.stream; cv.bias = h->to_image.bias; cv.N = h->to_image.N; cv.n_real = 48; cv.act = 0; cv.out = ti;
-        cv.rpad = 1;
+        ConvArgs cv = conv_args(h->to_image, x1, B, h1, w1, ti, 1, 0, 1);
         if ((rc = launch_conv(cv, s))) return rc;
     }
     {

@@ -11,7 +11,7 @@ struct GemmArgs {
     const f16 *a; int B, Hi, Wi, Cin;
     int Ho, Wo, stride, oy, ox, kw;
     int K;                    // taps*Cin, multiple of 32
-    const f16 *w;             // packed [N/16][K/32][64 lanes][8] (see pack_weight_frag in swin_unet.cpp)
+    const f16 *w;             // packed [N/16][K/32][64 lanes][8] (PackedLinear, packed_layers.h; layout: put_frag, host_weights.h)
     const float *bias;        // [N] (padded)
     int N;                    // padded to a multiple of 16
     int mode;                 // 0: NHWC fp16 [M][ldo]   1: 2x2 pixel-shuffle NHWC fp16   2: to_image NCHW f32 clamp
@@ -38,7 +38,7 @@ struct GemmArgs {
 int launch_gemm(const GemmArgs &g, hipStream_t s, const char *tag);
 
 // ---- PatchUp of the swin U-Nets (swin_patchup.hip): out = pixel_shuffle_2(Linear(192 -> 4 Cq)(a)) + res, NHWC fp16 ---------------
-// a: [B, Ho, Wo, 192]; w / bias: make_linear's packing with columns n = q Cq + c (q = 2 i + j the sub-pixel); res / out:
+// a: [B, Ho, Wo, 192]; w / bias: a PackedLinear (packed_layers.h) with columns n = q Cq + c (q = 2 i + j the sub-pixel); res / out:
 // [B, 2 Ho, 2 Wo, Cq] (out may alias res).  Cq = 96 or 192.  Weights resident in LDS, persistent workgroups, the next token
 // group's activations and the skip tiles of the next four trips in flight.
 // list (frame renders, swin_unet.cpp skip_plan): the launch walks the n_list INPUT tokens list[] names, (b Ho + y) Wo + x, instead of all
@@ -51,7 +51,7 @@ int launch_patchup(const PatchUpArgs &g, hipStream_t s);
 // ---- PatchDown of the swin U-Nets (swin_patchdown.hip): out[b, y, x, 192] = bias + sum over the taps of a 2 x 2 stride-2 patch --------
 // a: [B, 2 Ho, 2 Wo, Cin]; Cin = 96: K = 384 = the four taps (dy, dx) of a token, k = (2 dy + dx) Cin + c; Cin = 192: K = 384 = the
 // two taps of input row 2 y + oy (the other row is a second, accumulating pass on gemm_res_kernel); Cin = 64, N = 64: cunet's
-// Conv2d(64, 64, 2, 2) + LeakyReLU.  w / bias: make_linear's packing ([n-tile][k-step]).
+// Conv2d(64, 64, 2, 2) + LeakyReLU.  w / bias: a PackedLinear (packed_layers.h, [n-tile][k-step]).
 // list: as PatchUpArgs', OUTPUT tokens.  acc (Cin = 192): out += the pass, as gemm_res_kernel<12,2> with out as its residual computes it.
 struct PatchDownArgs { const f16 *a, *w; const float *bias; f16 *out; int B, Ho, Wo, Cin, oy, rev; int N = 192; int act = 0; float slope = 0.f;      // act 2: LeakyReLU(slope)
                        const unsigned *list = nullptr; unsigned n_list = 0; int acc = 0; };
@@ -227,7 +227,7 @@ struct ConvArgs {
     const f16 *a; const f16 *a2;
     int H2, W2, crop2;
     int B, Hi, Wi, Cin, Ho, Wo, stride, kh, kw;
-    const f16 *wstream;       // fragments in [k-step][n-tile] order, k = tap*Cin + ci, zero-padded by 16 KiB
+    const f16 *wstream;       // a PackedConv's stream (packed_layers.h): fragments in [k-step][n-tile] order, k = tap*Cin + ci, zero-padded by 16 KiB
     const float *bias;        // [N]
     int N, n_real;
     int act; float slope;     // 0 none, 2 LeakyReLU(slope), 3 ReLU

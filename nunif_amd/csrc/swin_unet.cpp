@@ -10,8 +10,7 @@
 #include <string>
 #include <vector>
 
-#include "host_weights.h"
-#include "swin_kernels.h"
+#include "packed_layers.h"
 #include "swin_skip_plan_host.h"
 
 namespace nunif {
@@ -21,17 +20,11 @@ int launch_stitch(const float *tile_out, float *y, const nunif_tile_grid *g, int
 
 namespace {
 
-struct Linear {          // fragment-packed fp16 weight + fp32 bias, device memory
-    f16 *w = nullptr;
-    float *bias = nullptr;
-    int N = 0, n_real = 0, K = 0;
-};
-
 struct Block {
-    Linear qkv, proj, mlp0, mlp3;
+    PackedLinear qkv, proj, mlp0, mlp3;
     // generic path (LayerNorm variants, head counts other than 6: swin_unet_4xl): mlp.0 / mlp.3 in the PLAIN k order for
     // gemm_kernel, LayerNormNoBias weights (nunif/modules/norm.py:17-22)
-    Linear mlp0p, mlp3p;
+    PackedLinear mlp0p, mlp3p;
     float *norm1 = nullptr, *norm2 = nullptr;
     bool fast = true;             // fused qkv+attention / register-chained tail kernels apply
     float *attn_bias = nullptr;   // [heads][36][48]
@@ -119,8 +112,8 @@ struct nunif_swin_unet : DeviceOwner {       // owns every device allocation mad
     int C1 = 48, C1P = 64;            // stem conv1 channels (real / padded to a multiple of 32)
     int top_dim = 96;                 // channels of level 1 on the decoder side (C for 1x/2x, 2C for 4x)
     float *stem1_w = nullptr, *stem1_b = nullptr;
-    Linear stem2, down1, down2, up2, up1, proj2, to_image, to_image_pre;
-    Linear down2b;                    // second tap row of down2 when 4 * Cin > 1024 (swin_unet_4xl: K = 1536 as two K = 768 passes)
+    PackedLinear stem2, down1, down2, up2, up1, proj2, to_image, to_image_pre;
+    PackedLinear down2b;                    // second tap row of down2 when 4 * Cin > 1024 (swin_unet_4xl: K = 1536 as two K = 768 passes)
     bool down2_split = false;
     f16 *to_image_chained = nullptr;  // ToImage weights in the chained k order, for the fused head of the last C = 96 block
     f16 *stemf_w1 = nullptr, *stemf_w2 = nullptr;   // fused stem (swin_stem.hip)
@@ -160,33 +153,6 @@ struct nunif_swin_unet : DeviceOwner {       // owns every device allocation mad
 namespace nunif {
 namespace {
 
-int pad16(int n) { return (n + 15) / 16 * 16; }
-
-// fragment layout, plain and chained k order: host_weights.h (put_frag).  `wt(n,k)` returns fp32.
-template <typename F>
-int make_linear(nunif_swin_unet *h, int n_real, int K, F wt, const float *bias, Linear *L, bool chained = false,
-                std::vector<f16> *keep = nullptr) {
-    const int N = pad16(n_real);
-    std::vector<f16> packed = pack_nt_ks(n_real, N, K, wt, chained);
-    std::vector<float> b(N, 0.0f);
-    for (int n = 0; n < n_real; ++n) b[n] = bias[n];
-    L->N = N; L->n_real = n_real; L->K = K;
-    if (keep) *keep = packed;
-    int rc = h->upload(packed, &L->w);
-    if (rc) return rc;
-    return h->upload(b, &L->bias);
-}
-
-int make_plain_linear(nunif_swin_unet *h, const TensorMap &m, const std::string &key, int n_real, int K, Linear *L,
-                      bool chained = false, std::vector<f16> *keep = nullptr) {
-    const HostTensor *w, *b;
-    int rc;
-    if ((rc = find(m, key + ".weight", &w)) || (rc = find(m, key + ".bias", &b))) return rc;
-    NUNIF_REQUIRE(w->numel == (int64_t)n_real * K && b->numel == n_real, "%s: unexpected shape", key.c_str());
-    const float *wd = w->data;
-    return make_linear(h, n_real, K, [=](int n, int k) { return wd[(size_t)n * K + k]; }, b->data, L, chained, keep);
-}
-
 // proj | mlp.0 | mlp.3 as one linear stream of 1-KiB fragments in the order proj_mlp_kernel (swin_block_tail.hip) and the block96
 // kernel consume them; returns the number of fragments written
 size_t put_tail_stream(const std::vector<f16> &proj, const std::vector<f16> &h0, const std::vector<f16> &h3, int dim, std::vector<f16> &stream) {
@@ -210,8 +176,7 @@ int make_stage(nunif_swin_unet *h, const TensorMap &m, const std::string &key, i
         const std::string p = key + ".block." + std::to_string(i) + ".";
         Block &bl = (*blocks)[i];
         int rc;
-        std::vector<f16> hq;
-        if ((rc = make_plain_linear(h, m, p + "attn.qkv", 3 * dim, dim, &bl.qkv, false, &hq))) return rc;
+        if ((rc = linear_from(h, m, p + "attn.qkv", 3 * dim, dim, 16, &bl.qkv))) return rc;
         const bool has_norm = m.find(p + "norm1.weight") != m.end();
         bl.fast = heads == 6 && (dim == 96 || dim == 192) && !has_norm;
         if (has_norm) {
@@ -224,9 +189,9 @@ int make_stage(nunif_swin_unet *h, const TensorMap &m, const std::string &key, i
             if ((rc = h->upload(g1, &bl.norm1)) || (rc = h->upload(g2, &bl.norm2))) return rc;
         }
         if (!bl.fast) {
-            if ((rc = make_plain_linear(h, m, p + "attn.proj", dim, dim, &bl.proj)) ||
-                (rc = make_plain_linear(h, m, p + "mlp.0", 2 * dim, dim, &bl.mlp0p)) ||
-                (rc = make_plain_linear(h, m, p + "mlp.3", dim, 2 * dim, &bl.mlp3p)))
+            if ((rc = linear_from(h, m, p + "attn.proj", dim, dim, 16, &bl.proj)) ||
+                (rc = linear_from(h, m, p + "mlp.0", 2 * dim, dim, 16, &bl.mlp0p)) ||
+                (rc = linear_from(h, m, p + "mlp.3", dim, 2 * dim, 16, &bl.mlp3p)))
                 return rc;
         }
         if (bl.fast) {
@@ -250,17 +215,17 @@ int make_stage(nunif_swin_unet *h, const TensorMap &m, const std::string &key, i
             for (int n = 0; n < 3 * dim; ++n) rb[n] = b->data[n] * (n < dim ? qs : 1.0f);
             if ((rc = h->upload(rb, &bl.qkv_rbias))) return rc;
         }
-        std::vector<f16> hp, h0, h3;
+        LinearHost hp, h0, h3;
         if (bl.fast) {
-        if ((rc = make_plain_linear(h, m, p + "attn.proj", dim, dim, &bl.proj, false, &hp))) return rc;
-        if ((rc = make_plain_linear(h, m, p + "mlp.0", 2 * dim, dim, &bl.mlp0, true, &h0))) return rc;   // chained
-        if ((rc = make_plain_linear(h, m, p + "mlp.3", dim, 2 * dim, &bl.mlp3, true, &h3))) return rc;   // chained
+        if ((rc = linear_from(h, m, p + "attn.proj", dim, dim, 16, &bl.proj, false, &hp))) return rc;
+        if ((rc = linear_from(h, m, p + "mlp.0", 2 * dim, dim, 16, &bl.mlp0, true, &h0))) return rc;   // chained
+        if ((rc = linear_from(h, m, p + "mlp.3", dim, 2 * dim, 16, &bl.mlp3, true, &h3))) return rc;   // chained
         }
         if (bl.fast) {
             const int KS = dim / 32, SH = 2 * dim / 32;
             const int nf = proj_mlp_stream_frags(dim);
             std::vector<f16> stream((size_t)(nf + 15) / 16 * 16 * 512, (f16)0.0f);     // whole 16-fragment chunks
-            const size_t fi = put_tail_stream(hp, h0, h3, dim, stream);
+            const size_t fi = put_tail_stream(hp.w, h0.w, h3.w, dim, stream);
             NUNIF_REQUIRE((int)fi == nf, "internal: tail stream has %zu fragments, expected %d", fi, nf);
             if ((rc = h->upload(stream, &bl.tail_stream))) return rc;
             if (dim == 192) {
@@ -271,13 +236,13 @@ int make_stage(nunif_swin_unet *h, const TensorMap &m, const std::string &key, i
                 auto putw = [&](const std::vector<f16> &src, int frag) { copy_frag(src, frag, ws, &wi); };
                 for (int w = 0; w < 4; ++w)
                     for (int nt = 0; nt < 3; ++nt)
-                        for (int ks = 0; ks < KS; ++ks) putw(hp, (3 * w + nt) * KS + ks);
+                        for (int ks = 0; ks < KS; ++ks) putw(hp.w, (3 * w + nt) * KS + ks);
                 for (int w = 0; w < 4; ++w)
                     for (int nt = 0; nt < 6; ++nt)
-                        for (int ks = 0; ks < KS; ++ks) putw(h0, (6 * w + nt) * KS + ks);
+                        for (int ks = 0; ks < KS; ++ks) putw(h0.w, (6 * w + nt) * KS + ks);
                 for (int w = 0; w < 4; ++w)
                     for (int nt = 0; nt < 3; ++nt)
-                        for (int ks = 0; ks < SH; ++ks) putw(h3, (3 * w + nt) * SH + ks);
+                        for (int ks = 0; ks < SH; ++ks) putw(h3.w, (3 * w + nt) * SH + ks);
                 NUNIF_REQUIRE((int)wi == proj_mlp_ws_stream_frags(), "internal: ws tail stream has %zu fragments", wi);
                 if ((rc = h->upload(ws, &bl.tail_ws))) return rc;
             }
@@ -293,7 +258,7 @@ int make_stage(nunif_swin_unet *h, const TensorMap &m, const std::string &key, i
             const float *pd = pw->data;
             std::vector<f16> hpc = pack_nt_ks(dim, dim, dim, [=](int n, int k) { return pd[(size_t)n * dim + k]; }, true);
             std::vector<f16> stream((size_t)swin_block96_tail_frags() * 512, (f16)0.0f);
-            const size_t fi = put_tail_stream(hpc, h0, h3, dim, stream);
+            const size_t fi = put_tail_stream(hpc, h0.w, h3.w, dim, stream);
             NUNIF_REQUIRE((int)fi == swin_block96_tail_frags(), "internal: block96 stream has %zu fragments", fi);
             if ((rc = h->upload(stream, &bl.b96_tail))) return rc;
             // R[h][i] = log2(e) * table[120 - i][h]: the keys of a 2 x 2 block are then at +0, +1, +11, +12 from the
@@ -337,22 +302,18 @@ int make_stage(nunif_swin_unet *h, const TensorMap &m, const std::string &key, i
     return NUNIF_HIP_OK;
 }
 
-int run_gemm(const Linear &L, const f16 *a, int B, int Hi, int Wi, int Cin, int Ho, int Wo, int stride, int oy,
+int run_gemm(const PackedLinear &L, const f16 *a, int B, int Hi, int Wi, int Cin, int Ho, int Wo, int stride, int oy,
              int ox, int kw, int mode, int act, float slope, const f16 *res, void *out, int ldo, int ps,
              hipStream_t s, const char *tag, int rev = 0) {
-    GemmArgs g;
-    g.a = a; g.B = B; g.Hi = Hi; g.Wi = Wi; g.Cin = Cin;
-    g.Ho = Ho; g.Wo = Wo; g.stride = stride; g.oy = oy; g.ox = ox; g.kw = kw;
-    g.K = L.K; g.w = L.w; g.bias = L.bias; g.N = L.N;
-    g.mode = mode; g.act = act; g.slope = slope; g.res = res; g.out = out; g.ldo = ldo;
-    g.n_real = L.n_real; g.ps = ps; g.oshift = 0; g.OH = 0; g.OW = 0; g.no_clamp = 0; g.lda = 0; g.nt_chunk = 0; g.rev = rev;
+    GemmArgs g = gemm_map_args(L, a, B, Hi, Wi, Cin, Ho, Wo, out, stride, kw, oy, ox);
+    g.mode = mode; g.act = act; g.slope = slope; g.res = res; g.ldo = ldo; g.ps = ps; g.rev = rev;
     return launch_gemm(g, s, tag);
 }
 
 // x = PatchUp(a) + skip, in place over the skip map (swin_unet.py:65-82,189-196): the resident-weight kernel when it takes the
 // shape (every launch of that shape, whatever the batch: results must not depend on the tile minibatch), else the generic GEMM
 // `pl` (frame renders): only the listed input tokens; a launch that cannot take the list is an error, never a whole-tile launch
-int run_patchup(const Linear &L, const f16 *a, int B, int H, int W, int Cq, f16 *skip, hipStream_t s, const char *tag, int rev,
+int run_patchup(const PackedLinear &L, const f16 *a, int B, int H, int W, int Cq, f16 *skip, hipStream_t s, const char *tag, int rev,
                 const ProducerList *pl = nullptr) {
     PatchUpArgs p = {a, L.w, L.bias, skip, skip, B, H, W, Cq, rev};
     if (pl && pl->list) { p.list = pl->list; p.n_list = pl->n; }
@@ -364,7 +325,7 @@ int run_patchup(const Linear &L, const f16 *a, int B, int H, int W, int Cq, f16 
 // PatchDown pass without a residual (swin_unet.py:45-62): a [B, 2 Ho, 2 Wo, Cin] -> out [B, Ho, Wo, 192], K = 384 = the taps of
 // input row(s) 2 y + oy ..; the K-outer prefetching kernel when it takes the shape (every launch of that shape), else the generic GEMM
 // acc: out += the pass (down2's second tap row).  `pl` as run_patchup's, output tokens.
-int run_patchdown(const Linear &L, const f16 *a, int B, int Ho, int Wo, int Cin, int oy, f16 *out, hipStream_t s, const char *tag,
+int run_patchdown(const PackedLinear &L, const f16 *a, int B, int Ho, int Wo, int Cin, int oy, f16 *out, hipStream_t s, const char *tag,
                   int rev, const ProducerList *pl = nullptr, int acc = 0) {
     PatchDownArgs p;
     p.a = a; p.w = L.w; p.bias = L.bias; p.out = out; p.B = B; p.Ho = Ho; p.Wo = Wo; p.Cin = Cin; p.oy = oy; p.rev = rev; p.acc = acc;
@@ -375,7 +336,7 @@ int run_patchdown(const Linear &L, const f16 *a, int B, int Ho, int Wo, int Cin,
     return run_gemm(L, a, B, 2 * Ho, 2 * Wo, Cin, Ho, Wo, 2, oy, 0, 2, 0, 0, 0.f, nullptr, out, L.n_real, 1, s, tag, rev);
 }
 
-int run_linear(const Linear &L, const f16 *a, int B, int H, int W, int act, const f16 *res, f16 *out,
+int run_linear(const PackedLinear &L, const f16 *a, int B, int H, int W, int act, const f16 *res, f16 *out,
                hipStream_t s, const char *tag, int rev = 0) {
     return run_gemm(L, a, B, H, W, L.K, H, W, 1, 0, 0, 1, 0, act, 0.f, res, out, L.n_real, 1, s, tag, rev);
 }
@@ -719,7 +680,7 @@ extern "C" int nunif_hip_swin_unet_create(const nunif_tensor_desc *tensors, int3
         const int C = (int)w2->shape[0];
         const int C1 = (int)w0->shape[0];
         if (C % 96 != 0 || C1 * 2 != C) { set_error("base_dim %d unsupported", C); rc = NUNIF_HIP_EUNSUPPORTED; break; }
-        h->C = C; h->heads = C / 16; h->C1 = C1; h->C1P = (C1 + 31) / 32 * 32;
+        h->C = C; h->heads = C / 16; h->C1 = C1; h->C1P = pad_to(C1, 32);
         h->has_proj2 = scale_factor >= 4;
         h->top_dim = h->has_proj2 ? 2 * C : C;
         {
@@ -729,15 +690,15 @@ extern "C" int nunif_hip_swin_unet_create(const nunif_tensor_desc *tensors, int3
         {   // conv2 [C][C1][3][3] -> W[n][k = (dy*3+dx)*C1P + ci], zero for the padded input channels
             const float *wd = w2->data;
             const int C1P = h->C1P;
-            rc = make_linear(h, C, 9 * C1P, [=](int n, int k) {
+            rc = make_linear(h, C, 16, 9 * C1P, [=](int n, int k) {
                 const int tap = k / C1P, ci = k % C1P;
                 return ci < C1 ? wd[((size_t)n * C1 + ci) * 9 + tap] : 0.0f;
-            }, b2->data, &h->stem2);
+            }, bias_at(b2->data), &h->stem2);
             if (rc) break;
         }
         if (stem_fused_supported(C1, C)) {
             const float *w0d = w0->data, *b0d = b0->data, *wd = w2->data;
-            std::vector<f16> p1 = pack_nt_ks(C1, pad16(C1), 32, [=](int n, int k) {
+            std::vector<f16> p1 = pack_nt_ks(C1, pad_to(C1, 16), 32, [=](int n, int k) {
                 return k < 27 ? w0d[(size_t)n * 27 + k] : (k == 27 ? b0d[n] : 0.0f); });
             const int K2 = 448;
             std::vector<f16> stream = pack_ks_nt(C, C, K2, [=](int n, int k) {
@@ -750,29 +711,27 @@ extern "C" int nunif_hip_swin_unet_create(const nunif_tensor_desc *tensors, int3
         if ((rc = make_stage(h, m, P + "swin3", 2 * C, 6, &h->swin[2]))) break;
         if ((rc = make_stage(h, m, P + "swin4", 2 * C, 2, &h->swin[3]))) break;
         if ((rc = make_stage(h, m, P + "swin5", h->top_dim, 2, &h->swin[4]))) break;
-        auto make_down = [&](const std::string &key, int cin, int cout, Linear *L) -> int {
+        auto make_down = [&](const std::string &key, int cin, int cout, PackedLinear *L) -> int {
             const HostTensor *w, *b;
             int r;
             if ((r = find(m, key + ".conv.weight", &w)) || (r = find(m, key + ".conv.bias", &b))) return r;
             NUNIF_REQUIRE(w->numel == (int64_t)cout * cin * 4, "%s: shape", key.c_str());
             const float *wd = w->data;   // [cout][cin][2][2] -> k = (i*2+j)*cin + ci
-            return make_linear(h, cout, 4 * cin, [=](int n, int k) {
+            return make_linear(h, cout, 16, 4 * cin, [=](int n, int k) {
                 const int tap = k / cin, ci = k % cin;
                 return wd[((size_t)n * cin + ci) * 4 + tap];
-            }, b->data, L);
+            }, bias_at(b->data), L);
         };
-        auto make_up = [&](const std::string &key, int cin, int cq, Linear *L) -> int {
+        auto make_up = [&](const std::string &key, int cin, int cq, PackedLinear *L) -> int {
             const HostTensor *w, *b;
             int r;
             if ((r = find(m, key + ".proj.weight", &w)) || (r = find(m, key + ".proj.bias", &b))) return r;
             NUNIF_REQUIRE(w->numel == (int64_t)4 * cq * cin, "%s: shape", key.c_str());
-            const float *wd = w->data;   // rows c*4 + q  ->  q*cq + c   (pixel_shuffle(2) channel order)
-            std::vector<float> bb(4 * cq);
-            for (int n = 0; n < 4 * cq; ++n) bb[n] = b->data[(n % cq) * 4 + n / cq];
-            return make_linear(h, 4 * cq, cin, [=](int n, int k) {
+            const float *wd = w->data, *bd = b->data;   // rows c*4 + q  ->  q*cq + c   (pixel_shuffle(2) channel order)
+            return make_linear(h, 4 * cq, 16, cin, [=](int n, int k) {
                 const int q = n / cq, c = n % cq;
                 return wd[((size_t)(c * 4 + q)) * cin + k];
-            }, bb.data(), L);
+            }, [=](int n) { return bd[(n % cq) * 4 + n / cq]; }, L);
         };
         if ((rc = make_down(P + "down1", C, 2 * C, &h->down1))) break;
         // the base_dim-96 nets' down2 runs the same way (K = 768, one token tile per wave on gemm_kernel<24,1>)
@@ -786,31 +745,29 @@ extern "C" int nunif_hip_swin_unet_create(const nunif_tensor_desc *tensors, int3
             const int cin = 2 * C, cout = 2 * C;
             if (w->numel != (int64_t)cout * cin * 4) { set_error("down2: shape"); rc = NUNIF_HIP_EINVAL; break; }
             const float *wd = w->data;
-            std::vector<float> zero(cout, 0.0f);
-            if ((rc = make_linear(h, cout, 2 * cin, [=](int n, int k) {
-                    const int dx = k / cin, ci = k % cin; return wd[((size_t)n * cin + ci) * 4 + dx]; }, b->data, &h->down2)) ||
-                (rc = make_linear(h, cout, 2 * cin, [=](int n, int k) {
-                    const int dx = k / cin, ci = k % cin; return wd[((size_t)n * cin + ci) * 4 + 2 + dx]; }, zero.data(), &h->down2b)))
+            if ((rc = make_linear(h, cout, 16, 2 * cin, [=](int n, int k) {
+                    const int dx = k / cin, ci = k % cin; return wd[((size_t)n * cin + ci) * 4 + dx]; }, bias_at(b->data), &h->down2)) ||
+                (rc = make_linear(h, cout, 16, 2 * cin, [=](int n, int k) {
+                    const int dx = k / cin, ci = k % cin; return wd[((size_t)n * cin + ci) * 4 + 2 + dx]; }, bias_at(nullptr), &h->down2b)))
                 break;
             h->down2_split = true;
         }
         if ((rc = make_up(P + "up2", 2 * C, 2 * C, &h->up2))) break;
         if ((rc = make_up(P + "up1", 2 * C, h->top_dim, &h->up1))) break;
-        if (h->has_proj2 && (rc = make_plain_linear(h, m, P + "proj2", 2 * C, C, &h->proj2))) break;
+        if (h->has_proj2 && (rc = linear_from(h, m, P + "proj2", 2 * C, C, 16, &h->proj2))) break;
         if (scale_factor == 8) {
             // ToImage of the 8x net (swin_unet.py:96-101): Linear -> LeakyReLU(0.2) -> Linear, both 192 wide
-            if ((rc = make_plain_linear(h, m, P + "to_image.proj.0", 192, h->top_dim, &h->to_image_pre)) ||
-                (rc = make_plain_linear(h, m, P + "to_image.proj.2", 192, 192, &h->to_image)))
+            if ((rc = linear_from(h, m, P + "to_image.proj.0", 192, h->top_dim, 16, &h->to_image_pre)) ||
+                (rc = linear_from(h, m, P + "to_image.proj.2", 192, 192, 16, &h->to_image)))
                 break;
-        } else if ((rc = make_plain_linear(h, m, P + "to_image.proj", 3 * scale_factor * scale_factor, h->top_dim,
-                                           &h->to_image)))
+        } else if ((rc = linear_from(h, m, P + "to_image.proj", 3 * scale_factor * scale_factor, h->top_dim, 16, &h->to_image)))
             break;
         if (h->top_dim == 96 && 3 * scale_factor * scale_factor <= 16) {
             const HostTensor *tw;
             if ((rc = find(m, P + "to_image.proj.weight", &tw))) break;
             const float *wd = tw->data;
             const int nr = 3 * scale_factor * scale_factor, K = h->top_dim;
-            std::vector<f16> ch = pack_nt_ks(nr, pad16(nr), K, [=](int n, int k) { return wd[(size_t)n * K + k]; }, true);
+            std::vector<f16> ch = pack_nt_ks(nr, pad_to(nr, 16), K, [=](int n, int k) { return wd[(size_t)n * K + k]; }, true);
             if ((rc = h->upload(ch, &h->to_image_chained))) break;
         }
     } while (0);

@@ -19,8 +19,7 @@
 #include <string>
 #include <vector>
 
-#include "host_weights.h"
-#include "swin_kernels.h"
+#include "packed_layers.h"
 #include "wa_block_host.h"
 
 namespace nunif {
@@ -273,12 +272,9 @@ using namespace nunif;
 // =====================================================================================================================
 namespace {
 
-struct Lin { f16 *w = nullptr; float *b = nullptr; int N = 0, n_real = 0, K = 0; };       // gemm_kernel packing [nt][ks]
-struct Conv3 { f16 *w = nullptr; float *b = nullptr; int Cin = 0, N = 0; };                 // conv_kernel stream [ks][nt]
-
 struct WacBlock {
-    Lin qkv, proj, w1, w2lin;     // w2lin: the plain-MLP form of the LAST decoder block (1x1)
-    Conv3 w2;                     // GLUConvMLP: 3x3 on mid / 2 channels
+    PackedLinear qkv, proj, w1, w2lin;     // w2lin: the plain-MLP form of the LAST decoder block (1x1)
+    PackedConv w2;                  // GLUConvMLP: 3x3 on mid / 2 channels
     float *norm = nullptr, *btab = nullptr, *bqkv = nullptr;
     int C = 0, heads = 0, ws = 8, shift = 0, mid = 0, glu = 1;
 };
@@ -289,65 +285,36 @@ struct nunif_swin_unet_v2 : DeviceOwner {
     int scale = 2, C = 96, C2 = 192;
     float *ir1_w = nullptr, *ir1_b = nullptr, *ir2_w = nullptr, *ir2_b = nullptr, *res_w = nullptr, *scale_bias = nullptr;
     WacBlock ir_blk[2];
-    Conv3 patch;
+    PackedConv patch;
     std::vector<WacBlock> wac1, wac2, wac3;
-    Lin down1, up1, to_image;
+    PackedLinear down1, up1, to_image;
     DeviceBuf ir, irf, irf2, f1, f1b, skip, f2, f2b, tmpA, tmpB, qkv, rimg;
 };
 
 namespace {
 
-// rows n < n_real of a [n_real][K_real] matrix (wt), zero beyond; K padded to a multiple of 32
-template <typename F, typename G>
-int make_lin(nunif_swin_unet_v2 *h, int n_real, int K_real, F wt, G bias, Lin *L) {
-    const int N = (n_real + 15) / 16 * 16, K = (K_real + 31) / 32 * 32;
-    std::vector<f16> packed = pack_nt_ks(n_real, N, K, [&](int n, int k) { return k < K_real ? wt(n, k) : 0.f; });
-    std::vector<float> b(N, 0.f);
-    for (int n = 0; n < n_real; ++n) b[n] = bias(n);
-    L->N = N; L->n_real = n_real; L->K = K;
-    int rc = h->upload(packed, &L->w);
-    return rc ? rc : h->upload(b, &L->b);
-}
-
-// 3x3 conv [N][Cin][3][3] -> conv_kernel stream, k = tap * Cin + ci
-int make_conv3(nunif_swin_unet_v2 *h, const HostTensor *w, const HostTensor *b, int N, int Cin, Conv3 *cv) {
-    NUNIF_REQUIRE(w->numel == (int64_t)N * Cin * 9 && b->numel == N && Cin % 32 == 0 && N % 16 == 0, "3x3 conv shape");
-    const float *wd = w->data;
-    std::vector<f16> stream = pack_ks_nt(N, N, 9 * Cin, [=](int n, int k) {
-        const int tap = k / Cin, ci = k % Cin;
-        return wd[((size_t)n * Cin + ci) * 9 + tap]; });
-    std::vector<float> bb(b->data, b->data + N);
-    cv->Cin = Cin; cv->N = N;
-    int rc = h->upload(stream, &cv->w);
-    return rc ? rc : h->upload(bb, &cv->b);
-}
-
 int make_wac(nunif_swin_unet_v2 *h, const TensorMap &m, const std::string &p, int C, int heads, int ws, int shift, WacBlock *bk) {
-    const HostTensor *wqkv, *bqkv, *wp, *bp, *nw, *w1, *b1, *w2, *b2, *tw0, *tb0, *tw2, *tb2;
+    const HostTensor *wqkv, *bqkv, *nw, *w1, *w2, *tw0, *tb0, *tw2, *tb2;
     int rc;
     if ((rc = find(m, p + "mha.mha.qkv_proj.weight", &wqkv)) || (rc = find(m, p + "mha.mha.qkv_proj.bias", &bqkv)) ||
-        (rc = find(m, p + "mha.mha.head_proj.weight", &wp)) || (rc = find(m, p + "mha.mha.head_proj.bias", &bp)) ||
         (rc = find(m, p + "norm.weight", &nw)) || (rc = find(m, p + "conv_mlp.w1.weight", &w1)) ||
-        (rc = find(m, p + "conv_mlp.w1.bias", &b1)) || (rc = find(m, p + "conv_mlp.w2.weight", &w2)) ||
-        (rc = find(m, p + "conv_mlp.w2.bias", &b2)) || (rc = find(m, p + "relative_bias.to_bias.0.weight", &tw0)) ||
+        (rc = find(m, p + "conv_mlp.w2.weight", &w2)) || (rc = find(m, p + "relative_bias.to_bias.0.weight", &tw0)) ||
         (rc = find(m, p + "relative_bias.to_bias.0.bias", &tb0)) || (rc = find(m, p + "relative_bias.to_bias.2.weight", &tw2)) ||
         (rc = find(m, p + "relative_bias.to_bias.2.bias", &tb2)))
         return rc;
-    NUNIF_REQUIRE(wqkv->numel == (int64_t)3 * C * C && wp->numel == (int64_t)C * C && nw->numel == C && C == heads * 32,
+    NUNIF_REQUIRE(wqkv->numel == (int64_t)3 * C * C && nw->numel == C && C == heads * 32,
                   "%s: expected %d channels in heads of 32", p.c_str(), C);
     bk->C = C; bk->heads = heads; bk->ws = ws; bk->shift = shift;
     const float qs = (1.0f / sqrtf(32.0f)) * 1.4426950408889634f;       // head_dim^-0.5 * log2(e), folded into q
     {
         const float *wd = wqkv->data, *bd = bqkv->data;
-        if ((rc = make_lin(h, 3 * C, C, [=](int n, int k) { return wd[(size_t)n * C + k] * (n < C ? qs : 1.f); },
-                           [=](int n) { return bd[n] * (n < C ? qs : 1.f); }, &bk->qkv)))
+        if ((rc = make_linear(h, 3 * C, 16, C, [=](int n, int k) { return wd[(size_t)n * C + k] * (n < C ? qs : 1.f); },
+                              [=](int n) { return bd[n] * (n < C ? qs : 1.f); }, &bk->qkv)))
             return rc;
         std::vector<float> bq(3 * C);
         for (int n = 0; n < 3 * C; ++n) bq[n] = bd[n] * (n < C ? qs : 1.f);
         if ((rc = h->upload(bq, &bk->bqkv))) return rc;
-        const float *pd = wp->data, *pb = bp->data;
-        if ((rc = make_lin(h, C, C, [=](int n, int k) { return pd[(size_t)n * C + k]; }, [=](int n) { return pb[n]; }, &bk->proj)))
-            return rc;
+        if ((rc = linear_from(h, m, p + "mha.mha.head_proj", C, C, 16, &bk->proj))) return rc;
         std::vector<float> g(nw->data, nw->data + C);
         if ((rc = h->upload(g, &bk->norm))) return rc;
     }
@@ -358,31 +325,20 @@ int make_wac(nunif_swin_unet_v2 *h, const TensorMap &m, const std::string &p, in
     const int mid = (int)w1->shape[0];
     bk->mid = mid;
     bk->glu = w2->shape.size() == 4 && w2->shape[2] == 3;
-    {
-        const float *wd = w1->data, *bd = b1->data;
-        NUNIF_REQUIRE(w1->numel == (int64_t)mid * C && mid % 32 == 0, "%s: conv_mlp.w1 shape", p.c_str());
-        if ((rc = make_lin(h, mid, C, [=](int n, int k) { return wd[(size_t)n * C + k]; }, [=](int n) { return bd[n]; }, &bk->w1)))
-            return rc;
-    }
+    NUNIF_REQUIRE(mid % 32 == 0, "%s: conv_mlp.w1 shape", p.c_str());
+    if ((rc = linear_from(h, m, p + "conv_mlp.w1", mid, C, 16, &bk->w1))) return rc;
     if (bk->glu) {
         NUNIF_REQUIRE(mid % 64 == 0, "%s: GLU needs mid / 2 in multiples of 32", p.c_str());
-        if ((rc = make_conv3(h, w2, b2, C, mid / 2, &bk->w2))) return rc;
-    } else {
-        const float *wd = w2->data, *bd = b2->data;
-        NUNIF_REQUIRE(w2->numel == (int64_t)C * mid, "%s: conv_mlp.w2 (MLP) shape", p.c_str());
-        if ((rc = make_lin(h, C, mid, [=](int n, int k) { return wd[(size_t)n * mid + k]; }, [=](int n) { return bd[n]; }, &bk->w2lin)))
-            return rc;
+        return conv_from(h, m, p + "conv_mlp.w2", C, 16, mid / 2, mid / 2, 3, &bk->w2);
     }
-    return NUNIF_HIP_OK;
+    return linear_from(h, m, p + "conv_mlp.w2", C, mid, 16, &bk->w2lin);
 }
 
-int run_lin(const Lin &L, const f16 *a, int B, int Hi, int Wi, int Cin, int Ho, int Wo, int stride, int kw, int mode, int act,
-            float slope, const f16 *res, void *out, int ldo, hipStream_t s, const char *tag) {
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.a = a; g.B = B; g.Hi = Hi; g.Wi = Wi; g.Cin = Cin; g.Ho = Ho; g.Wo = Wo; g.stride = stride; g.kw = kw;
-    g.K = L.K; g.w = L.w; g.bias = L.b; g.N = L.N; g.mode = mode; g.act = act; g.slope = slope; g.res = res; g.out = out;
-    g.ldo = ldo; g.n_real = L.n_real; g.ps = 1;
+// a Linear over the NHWC map [B,S,S,K]; act 2: LeakyReLU(slope); res may alias out
+int run_lin(const PackedLinear &L, const f16 *a, int B, int S, int act, float slope, const f16 *res, f16 *out, hipStream_t s,
+            const char *tag) {
+    GemmArgs g = gemm_map_args(L, a, B, S, S, L.K, S, S, out);
+    g.act = act; g.slope = slope; g.res = res;
     return launch_gemm(g, s, tag);
 }
 
@@ -410,7 +366,7 @@ int run_wac(nunif_swin_unet_v2 *h, const WacBlock &bk, f16 **px, f16 **pother, i
     int rc;
     // x = x + head_proj(window_mha(qkv_proj(layer_norm(x))))          (WACBlock.forward :95-96)
     if ((rc = launch_layernorm_nobias(x, tmpA, bk.norm, M, C, s))) return rc;
-    if ((rc = run_lin(bk.qkv, tmpA, B, S, S, C, S, S, 1, 1, 0, 0, 0.f, nullptr, qkv, 3 * C, s, "v2_qkv"))) return rc;
+    if ((rc = run_lin(bk.qkv, tmpA, B, S, 0, 0.f, nullptr, qkv, s, "v2_qkv"))) return rc;
     {
         V2AttnArgs a;
         a.qkv = qkv; a.att = tmpA; a.btab = bk.btab; a.bqkv = bk.bqkv; a.B = B; a.H = S; a.W = S; a.C = C; a.heads = bk.heads;
@@ -421,23 +377,21 @@ int run_wac(nunif_swin_unet_v2 *h, const WacBlock &bk, f16 **px, f16 **pother, i
             return rc;
         }
     }
-    if ((rc = run_lin(bk.proj, tmpA, B, S, S, C, S, S, 1, 1, 0, 0, 0.f, x, x, C, s, "v2_proj"))) return rc;
+    if ((rc = run_lin(bk.proj, tmpA, B, S, 0, 0.f, x, x, s, "v2_proj"))) return rc;
     if (bk.glu) {
         // x = x + leaky_relu(conv3x3(replicate_pad(glu(w1 x))), 0.2)      (GLUConvMLP :27-35)
-        if ((rc = run_lin(bk.w1, x, B, S, S, C, S, S, 1, 1, 0, 0, 0.f, nullptr, tmpB, bk.mid, s, "v2_mlp_w1"))) return rc;
+        if ((rc = run_lin(bk.w1, x, B, S, 0, 0.f, nullptr, tmpB, s, "v2_mlp_w1"))) return rc;
         const int m2 = bk.mid / 2;
         v2_glu_kernel<<<(unsigned)((M * (m2 / 8) + 255) / 256), 256, 0, s>>>(tmpB, tmpA, M, m2);
         NUNIF_LAUNCH_CHECK();
-        ConvArgs c;
-        memset(&c, 0, sizeof(c));
-        c.a = tmpA; c.B = B; c.Hi = S; c.Wi = S; c.Cin = m2; c.Ho = S; c.Wo = S; c.stride = 1; c.kh = 3; c.kw = 3;
-        c.wstream = bk.w2.w; c.bias = bk.w2.b; c.N = C; c.n_real = C; c.act = 2; c.slope = 0.2f; c.out = other; c.rpad = 1; c.res = x;
+        ConvArgs c = conv_args(bk.w2, tmpA, B, S, S, other, 1, 0, 1);
+        c.act = 2; c.slope = 0.2f; c.res = x;
         if ((rc = launch_conv(c, s))) return rc;
         *px = other; *pother = x;
     } else {
         // x = x + w2(leaky_relu(w1 x, 0.1))                                (MLP :62-68)
-        if ((rc = run_lin(bk.w1, x, B, S, S, C, S, S, 1, 1, 0, 2, 0.1f, nullptr, tmpB, bk.mid, s, "v2_mlp_w1"))) return rc;
-        if ((rc = run_lin(bk.w2lin, tmpB, B, S, S, bk.mid, S, S, 1, 1, 0, 0, 0.f, x, x, C, s, "v2_mlp_w2"))) return rc;
+        if ((rc = run_lin(bk.w1, x, B, S, 2, 0.1f, nullptr, tmpB, s, "v2_mlp_w1"))) return rc;
+        if ((rc = run_lin(bk.w2lin, tmpB, B, S, 0, 0.f, x, x, s, "v2_mlp_w2"))) return rc;
     }
     return NUNIF_HIP_OK;
 }
@@ -471,25 +425,25 @@ extern "C" int nunif_hip_swin_unet_v2_create(const nunif_tensor_desc *tensors, i
         if ((rc = make_wac(h, m, P + "ir.path2.2.", 64, 2, 8, 1, &h->ir_blk[0])) ||
             (rc = make_wac(h, m, P + "ir.path2.3.", 64, 2, 8, 0, &h->ir_blk[1])))
             break;
-        if ((rc = find(m, P + "patch.weight", &w)) || (rc = find(m, P + "patch.bias", &b))) break;
+        if ((rc = find(m, P + "patch.weight", &w))) break;
         const int C = (int)w->shape[0];
-        if ((rc = make_conv3(h, w, b, C, 32, &h->patch))) break;
+        if ((rc = conv_from(h, m, P + "patch", C, 16, 32, 32, 3, &h->patch))) break;
         if ((rc = find(m, P + "down1.conv.weight", &w)) || (rc = find(m, P + "down1.conv.bias", &b))) break;
         const int C2 = (int)w->shape[0];
         h->C = C; h->C2 = C2;
         if (C % 32 || C2 % 32 || (4 * C) % C2) { set_error("swin_unet_v2: base_dim %d / %d unsupported", C, C2); rc = NUNIF_HIP_EUNSUPPORTED; break; }
         {   // down1: 2x2 stride-2 conv as a gather GEMM, k = (dy*2 + dx) * C + ci
             const float *wd = w->data, *bd = b->data;
-            if ((rc = make_lin(h, C2, 4 * C, [=](int n, int k) { const int tap = k / C, ci = k % C; return wd[((size_t)n * C + ci) * 4 + tap]; },
-                               [=](int n) { return bd[n]; }, &h->down1)))
+            if ((rc = make_linear(h, C2, 16, 4 * C, [=](int n, int k) { const int tap = k / C, ci = k % C; return wd[((size_t)n * C + ci) * 4 + tap]; },
+                                  bias_at(bd), &h->down1)))
                 break;
         }
         if ((rc = find(m, P + "up1.proj.weight", &w)) || (rc = find(m, P + "up1.proj.bias", &b))) break;
         if (w->numel != (int64_t)4 * C * C2) { set_error("swin_unet_v2: up1.proj shape"); rc = NUNIF_HIP_EINVAL; break; }
         {   // up1: gemm mode 1 writes column n' = q * C + c to sub-pixel q: torch's pixel_shuffle takes channel c * 4 + q
             const float *wd = w->data, *bd = b->data;
-            if ((rc = make_lin(h, 4 * C, C2, [=](int n, int k) { const int q = n / C, c = n % C; return wd[(size_t)(c * 4 + q) * C2 + k]; },
-                               [=](int n) { const int q = n / C, c = n % C; return bd[c * 4 + q]; }, &h->up1)))
+            if ((rc = make_linear(h, 4 * C, 16, C2, [=](int n, int k) { const int q = n / C, c = n % C; return wd[(size_t)(c * 4 + q) * C2 + k]; },
+                                  [=](int n) { const int q = n / C, c = n % C; return bd[c * 4 + q]; }, &h->up1)))
                 break;
         }
         auto count_blocks = [&](const std::string &key) {
@@ -512,14 +466,8 @@ extern "C" int nunif_hip_swin_unet_v2_create(const nunif_tensor_desc *tensors, i
         for (int i = 0; i < n3 && !rc; ++i)
             rc = make_wac(h, m, P + "wac3.blocks." + std::to_string(i) + ".", C, heads, 8, shift_of(n3, i), &h->wac3[i]);
         if (rc) break;
-        if ((rc = find(m, P + "to_residual_image.proj.weight", &w)) || (rc = find(m, P + "to_residual_image.proj.bias", &b))) break;
         const int s2 = scale_factor * scale_factor;
-        if (w->numel != (int64_t)3 * s2 * C) { set_error("swin_unet_v2: to_residual_image shape"); rc = NUNIF_HIP_EINVAL; break; }
-        {
-            const float *wd = w->data, *bd = b->data;
-            if ((rc = make_lin(h, 3 * s2, C, [=](int n, int k) { return wd[(size_t)n * C + k]; }, [=](int n) { return bd[n]; }, &h->to_image)))
-                break;
-        }
+        if ((rc = linear_from(h, m, P + "to_residual_image.proj", 3 * s2, C, 16, &h->to_image))) break;
         if ((rc = find(m, P + "to_image.resampling.weight", &w)) || (rc = find(m, P + "to_image.scale_bias", &b))) break;
         if (w->numel != (int64_t)3 * s2 * 27 || b->numel != 1) { set_error("swin_unet_v2: to_image shape"); rc = NUNIF_HIP_EINVAL; break; }
         {
@@ -575,10 +523,8 @@ extern "C" int nunif_hip_swin_unet_v2_forward(nunif_swin_unet_v2 *h, const float
     // ---- patch: 3x3 VALID 32 -> C, crop 7, LeakyReLU(0.2) (:339-341): conv rows / cols [7, 7 + S) of the (T - 2)^2 result ------
     f16 *f1 = (f16 *)h->f1.p, *f1b = (f16 *)h->f1b.p;
     {
-        ConvArgs c;
-        memset(&c, 0, sizeof(c));
-        c.a = ir + ((long)7 * T + 7) * 32; c.B = B; c.Hi = T; c.Wi = T; c.Cin = 32; c.Ho = S; c.Wo = S; c.stride = 1; c.kh = 3; c.kw = 3;
-        c.wstream = h->patch.w; c.bias = h->patch.b; c.N = C; c.n_real = C; c.act = 2; c.slope = 0.2f; c.out = f1;
+        ConvArgs c = conv_args(h->patch, ir + ((long)7 * T + 7) * 32, B, T, T, f1);
+        c.Ho = S; c.Wo = S; c.act = 2; c.slope = 0.2f;
         if ((rc = launch_conv(c, s))) return rc;
     }
     for (auto &bk : h->wac1)
@@ -590,13 +536,21 @@ extern "C" int nunif_hip_swin_unet_v2_forward(nunif_swin_unet_v2 *h, const float
     f16 *f2 = (f16 *)h->f2.p, *f2b = (f16 *)h->f2b.p;
     v2_down_shortcut_kernel<<<(unsigned)((M2 * C2 + 255) / 256), 256, 0, s>>>(skip, f2, B, S, S, C, C2);
     NUNIF_LAUNCH_CHECK();
-    if ((rc = run_lin(h->down1, skip, B, S, S, C, S / 2, S / 2, 2, 2, 0, 2, 0.2f, f2, f2, C2, s, "v2_down1"))) return rc;
+    {
+        GemmArgs g = gemm_map_args(h->down1, skip, B, S, S, C, S / 2, S / 2, f2, 2, 2);
+        g.act = 2; g.slope = 0.2f; g.res = f2;
+        if ((rc = launch_gemm(g, s, "v2_down1"))) return rc;
+    }
     for (auto &bk : h->wac2)
         if ((rc = run_wac(h, bk, &f2, &f2b, B, S / 2, s))) return rc;
     // ---- up1 (:186-192) + skip (:348): shortcut + skip first, then proj + LeakyReLU(0.2) + pixel shuffle accumulates onto it -------
     v2_up_shortcut_kernel<<<(unsigned)((M1 * C + 255) / 256), 256, 0, s>>>(f2, skip, dec, B, S, S, C, C2);
     NUNIF_LAUNCH_CHECK();
-    if ((rc = run_lin(h->up1, f2, B, S / 2, S / 2, C2, S / 2, S / 2, 1, 1, 1, 2, 0.2f, dec, dec, C, s, "v2_up1"))) return rc;
+    {
+        GemmArgs g = gemm_map_args(h->up1, f2, B, S / 2, S / 2, C2, S / 2, S / 2, dec);
+        g.mode = 1; g.act = 2; g.slope = 0.2f; g.res = dec; g.ldo = C;
+        if ((rc = launch_gemm(g, s, "v2_up1"))) return rc;
+    }
     f16 *other = f1b;
     if (other == dec || other == skip) other = (f16 *)h->skip.p == dec || (f16 *)h->skip.p == skip ? (f16 *)h->f1.p : (f16 *)h->skip.p;
     for (auto &bk : h->wac3)
@@ -604,11 +558,8 @@ extern "C" int nunif_hip_swin_unet_v2_forward(nunif_swin_unet_v2 *h, const float
     // ---- to_residual_image (:199-213): 1x1 conv, pixel shuffle, crop `scale`; then the source residual + clamp --------------------
     const int O = S * sc - 2 * sc;
     {
-        GemmArgs g;
-        memset(&g, 0, sizeof(g));
-        g.a = dec; g.B = B; g.Hi = S; g.Wi = S; g.Cin = C; g.Ho = S; g.Wo = S; g.stride = 1; g.kw = 1;
-        g.K = h->to_image.K; g.w = h->to_image.w; g.bias = h->to_image.b; g.N = h->to_image.N; g.mode = 2; g.out = h->rimg.p;
-        g.n_real = h->to_image.n_real; g.ps = sc; g.oshift = -sc; g.OH = O; g.OW = O; g.no_clamp = 1;
+        GemmArgs g = gemm_map_args(h->to_image, dec, B, S, S, C, S, S, h->rimg.p);
+        g.mode = 2; g.ldo = 0; g.ps = sc; g.oshift = -sc; g.OH = O; g.OW = O; g.no_clamp = 1;
         if ((rc = launch_gemm(g, s, "v2_to_image"))) return rc;
     }
     const long n_out = (long)B * 3 * O * O;

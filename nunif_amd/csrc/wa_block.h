@@ -4,14 +4,14 @@
 #pragma once
 #include <string>
 
-#include "host_weights.h"
+#include "packed_layers.h"
 
 namespace nunif {
 
 struct WaBlock {
     f16 *wfrag = nullptr; float *bqkv = nullptr, *bproj = nullptr, *btab = nullptr;
-    f16 *w1 = nullptr; float *b1 = nullptr;          // conv_mlp[0] 1x1, gemm_kernel packing [nt][ks]
-    f16 *w3 = nullptr; float *b3 = nullptr;          // conv_mlp[3] 3x3, conv_kernel stream [ks][nt]
+    PackedLinear mlp1;                               // conv_mlp[0] 1x1
+    PackedConv mlp3;                                 // conv_mlp[3] 3x3
     int window = 4;
 };
 

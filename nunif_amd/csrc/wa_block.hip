@@ -265,10 +265,12 @@ int make_wa_block(DeviceOwner *h, const TensorMap &m, const std::string &p, int 
     if ((rc = wa_block_pack(m, p, window, C, hd, window == 8 ? 64 : 16, &b))) return rc;
     bk->window = window;
     if ((rc = h->upload(b.wfrag, &bk->wfrag)) || (rc = h->upload(b.bqkv, &bk->bqkv)) || (rc = h->upload(b.bproj, &bk->bproj)) ||
-        (rc = h->upload(b.btab, &bk->btab)) || (rc = h->upload(b.w1, &bk->w1)) || (rc = h->upload(b.b1, &bk->b1)) ||
-        (rc = h->upload(b.w3, &bk->w3)))
+        (rc = h->upload(b.btab, &bk->btab)) || (rc = h->upload(b.w1, &bk->mlp1.w)) || (rc = h->upload(b.b1, &bk->mlp1.bias)) ||
+        (rc = h->upload(b.w3, &bk->mlp3.stream)))
         return rc;
-    return h->upload(b.b3, &bk->b3);
+    bk->mlp1.N = bk->mlp1.n_real = bk->mlp1.K = C;
+    bk->mlp3.N = bk->mlp3.n_real = bk->mlp3.Cin = C;
+    return h->upload(b.b3, &bk->mlp3.bias);
 }
 
 int run_wa_blocks(WaMaps *h, const WaBlock *blk, int n, const int *sy, const int *sx, int C, int B, int H, int W, int act, float slope,
@@ -284,21 +286,13 @@ int run_wa_blocks(WaMaps *h, const WaBlock *blk, int n, const int *sy, const int
             a.B = B; a.H = H; a.W = W; a.sy = sy[bi]; a.sx = sx[bi];
             if ((rc = launch_wmha(a, bk.window, C, s))) return rc;
         }
-        {   // conv_mlp[0..1]: 1x1 + GELU(erf)
-            GemmArgs g;
-            memset(&g, 0, sizeof(g));
-            g.a = cur; g.B = B; g.Hi = H; g.Wi = W; g.Cin = C; g.Ho = H; g.Wo = W; g.stride = 1; g.kw = 1;
-            g.K = C; g.w = bk.w1; g.bias = bk.b1; g.N = C; g.mode = 0; g.act = 1; g.out = t1; g.ldo = C; g.n_real = C; g.ps = 1;
-            if ((rc = launch_gemm(g, s, tag))) return rc;
-        }
-        {   // conv_mlp[2..4]: ReplicationPad2d(1) + 3x3 + the net's activation, then the block's residual
-            ConvArgs c;
-            memset(&c, 0, sizeof(c));
-            c.a = t1; c.B = B; c.Hi = H; c.Wi = W; c.Cin = C; c.Ho = H; c.Wo = W; c.stride = 1; c.kh = 3; c.kw = 3;
-            c.wstream = bk.w3; c.bias = bk.b3; c.N = C; c.n_real = C; c.act = act; c.slope = slope; c.out = other;
-            c.rpad = 1; c.res = cur;
-            if ((rc = launch_conv(c, s))) return rc;
-        }
+        GemmArgs g = gemm_map_args(bk.mlp1, cur, B, H, W, C, H, W, t1);      // conv_mlp[0..1]: 1x1 + GELU(erf)
+        g.act = 1;
+        if ((rc = launch_gemm(g, s, tag))) return rc;
+        // conv_mlp[2..4]: ReplicationPad2d(1) + 3x3 + the net's activation, then the block's residual
+        ConvArgs c = conv_args(bk.mlp3, t1, B, H, W, other, 1, 0, 1);
+        c.act = act; c.slope = slope; c.res = cur;
+        if ((rc = launch_conv(c, s))) return rc;
         std::swap(cur, other);
     }
     *out = cur;

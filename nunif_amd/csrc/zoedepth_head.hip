@@ -24,8 +24,7 @@
 #include <string>
 #include <vector>
 
-#include "host_weights.h"
-#include "swin_kernels.h"
+#include "packed_layers.h"
 
 namespace nunif {
 
@@ -216,8 +215,6 @@ __global__ void __launch_bounds__(256) zoe_prep_kernel(const float *__restrict__
 using namespace nunif;
 
 namespace {
-struct ZLin { f16 *w = nullptr; float *b = nullptr; int N = 0, K = 0; };
-
 // the steps of reflection_pad2d_loop along one axis; false when more than kZPadSteps are needed
 bool pad_axis(int size, int lo, int hi, ZoePadAxis *a) {
     const int base = size;
@@ -235,33 +232,17 @@ bool pad_axis(int size, int lo, int hi, ZoePadAxis *a) {
 struct nunif_zoedepth_head : DeviceOwner {
     int F = 256, n_attr[4] = {16, 8, 4, 1};
     float alpha = 1000.f, min_temp = 0.0212f, max_temp = 50.f;
-    ZLin conv2, seed1, sproj1, sproj2, proj1[4], proj2[4], att1[4], e80;
+    PackedLinear conv2, seed1, sproj1, sproj2, proj1[4], proj2[4], att1[4], e80;
     float *seed_w = nullptr, *seed_b = nullptr, *att_w[4] = {}, *att_b[4] = {}, *w1 = nullptr, *w2 = nullptr, *logbinom = nullptr;
     DeviceBuf x0, s1, t128, emb[2], xa, a1, cen[5], e80buf;
     int tap_h[5] = {}, tap_w[5] = {}, tap_b = 0;
 };
 
 namespace {
-int zlin_from(nunif_zoedepth_head *h, const TensorMap &m, const std::string &key, int N, int K, int k0, int Kt, int Np, ZLin *L) {
-    // rows n < N, columns k0 .. k0 + K of a [N][Kt] 1x1 conv; N padded to Np
-    const HostTensor *w, *b;
-    int rc;
-    if ((rc = find(m, key + ".weight", &w)) || (rc = find(m, key + ".bias", &b))) return rc;
-    NUNIF_REQUIRE(w->numel == (int64_t)N * Kt && b->numel == N, "%s: unexpected shape", key.c_str());
-    const float *wd = w->data;
-    std::vector<f16> packed = pack_nt_ks(N, Np, K, [=](int n, int k) { return wd[(size_t)n * Kt + k0 + k]; });
-    std::vector<float> bias(Np, 0.f);
-    for (int n = 0; n < N; ++n) bias[n] = b->data[n];
-    L->N = Np; L->K = K;
-    if ((rc = h->upload(packed, &L->w))) return rc;
-    return h->upload(bias, &L->b);
-}
-int zrun(const ZLin &L, const f16 *a, long M, int relu, f16 *out, hipStream_t s, const char *tag) {
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.a = a; g.B = 1; g.Hi = 1; g.Wi = (int)M; g.Cin = L.K; g.Ho = 1; g.Wo = (int)M; g.stride = 1; g.kw = 1;
-    g.K = L.K; g.w = L.w; g.bias = L.b; g.N = L.N; g.mode = 0; g.act = relu ? 2 : 0; g.slope = 0.f; g.out = out;
-    g.ldo = L.N; g.n_real = L.N; g.ps = 1;
+// a 1x1 conv as a token Linear; the output rows are N wide, padding included (e80: 80 of 96)
+int zrun(const PackedLinear &L, const f16 *a, long M, int relu, f16 *out, hipStream_t s, const char *tag) {
+    GemmArgs g = gemm_token_args(L, a, M, out);
+    g.act = relu ? 2 : 0; g.ldo = L.N; g.n_real = L.N;
     return launch_gemm(g, s, tag);
 }
 unsigned zblocks(long n) { return (unsigned)((n + 255) / 256); }
@@ -283,18 +264,18 @@ extern "C" int nunif_hip_zoedepth_head_create(const nunif_tensor_desc *tensors, 
         const int F = (int)b->numel;
         if (F != 256) { set_error("zoedepth_head: bottleneck width %d unsupported (256)", F); rc = NUNIF_HIP_EUNSUPPORTED; break; }
         h->F = F;
-        if ((rc = zlin_from(h, m, "conv2", F, F, 0, F, F, &h->conv2)) || (rc = zlin_from(h, m, "seed_bin_regressor.conv1", 256, F, 0, F, 256, &h->seed1)) ||
-            (rc = zlin_from(h, m, "seed_projector.conv1", kZEmb, F, 0, F, kZEmb, &h->sproj1)) ||
-            (rc = zlin_from(h, m, "seed_projector.conv2", kZEmb, kZEmb, 0, kZEmb, kZEmb, &h->sproj2)))
+        if ((rc = linear_from(h, m, "conv2", F, F, 32, &h->conv2)) || (rc = linear_from(h, m, "seed_bin_regressor.conv1", 256, F, 32, &h->seed1)) ||
+            (rc = linear_from(h, m, "seed_projector.conv1", kZEmb, F, 32, &h->sproj1)) ||
+            (rc = linear_from(h, m, "seed_projector.conv2", kZEmb, kZEmb, 32, &h->sproj2)))
             break;
         if ((rc = find(m, "seed_bin_regressor.conv2.weight", &w)) || (rc = find(m, "seed_bin_regressor.conv2.bias", &b))) break;
         if (w->numel != (int64_t)kZBins * 256 || b->numel != kZBins) { set_error("zoedepth_head: 64 bins expected"); rc = NUNIF_HIP_EUNSUPPORTED; break; }
         if ((rc = h->upload_f32(w, &h->seed_w)) || (rc = h->upload_f32(b, &h->seed_b))) break;
         for (int i = 0; i < 4 && !rc; ++i) {
             const std::string p = "projectors." + std::to_string(i), a = "attractors." + std::to_string(i);
-            if ((rc = zlin_from(h, m, p + ".conv1", kZEmb, F, 0, F, kZEmb, &h->proj1[i])) ||
-                (rc = zlin_from(h, m, p + ".conv2", kZEmb, kZEmb, 0, kZEmb, kZEmb, &h->proj2[i])) ||
-                (rc = zlin_from(h, m, a + ".conv1", kZEmb, kZEmb, 0, kZEmb, kZEmb, &h->att1[i])))
+            if ((rc = linear_from(h, m, p + ".conv1", kZEmb, F, 32, &h->proj1[i])) ||
+                (rc = linear_from(h, m, p + ".conv2", kZEmb, kZEmb, 32, &h->proj2[i])) ||
+                (rc = linear_from(h, m, a + ".conv1", kZEmb, kZEmb, 32, &h->att1[i])))
                 break;
             if ((rc = find(m, a + ".conv2.weight", &w)) || (rc = find(m, a + ".conv2.bias", &b))) break;
             const int na = (int)b->numel;
@@ -304,7 +285,7 @@ extern "C" int nunif_hip_zoedepth_head_create(const nunif_tensor_desc *tensors, 
         }
         if (rc) break;
         const std::string c = "conditional_log_binomial.mlp.";
-        if ((rc = zlin_from(h, m, c + "0", kZHid, kZEmb, kZRel, kZRel + kZEmb, kZHidP, &h->e80))) break;
+        if ((rc = linear_from(h, m, c + "0", kZHid, kZEmb, 32, &h->e80, false, nullptr, kZRel, kZRel + kZEmb))) break;
         const HostTensor *w2, *b2;
         if ((rc = find(m, c + "0.weight", &w)) || (rc = find(m, c + "2.weight", &w2)) || (rc = find(m, c + "2.bias", &b2))) break;
         if (w2->numel != 4 * kZHid || b2->numel != 4) { set_error("%s2: unexpected shape", c.c_str()); rc = NUNIF_HIP_EINVAL; break; }
