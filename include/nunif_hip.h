@@ -366,6 +366,15 @@ int nunif_hip_light_inpaint_infer(nunif_light_inpaint *handle, const float *x, c
 int nunif_hip_light_inpaint_infer_ex(nunif_light_inpaint *handle, const float *x, const uint8_t *mask, float *out, int32_t B,
                                      int32_t H, int32_t W, int32_t closing, int32_t inner_iter, int32_t outer_iter,
                                      int32_t mirror_x, void *stream);
+/* infer_ex that also copies out the maps of the forward (tests only; the same function body as infer_ex, the copies are
+ * device-to-device between its launches).  taps: n_taps = 21 device pointers, NULL = skip:
+ *   0 hard, 1 soft: f32 [B,H,W];  2 mtok: u8 [B,h1,w1];  then f16 NHWC maps: 3 patch (after the mask bias), 4 enc1.gmlp (after the
+ *   gMLP and its shortcuts), 5 enc1, 6 down, 7 + 2 i enc2.i.gmlp, 8 + 2 i enc2.i (i < 5; the image net has no enc2.4), 17 up
+ *   (x1 + shuffle(up)), 18 dec1.gmlp, 19 dec1, 20 to_image ([B,h1,w1,48], the video nets [B,h1,w1,64] with 48 real channels).
+ * Level 1: h1 = Hp / 4, w1 = Wp / 4, C = base_dim; level 2 (down, enc2.*): h1 / 2, w1 / 2, 2 C; Hp = H + 64 - H % 64 (W alike). */
+int nunif_hip_light_inpaint_debug_taps(nunif_light_inpaint *handle, const float *x, const uint8_t *mask, float *out, int32_t B,
+                                       int32_t H, int32_t W, int32_t closing, int32_t inner_iter, int32_t outer_iter,
+                                       int32_t mirror_x, void *const *taps, int32_t n_taps, void *stream);
 
 /* iw3 output formats.
  * anaglyph: iw3/anaglyph.py apply_anaglyph_redcyan :96-110; left, right, out: [3,H,W] f32; mode 0 color, 1 gray, 2 half-color,

@@ -525,8 +525,14 @@ int lin(const PackedLinear &L, const f16 *a, long rows, int n_real, int act, flo
     return launch_gemm(g, s, tag);
 }
 
+// a debug tap: the map as it stands at this point of the stream, copied device to device (nullptr: nothing is enqueued)
+int li_tap(void *dst, const void *src, size_t bytes, hipStream_t s) {
+    if (dst) NUNIF_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s));
+    return NUNIF_HIP_OK;
+}
+
 template <int C, int V>
-int run_gblock(nunif_light_inpaint *h, const GBlock &g, f16 *x, int B, int hh, int ww, hipStream_t s) {
+int run_gblock(nunif_light_inpaint *h, const GBlock &g, f16 *x, int B, int hh, int ww, hipStream_t s, void *tap_gmlp) {
     const int pad = (g.shift && !g.temporal) ? g.ws / 2 : 0, hp = hh + 2 * pad, wp = ww + 2 * pad, N = g.ws * g.ws;
     const long tok = (long)B * hh * ww, tokp = (long)B * hp * wp, wins = g.temporal ? 0 : tokp / N;
     f16 *a = (f16 *)h->a.p, *pi = (f16 *)h->pi.p, *vt = (f16 *)h->vt.p, *st = (f16 *)h->st.p, *gg = (f16 *)h->g.p;
@@ -564,6 +570,7 @@ int run_gblock(nunif_light_inpaint *h, const GBlock &g, f16 *x, int B, int hh, i
         ProfScope ps("li_crop_add_kernel", s, 0.0, (double)tok * C * 6.0);
         li_crop_add_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(x, po, B, hh, ww, pad, C);
     }
+    if ((rc = li_tap(tap_gmlp, x, (size_t)tok * C * sizeof(f16), s))) return rc;
     // GLUConvMLP: 1x1 -> GLU -> replicate pad + 3x3, residual
     if ((rc = lin(g.w1, x, tok, C, 0, 0.f, nullptr, y, s, "li_glu_w1"))) return rc;
     {
@@ -580,19 +587,24 @@ int run_gblock(nunif_light_inpaint *h, const GBlock &g, f16 *x, int B, int hh, i
 
 // (C, V) pairs of the registered nets: image / video-small 96: (96,192) (192,192) (192,384); video-medium 128: (128,256)
 // (256,512); video-large 192: (192,384) (384,768)
-int run_gblock_any(nunif_light_inpaint *h, const GBlock &g, f16 *x, int B, int hh, int ww, hipStream_t s) {
+// taps: nullptr, or the two slots of this block (<block>.gmlp after li_crop_add_kernel, <block> = its output)
+int run_gblock_any(nunif_light_inpaint *h, const GBlock &g, f16 *x, int B, int hh, int ww, hipStream_t s, void *const *taps) {
     const int key = g.C * 1000 + g.V;
+    void *tap_gmlp = taps ? taps[0] : nullptr;
+    int rc;
     switch (key) {
-        case 96192: return run_gblock<96, 192>(h, g, x, B, hh, ww, s);
-        case 192192: return run_gblock<192, 192>(h, g, x, B, hh, ww, s);
-        case 192384: return run_gblock<192, 384>(h, g, x, B, hh, ww, s);
-        case 128256: return run_gblock<128, 256>(h, g, x, B, hh, ww, s);
-        case 256512: return run_gblock<256, 512>(h, g, x, B, hh, ww, s);
-        case 384768: return run_gblock<384, 768>(h, g, x, B, hh, ww, s);
+        case 96192: rc = run_gblock<96, 192>(h, g, x, B, hh, ww, s, tap_gmlp); break;
+        case 192192: rc = run_gblock<192, 192>(h, g, x, B, hh, ww, s, tap_gmlp); break;
+        case 192384: rc = run_gblock<192, 384>(h, g, x, B, hh, ww, s, tap_gmlp); break;
+        case 128256: rc = run_gblock<128, 256>(h, g, x, B, hh, ww, s, tap_gmlp); break;
+        case 256512: rc = run_gblock<256, 512>(h, g, x, B, hh, ww, s, tap_gmlp); break;
+        case 384768: rc = run_gblock<384, 768>(h, g, x, B, hh, ww, s, tap_gmlp); break;
         default:
             set_error("light_inpaint: block with C = %d, V = %d is not a registered variant", g.C, g.V);
             return NUNIF_HIP_EUNSUPPORTED;
     }
+    if (rc) return rc;
+    return li_tap(taps ? taps[1] : nullptr, x, (size_t)B * hh * ww * g.C * sizeof(f16), s);
 }
 
 }  // namespace
@@ -685,13 +697,19 @@ extern "C" int nunif_hip_light_inpaint_infer(nunif_light_inpaint *h, const float
     return nunif_hip_light_inpaint_infer_ex(h, x, mask, out, B, H, W, closing, inner_iter, outer_iter, 0, stream);
 }
 
-extern "C" int nunif_hip_light_inpaint_infer_ex(nunif_light_inpaint *h, const float *x, const uint8_t *mask, float *out, int32_t B,
-                                                int32_t H, int32_t W, int32_t closing, int32_t inner_iter, int32_t outer_iter,
-                                                int32_t mirror_x, void *stream) {
+// The slots of nunif_hip_light_inpaint_debug_taps (include/nunif_hip.h), in the order the maps come to exist
+enum LiTap { T_HARD = 0, T_SOFT, T_MTOK, T_PATCH, T_ENC1_GMLP, T_ENC1, T_DOWN, T_ENC2 = 7 /* 2 i: .gmlp, 2 i + 1: the block */,
+             T_UP = 17, T_DEC1_GMLP, T_DEC1, T_TO_IMAGE, T_COUNT };
+
+// infer and debug_taps: ONE body.  taps = nullptr (infer) or T_COUNT device pointers, NULL = skip; a tap is a device-to-device copy
+// enqueued between the launches, so that without taps the launch sequence is what it was
+static int li_infer(nunif_light_inpaint *h, const float *x, const uint8_t *mask, float *out, int32_t B, int32_t H, int32_t W,
+                    int32_t closing, int32_t inner_iter, int32_t outer_iter, int32_t mirror_x, void *const *taps, void *stream) {
     NUNIF_REQUIRE(h && x && mask && out && B > 0 && H > 0 && W > 0 && inner_iter >= 0 && outer_iter >= 0 && x != out,
                   "light_inpaint_infer: bad argument");
     NUNIF_REQUIRE(!h->video || B == 12, "light_inpaint_infer: the video net takes exactly 12 frames per call (got %d)", B);
     hipStream_t s = (hipStream_t)stream;
+    auto tap = [&](int i) -> void * { return taps ? taps[i] : nullptr; };
     const int Hp = H + 64 - H % 64, Wp = W + 64 - W % 64;            // light_inpaint_v1.py:135-137: always pads (1..64)
     const int h1 = Hp / 4, w1 = Wp / 4, h2 = h1 / 2, w2 = w1 / 2;
     const long px = (long)B * H * W, t1 = (long)B * h1 * w1, t2 = (long)B * h2 * w2;
@@ -727,6 +745,7 @@ extern "C" int nunif_hip_light_inpaint_infer_ex(nunif_light_inpaint *h, const fl
         li_blur_kernel<<<pb, 256, 0, s>>>(hard, hard, mf2, B, H, W, 0, h->gauss);
         li_blur_kernel<<<pb, 256, 0, s>>>(mf2, hard, soft, B, H, W, 1, h->gauss);
     }
+    if ((rc = li_tap(tap(T_HARD), hard, (size_t)px * 4, s)) || (rc = li_tap(tap(T_SOFT), soft, (size_t)px * 4, s))) return rc;
     f16 *x1 = (f16 *)h->x1.p, *x2 = (f16 *)h->x2.p, *a = (f16 *)h->a.p, *ti = (f16 *)h->ti.p;
     uint8_t *mtok = (uint8_t *)h->mtok.p;
     {
@@ -739,13 +758,15 @@ extern "C" int nunif_hip_light_inpaint_infer_ex(nunif_light_inpaint *h, const fl
         const long n = t1 * (C / 8);
         li_mask_bias_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(x1, mtok, h->mask_bias, t1, C);
     }
-    if ((rc = run_gblock_any(h, h->enc1, x1, B, h1, w1, s))) return rc;
+    if ((rc = li_tap(tap(T_MTOK), mtok, (size_t)t1, s)) || (rc = li_tap(tap(T_PATCH), x1, (size_t)t1 * C * 2, s))) return rc;
+    if ((rc = run_gblock_any(h, h->enc1, x1, B, h1, w1, s, taps ? taps + T_ENC1_GMLP : nullptr))) return rc;
     {   // down: 2x2 stride-2 conv as a gather GEMM
         GemmArgs g = gemm_map_args(h->down, x1, B, h1, w1, C, h2, w2, x2, 2, 2);
         if ((rc = launch_gemm(g, s, "li_down"))) return rc;
     }
+    if ((rc = li_tap(tap(T_DOWN), x2, (size_t)t2 * C2 * 2, s))) return rc;
     for (int i = 0; i < h->n_enc2; ++i) {
-        if ((rc = run_gblock_any(h, h->enc2[i], x2, B, h2, w2, s))) return rc;
+        if ((rc = run_gblock_any(h, h->enc2[i], x2, B, h2, w2, s, taps ? taps + T_ENC2 + 2 * i : nullptr))) return rc;
     }
     {   // x = x1 + pixel_shuffle(up(x2), 2), written over x1
         GemmArgs g = gemm_map_args(h->up, x2, B, h2, w2, C2, h2, w2, x1);
@@ -757,19 +778,39 @@ extern "C" int nunif_hip_light_inpaint_infer_ex(nunif_light_inpaint *h, const fl
             if ((rc = launch_patchup(pu, s))) return rc;
         } else if ((rc = launch_gemm(g, s, "li_up"))) return rc;
     }
-    if ((rc = run_gblock_any(h, h->dec1, x1, B, h1, w1, s))) return rc;
+    if ((rc = li_tap(tap(T_UP), x1, (size_t)t1 * C * 2, s))) return rc;
+    if ((rc = run_gblock_any(h, h->dec1, x1, B, h1, w1, s, taps ? taps + T_DEC1_GMLP : nullptr))) return rc;
     if (h->video) {
         if ((rc = lin(h->to_image1, x1, t1, 64, 0, 0.f, nullptr, ti, s, "li_to_image"))) return rc;
     } else {
         ConvArgs cv = conv_args(h->to_image, x1, B, h1, w1, ti, 1, 0, 1);
         if ((rc = launch_conv(cv, s))) return rc;
     }
+    if ((rc = li_tap(tap(T_TO_IMAGE), ti, (size_t)t1 * (h->video ? 64 : 48) * 2, s))) return rc;
     {
         ProfScope ps("li_compose_kernel", s, 0.0, (double)px * 36.0);
         li_compose_kernel<<<pb, 256, 0, s>>>(x, hard, soft, ti, out, B, H, W, h1, w1, h->video ? 64 : 48, mirror_x);
     }
     NUNIF_LAUNCH_CHECK();
     return NUNIF_HIP_OK;
+}
+
+extern "C" int nunif_hip_light_inpaint_infer_ex(nunif_light_inpaint *h, const float *x, const uint8_t *mask, float *out, int32_t B,
+                                                int32_t H, int32_t W, int32_t closing, int32_t inner_iter, int32_t outer_iter,
+                                                int32_t mirror_x, void *stream) {
+    return li_infer(h, x, mask, out, B, H, W, closing, inner_iter, outer_iter, mirror_x, nullptr, stream);
+}
+
+extern "C" int nunif_hip_light_inpaint_debug_taps(nunif_light_inpaint *h, const float *x, const uint8_t *mask, float *out, int32_t B,
+                                                  int32_t H, int32_t W, int32_t closing, int32_t inner_iter, int32_t outer_iter,
+                                                  int32_t mirror_x, void *const *taps, int32_t n_taps, void *stream) {
+    NUNIF_REQUIRE(h && taps && n_taps == T_COUNT, "light_inpaint_debug_taps: %d tap slots expected", (int)T_COUNT);
+    for (int i = h->n_enc2; i < 5; ++i)
+        NUNIF_REQUIRE(!taps[T_ENC2 + 2 * i] && !taps[T_ENC2 + 2 * i + 1], "light_inpaint_debug_taps: this net has no enc2.%d", i);
+    for (int i = 0; i < T_COUNT; ++i)
+        NUNIF_REQUIRE(taps[i] != (const void *)x && taps[i] != (const void *)mask && taps[i] != (void *)out,
+                      "light_inpaint_debug_taps: tap %d aliases an argument", i);
+    return li_infer(h, x, mask, out, B, H, W, closing, inner_iter, outer_iter, mirror_x, taps, stream);
 }
 
 // ---- stand-alone mask morphology (iw3/dilation.py dilate :41-46, erode :49-54, closing :57-64, mask_closing :145-153,

@@ -57,6 +57,7 @@ class HipLightInpaintEngine(HipEngine):
     def __init__(self, state_dict, device):
         super().__init__(device, state_dict, "nunif_hip_light_inpaint_create", "nunif_hip_light_inpaint_destroy",
                          label="light_inpaint")
+        self.dim, self.video = int(state_dict["mask_bias"].numel()), "patch.weight" in state_dict
 
     def infer(self, x, mask, closing, inner_iter, outer_iter, mirror_x=False):
         B, C, H, W = x.shape
@@ -66,6 +67,41 @@ class HipLightInpaintEngine(HipEngine):
                   ctypes.c_void_p(mask.data_ptr()), ctypes.c_void_p(out.data_ptr()), B, H, W, 1 if closing else 0, int(inner_iter),
                   int(outer_iter), 1 if mirror_x else 0)
         return out
+
+    TAPS = ("hard", "soft", "mtok", "patch", "enc1.gmlp", "enc1", "down") + tuple(
+        f"enc2.{i}{s}" for i in range(5) for s in (".gmlp", "")) + ("up", "dec1.gmlp", "dec1", "to_image")
+
+    def debug_taps(self, x, mask, closing, inner_iter, outer_iter, mirror_x=False, names=None):
+        """``infer`` that also returns the maps of the forward (tests only; ``nunif_hip_light_inpaint_debug_taps``): (out, {name: map}),
+        every map NCHW at its own resolution — ``hard`` / ``soft`` fp32 [B,1,H,W], ``mtok`` bool [B,1,h1,w1], the rest fp16."""
+        B, C, H, W = x.shape
+        assert C == 3 and tuple(mask.shape) == (B, 1, H, W)
+        dim, n2 = self.dim, 5 if self.video else 4
+        h1, w1 = (H + 64 - H % 64) // 4, (W + 64 - W % 64) // 4
+        names = [n for n in self.TAPS if not n.startswith(f"enc2.{n2}")] if names is None else list(names)
+        assert set(names) <= set(self.TAPS), sorted(set(names) - set(self.TAPS))
+        bufs = {}
+        for n in names:
+            if n in ("hard", "soft"):
+                bufs[n] = torch.empty(B, 1, H, W, dtype=torch.float32, device=x.device)
+            elif n == "mtok":
+                bufs[n] = torch.empty(B, 1, h1, w1, dtype=torch.uint8, device=x.device)
+            elif n == "to_image":
+                bufs[n] = torch.empty(B, h1, w1, 64 if n2 == 5 else 48, dtype=torch.float16, device=x.device)
+            elif n == "down" or n.startswith("enc2."):
+                bufs[n] = torch.empty(B, h1 // 2, w1 // 2, 2 * dim, dtype=torch.float16, device=x.device)
+            else:
+                bufs[n] = torch.empty(B, h1, w1, dim, dtype=torch.float16, device=x.device)
+        ptrs = (ctypes.c_void_p * len(self.TAPS))(*[bufs[n].data_ptr() if n in bufs else None for n in self.TAPS])
+        out = torch.empty_like(x)
+        self.call(_hip.lib().nunif_hip_light_inpaint_debug_taps, self.handle, ctypes.c_void_p(x.data_ptr()),
+                  ctypes.c_void_p(mask.data_ptr()), ctypes.c_void_p(out.data_ptr()), B, H, W, 1 if closing else 0, int(inner_iter),
+                  int(outer_iter), 1 if mirror_x else 0, ptrs, len(self.TAPS))
+        taps = {}
+        for n, t in bufs.items():
+            taps[n] = t if t.dim() == 4 and t.dtype != torch.float16 else t.permute(0, 3, 1, 2)[:, :48 if n == "to_image" else None]
+        taps["mtok"] = taps["mtok"].bool() if "mtok" in taps else None
+        return out, {k: v for k, v in taps.items() if v is not None}
 
 
 @register_model

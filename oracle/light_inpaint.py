@@ -45,9 +45,17 @@ def window_gmlp(sd, p, x, ws, shift):
     return x[:, :, pad:x.shape[2] - pad, pad:x.shape[3] - pad] if pad else x
 
 
-def gmlp_block(sd, p, x, ws, shift):
-    x = x + window_gmlp(sd, p, x, ws, shift)
-    return _glu_conv(sd, p, x)
+def _tap(taps, name, t):
+    """Record a map of the forward for the localised checks (tests/errloc.py): NCHW at token resolution, left as computed."""
+    if taps is not None:
+        taps[name] = t
+    return t
+
+
+def gmlp_block(sd, p, x, ws, shift, taps=None):
+    """``taps``: ``<p>gmlp`` = the map after the gMLP and both of its shortcuts, ``<p>`` (without the dot) = the block's output."""
+    x = _tap(taps, p + "gmlp", x + window_gmlp(sd, p, x, ws, shift))
+    return _tap(taps, p[:-1], _glu_conv(sd, p, x))
 
 
 def gaussian_kernel1d(k):
@@ -64,48 +72,52 @@ def mask_blur(m, k=15):
     return F.conv2d(m, g.view(1, 1, k, 1))
 
 
-def preprocess(x, mask, closing=False, inner_dilation=0, outer_dilation=0, base_width=None):
+def preprocess(x, mask, closing=False, inner_dilation=0, outer_dilation=0, base_width=None, taps=None):
+    """``taps``: a dict that receives ``hard`` (the closed / dilated 0 / 1 mask) and ``soft``, both [B,1,H,W] fp32 whatever x is."""
     if closing:
         m0 = mask.float()
         mask = (OM.closing(m0, kernel_size=3, n_iter=2) + m0).clamp(0, 1)
     else:
         mask = mask.float()
     mask = OM.dilate_inner(mask, inner_dilation, base_width).float()
-    mask = OM.dilate_outer(mask, outer_dilation, base_width).float()
+    mask = _tap(taps, "hard", OM.dilate_outer(mask, outer_dilation, base_width).float())
     x = x * (1 - mask)
-    return x, torch.clamp(mask_blur(mask) + mask, 0, 1)
+    return x, _tap(taps, "soft", torch.clamp(mask_blur(mask) + mask, 0, 1))
 
 
-def net(sd, x, mask):
-    """_forward: x normalised [B,3,Hp,Wp] (multiples of 64), mask float [B,1,Hp,Wp] -> [B,3,Hp,Wp]."""
+def net(sd, x, mask, taps=None):
+    """_forward: x normalised [B,3,Hp,Wp] (multiples of 64), mask float [B,1,Hp,Wp] -> [B,3,Hp,Wp].
+    ``taps``: a dict that receives ``mtok`` (bool), ``patch`` (after the mask bias), ``enc1.gmlp``, ``enc1``, ``down``, ``enc2.i.gmlp`` /
+    ``enc2.i``, ``up`` (x1 + shuffle(up)), ``dec1.gmlp``, ``dec1`` and ``to_image`` (the 48 channels before the pixel shuffle)."""
     x = F.leaky_relu(F.conv2d(F.pixel_unshuffle(x, 4), sd["patch.0.weight"], sd["patch.0.bias"]), 0.2)
-    mtok = F.pixel_unshuffle(mask, 4).amax(dim=1, keepdim=True) > 0.99
-    x = torch.where(mtok, sd["mask_bias"], x)
-    x1 = gmlp_block(sd, "enc1.", x, 16, True)
-    x2 = F.conv2d(x1, sd["down.weight"], sd["down.bias"], stride=2)
+    mtok = _tap(taps, "mtok", F.pixel_unshuffle(mask, 4).amax(dim=1, keepdim=True) > 0.99)
+    x = _tap(taps, "patch", torch.where(mtok, sd["mask_bias"], x))
+    x1 = gmlp_block(sd, "enc1.", x, 16, True, taps)
+    x2 = _tap(taps, "down", F.conv2d(x1, sd["down.weight"], sd["down.bias"], stride=2))
     for i, sh in enumerate((False, True, False, True)):
-        x2 = gmlp_block(sd, f"enc2.{i}.", x2, 8, sh)
+        x2 = gmlp_block(sd, f"enc2.{i}.", x2, 8, sh, taps)
     x2 = F.pixel_shuffle(F.conv2d(x2, sd["up.weight"], sd["up.bias"]), 2)
-    x = gmlp_block(sd, "dec1.", x1 + x2, 16, False)
-    x = F.conv2d(F.pad(x, (1, 1, 1, 1), mode="replicate"), sd["to_image.1.weight"], sd["to_image.1.bias"])
+    x = gmlp_block(sd, "dec1.", _tap(taps, "up", x1 + x2), 16, False, taps)
+    x = _tap(taps, "to_image", F.conv2d(F.pad(x, (1, 1, 1, 1), mode="replicate"), sd["to_image.1.weight"], sd["to_image.1.bias"]))
     return F.pixel_shuffle(x, 4)
 
 
-def forward(sd, x, mask, skip_i2i_offset=True):
+def forward(sd, x, mask, skip_i2i_offset=True, taps=None):
     src = x
     H, W = x.shape[2:]
     pad1, pad2 = 64 - W % 64, 64 - H % 64
     xn = F.pad((x - 0.5) / 0.5, (0, pad1, 0, pad2), mode="replicate")
     mp = F.pad(mask, (0, pad1, 0, pad2), mode="replicate")
-    y = net(sd, xn, mp)[:, :, :H, :W]
+    y = net(sd, xn, mp, taps)[:, :, :H, :W]
     if not skip_i2i_offset:
         src, mask, y = (t[:, :, 16:-16, 16:-16] for t in (src, mask, y))
     return (src * (1 - mask) + y * mask).clamp(0, 1)
 
 
-def infer(sd, x, mask, closing=False, inner_dilation=0, outer_dilation=0, base_width=None):
-    x, mask = preprocess(x, mask, closing, inner_dilation, outer_dilation, base_width)
-    return forward(sd, x, mask, skip_i2i_offset=True)
+def infer(sd, x, mask, closing=False, inner_dilation=0, outer_dilation=0, base_width=None, taps=None):
+    """``taps``: as ``net``, plus ``hard`` / ``soft`` = the two masks of ``preprocess``."""
+    x, mask = preprocess(x, mask, closing, inner_dilation, outer_dilation, base_width, taps)
+    return forward(sd, x, mask, skip_i2i_offset=True, taps=taps)
 
 
 # ---- MLBWInpaintImage (iw3/mlbw_inpaint.py:78-157; max_width = None) ------------------------------------------------------
@@ -146,27 +158,39 @@ def _glu_conv(sd, p, x):
     return x + F.conv2d(F.pad(y, (1, 1, 1, 1), mode="replicate"), sd[p + "glu_conv.w2.weight"], sd[p + "glu_conv.w2.bias"])
 
 
-def video_net(sd, x, mask):
-    """_forward :166-197 (the micro-batching only chunks per-frame work): x [12,3,Hp,Wp] normalised, mask float."""
+def video_net(sd, x, mask, taps=None):
+    """_forward :166-197 (the micro-batching only chunks per-frame work): x [12,3,Hp,Wp] normalised, mask float.
+    ``taps``: as ``net`` (``enc2.i.gmlp`` of a temporal block = its input + the temporal gMLP)."""
     assert x.shape[0] == SEQ_LEN
-    mtok = F.pixel_unshuffle(mask, 4).amax(dim=1, keepdim=True) > 0.99
+    mtok = _tap(taps, "mtok", F.pixel_unshuffle(mask, 4).amax(dim=1, keepdim=True) > 0.99)
     x0 = F.leaky_relu(F.conv2d(x, sd["patch.weight"], sd["patch.bias"], stride=4), 0.1)
-    x0 = torch.where(mtok, sd["mask_bias"], x0)
-    x1 = gmlp_block(sd, "enc1.", x0, 16, False)
-    x2 = F.conv2d(x1, sd["down.weight"], sd["down.bias"], stride=2)
+    x0 = _tap(taps, "patch", torch.where(mtok, sd["mask_bias"], x0))
+    x1 = gmlp_block(sd, "enc1.", x0, 16, False, taps)
+    x2 = _tap(taps, "down", F.conv2d(x1, sd["down.weight"], sd["down.bias"], stride=2))
     for i, kind in enumerate(("s1", "t", "s0", "t", "s1")):
         p = f"enc2.{i}."
         if kind == "t":
-            x2 = _glu_conv(sd, p, x2 + temporal_gmlp(sd, p, x2))
+            x2 = _tap(taps, p[:-1], _glu_conv(sd, p, _tap(taps, p + "gmlp", x2 + temporal_gmlp(sd, p, x2))))
         else:
-            x2 = gmlp_block(sd, p, x2, 8, kind == "s1")
+            x2 = gmlp_block(sd, p, x2, 8, kind == "s1", taps)
     x3 = F.pixel_shuffle(F.conv2d(x2, sd["up.weight"], sd["up.bias"]), 2)
-    out = gmlp_block(sd, "dec1.", x1 + x3, 16, False)
-    return F.pixel_shuffle(F.conv2d(out, sd["to_image.weight"], sd["to_image.bias"]), 4)
+    out = gmlp_block(sd, "dec1.", _tap(taps, "up", x1 + x3), 16, False, taps)
+    return F.pixel_shuffle(_tap(taps, "to_image", F.conv2d(out, sd["to_image.weight"], sd["to_image.bias"])), 4)
 
 
-def video_infer(sd, x, mask, closing=False, inner_dilation=0, outer_dilation=0, base_width=None):
-    """infer :140-164: pad the batch to 12 frames by repeating the first / last frame, preprocess, forward, un-pad."""
+def video_forward(sd, xp, mp, taps=None):
+    """The part of ``video_infer`` after ``preprocess``: xp [12,3,H,W] the masked frames, mp the soft mask."""
+    H, W = xp.shape[2:]
+    pad1, pad2 = 64 - W % 64, 64 - H % 64
+    xn = F.pad((xp - 0.5) / 0.5, (0, pad1, 0, pad2), mode="replicate")
+    mpp = F.pad(mp, (0, pad1, 0, pad2), mode="replicate")
+    y = video_net(sd, xn, mpp, taps)[:, :, :H, :W]
+    return (xp * (1 - mp) + y * mp).clamp(0, 1)
+
+
+def video_infer(sd, x, mask, closing=False, inner_dilation=0, outer_dilation=0, base_width=None, taps=None):
+    """infer :140-164: pad the batch to 12 frames by repeating the first / last frame, preprocess, forward, un-pad.
+    ``taps``: as ``infer``; the maps keep all 12 frames."""
     n = x.shape[0]
     b1 = b2 = 0
     if n % SEQ_LEN != 0:
@@ -174,13 +198,8 @@ def video_infer(sd, x, mask, closing=False, inner_dilation=0, outer_dilation=0, 
         b1, b2 = pad // 2, pad - pad // 2
         x = torch.cat([x[0:1]] * b1 + [x] + [x[-1:]] * b2, dim=0)
         mask = torch.cat([mask[0:1]] * b1 + [mask] + [mask[-1:]] * b2, dim=0)
-    xp, mp = preprocess(x, mask, closing, inner_dilation, outer_dilation, base_width)
-    H, W = x.shape[2:]
-    pad1, pad2 = 64 - W % 64, 64 - H % 64
-    xn = F.pad((xp - 0.5) / 0.5, (0, pad1, 0, pad2), mode="replicate")
-    mpp = F.pad(mp, (0, pad1, 0, pad2), mode="replicate")
-    y = video_net(sd, xn, mpp)[:, :, :H, :W]
-    out = (xp * (1 - mp) + y * mp).clamp(0, 1)
+    xp, mp = preprocess(x, mask, closing, inner_dilation, outer_dilation, base_width, taps)
+    out = video_forward(sd, xp, mp, taps)
     return out[b1:out.shape[0] - b2]
 
 

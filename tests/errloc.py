@@ -27,6 +27,15 @@ is pinned on its final outputs only, [B,1,h,w], with the side nets' constants an
 token (14 x 14 pixels of the map), per 4 x 4 token block (the footprint of one ``layer4_rn`` pixel pair) and per 8 x 32 conv patch of
 ``output_conv2.0``; DepthAA per 8 x 8 window = 16 x 16 pixels behind its centred pad, shifted by 8 pixels in blocks 0 and 2
 (``tests/depth_cases.py``).
+
+The light inpaint nets (``inpaint.light_inpaint_v1``, ``inpaint.light_video_inpaint_v1*``: csrc/light_inpaint.hip) go wrong per 16 x 16 /
+8 x 8 token window (the zero-padded shifted blocks, the per-window transposed token mixing), per 8 x 32-token conv patch and per token
+(the mask rule): cells (64, 64) and (32, 128) output pixels from pixel 0 (the pad is bottom / right only) with the clamped-output
+constants, and the engine's debug taps per window and conv patch of their level with the tap constants.  ``preprocess`` (the masks)
+runs in fp32 outside the emulation, so the token decisions are the same on all three sides (``tests/inpaint_cases.py``).  Measured on
+an MI355X over the 19 cases of tests/test_gpu_inpaint_errloc.py (profiles/light_inpaint_errloc.txt): outputs worst 1.28 global / 3.44 per
+region (the small video net at 12 x 72 x 136; the image net 1.20 / 1.36, 2.67 with the hot weights), taps worst 1.60 / 4.07 (``dec1``
+per 16-channel group).
 """
 import math
 
@@ -36,6 +45,7 @@ import torch.nn.functional as F
 from oracle import cunet as OC
 from oracle import depth_aa as ODAA
 from oracle import depth_anything_v2 as ODA
+from oracle import light_inpaint as OL
 from oracle import mlbw as OM
 from oracle import row_flow_v3 as ORF
 from oracle import swin_unet as O
@@ -68,6 +78,15 @@ DEPTH_ANYTHING, DEPTH_AA = "iw3.depth_anything", "iw3.depth_aa"
 DEPTH_ANYTHING_CELLS = ((14, 14), (56, 56), (8, 32))
 DEPTH_AA_CELL, DEPTH_AA_SHIFT = (16, 16), (8, 8)
 
+# the light inpaint nets (csrc/light_inpaint.hip): 4 x 4 pixels per level-1 token, pad bottom / right only (origin 0).  (64, 64) output
+# pixels = one 16 x 16 level-1 window = one 8 x 8 level-2 window, and the default half-cell shift is the shifted blocks' partition;
+# (32, 128) = the 8 x 32-token patch of a conv workgroup at level 1.  Taps at token resolution: the window and the conv patch of the level
+INPAINT_IMAGE = "inpaint.light_inpaint_v1"
+INPAINT_VIDEO = ("inpaint.light_video_inpaint_v1", "inpaint.light_video_inpaint_v1_medium", "inpaint.light_video_inpaint_v1_large")
+INPAINT = (INPAINT_IMAGE,) + INPAINT_VIDEO
+INPAINT_CELLS = ((64, 64), (32, 128))
+INPAINT_TAP_CELLS = {1: ((16, 16), (8, 32)), 2: ((8, 8), (8, 32))}
+
 # Thresholds: about twice the worst ratios measured on an MI355X over every case of tests/test_gpu_swin_errloc.py (its docstring)
 A_OUT, B_OUT, TAU_OUT = 2.5, 3.75, 5e-4          # clamped [0,1] outputs (worst 1.16 / 1.82); tau = one fp16 ulp in [0.5, 1)
 A_TAP, B_TAP = 3.5, 5.5                          # NHWC debug taps per 6 x 6 window and head (worst 1.69 / 2.78)
@@ -93,7 +112,11 @@ def warp_floor(c):
     return WARP_FLOOR_ULPS * 2.0 ** -23 * (0.5 * (w - 1) * sx + 0.5 * (h - 1) * sy)
 
 
-def _forward(sd, x, name, taps=None, no_clip=False, max_depth=0.0, infer=False):
+def _forward(sd, x, name, taps=None, no_clip=False, max_depth=0.0, infer=False, soft=None):
+    if name in INPAINT:
+        assert not no_clip and not infer and max_depth == 0.0 and soft is not None, "the inpaint nets take the soft mask only"
+        # x: the pre-processed frames x (1 - hard mask), soft: the fp32 soft mask (``inpaint_preprocess``); taps: a dict to fill
+        return (OL.forward if name == INPAINT_IMAGE else OL.video_forward)(sd, x, soft, taps=taps)
     if name == DEPTH_ANYTHING:
         assert not no_clip and not infer, "the depth engine has no no_clip / infer"
         # x: [B,3,h,w] ImageNet-normalised; taps = the four encoder blocks that feed the head (None: the checkpoint's default)
@@ -117,10 +140,22 @@ def _forward(sd, x, name, taps=None, no_clip=False, max_depth=0.0, infer=False):
     return torch.clamp(O.unet_forward(sd, x, O.GEOMETRY.get(name, (0, 0, 0, SCALE[name]))[3], taps=taps), 0.0, 1.0)
 
 
+def inpaint_preprocess(x, mask, pre=None, taps=None):
+    """``oracle.light_inpaint.preprocess`` of the frames x (any float type) and the bool hole mask: (x (1 - hard), soft).  The soft mask
+    is fp32 in every precision, as in the reference (``mask.float()``, an fp32 gaussian), and it is computed OUTSIDE the fp16
+    emulation: the token decision max(soft) > 0.99 and the compose weights are then the same for the oracle, the emulation and the
+    engine (which blurs in fp32 too)."""
+    return OL.preprocess(x, mask, taps=taps, **(pre or {}))
+
+
 def oracle64(sd, x, name, taps=None, no_clip=False, **kwargs):
     """The oracle forward with the state dict and the input cast to float64 (float64 output, clamped like the wrapper).
-    ``kwargs``: ``max_depth`` (the depth engine's metric head), ``infer`` (DepthAA.infer instead of forward(clamp=False))."""
+    ``kwargs``: ``max_depth`` (the depth engine's metric head), ``infer`` (DepthAA.infer instead of forward(clamp=False)); the inpaint
+    nets: ``mask`` (bool holes) and ``pre`` (the options of ``preprocess``), x = the frames as given to ``infer``."""
     sd64 = {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
+    if name in INPAINT:
+        xp, soft = inpaint_preprocess(x.double(), kwargs["mask"], kwargs.get("pre"), taps)
+        return _forward(sd64, xp, name, taps, soft=soft)
     return _forward(sd64, x.double(), name, taps, no_clip, **kwargs)
 
 
@@ -128,6 +163,10 @@ def emulated(sd, x, name, taps=None, no_clip=False, **kwargs):
     """The reference's own GPU arithmetic: fp16 parameters, every op result rounded to fp16 (oracle/fp16_emulation.py).
     ``half_weights`` keeps every key containing ``norm`` in fp32: that is right for the ViT LayerNorms of the depth engine
     (``pretrained.blocks.*.norm1 / norm2``, ``pretrained.norm``), which autocast runs in fp32 with fp32 parameters."""
+    if name in INPAINT:
+        xp, soft = inpaint_preprocess(x.float(), kwargs["mask"], kwargs.get("pre"), taps)
+        with fp16_autocast_emulation():
+            return _forward(half_weights(sd), xp, name, taps, soft=soft)
     with fp16_autocast_emulation():
         return _forward(half_weights(sd), x.float(), name, taps, no_clip, **kwargs)
 
@@ -142,7 +181,7 @@ def mlbw_pad(h, w):
     return (4 - h % 4) // 2, (32 - w % 32) // 2
 
 
-def cells_for(name, origin=0, shape=None):
+def cells_for(name, origin=0, shape=None, level=None):
     """[(cell, offset)] of the windows of every level mapped to output pixels: the aligned partition of each level.
     ``origin``: the tile-output pixel the compared map starts at (a crop of the tile output).
     The side nets have rectangular cells: entries ((cell_h, cell_w), (off_y, off_x)[, (shift_y, shift_x)]); the shift is the second
@@ -150,7 +189,11 @@ def cells_for(name, origin=0, shape=None):
     centred, so its windows start at (-ph1, -pw1) of the ``shape`` = (h, w) output, and its shifted blocks sit 2 tokens further
     (sy / sx of nunif_hip_mlbw_create: (2, 2) tokens = (2, 16) pixels for the full nets, (0, 2) = (0, 16) for the small ones).
     The depth engine: cells (14, 14) / (56, 56) / (8, 32) from pixel 0, shifted by half a cell.  DepthAA: (16, 16) cells from
-    (-ph1, -pw1) of the ``shape`` = (h, w) map (``depth_aa_pad``), the second partition 8 pixels further."""
+    (-ph1, -pw1) of the ``shape`` = (h, w) map (``depth_aa_pad``), the second partition 8 pixels further.
+    The inpaint nets: (64, 64) and (32, 128) output pixels from pixel 0; ``level`` = 1 / 2: the cells of a tap at that token resolution."""
+    if name in INPAINT:
+        return [(c, (0, 0)) for c in (INPAINT_CELLS if level is None else INPAINT_TAP_CELLS[level])]
+    assert level is None, "level is an option of the inpaint nets"
     if name == ROW_FLOW:
         return [(c, (0, 0)) for c in ROW_FLOW_CELLS]
     if name == DEPTH_ANYTHING:                      # no pad: tokens, token blocks and conv patches all start at pixel 0

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import errloc as E
 from conftest import GOLDEN, psnr, sd_checksum
 from oracle import light_inpaint as OL
 from oracle import mlbw as OM
@@ -34,6 +35,17 @@ def test_oracle_mlbw_inpaint_image_flow(g):
     assert le is not None and (ri - g["mi_right_only"].float()).abs().max().item() < 2e-3
 
 
+def _errloc(y, sd, x, mask, name, **pre):
+    """The localised bound of tests/errloc.py next to a PSNR assert: worst (64, 64) / (32, 128) region against the float64 oracle."""
+    E.set_threads()
+    n, b1 = x.shape[0], 0
+    if name != E.INPAINT_IMAGE and n < OL.SEQ_LEN:      # video_infer :141-150: first / last frame repeated up to 12
+        b1 = (OL.SEQ_LEN - n) // 2
+        x, mask = (torch.cat([t[0:1]] * b1 + [t] + [t[-1:]] * (OL.SEQ_LEN - n - b1)) for t in (x, mask))
+    y64, ye = (f(sd, x, name, mask=mask, pre=pre)[b1:b1 + n] for f in (E.oracle64, E.emulated))
+    return E.check_localised(y.cpu().float(), y64, ye, E.cells_for(name), E.A_OUT, E.B_OUT, E.TAU_OUT, label=name)
+
+
 def _models():
     from nunif_amd.nunif.models import create_model
     from nunif_amd.iw3 import models  # noqa: F401
@@ -53,11 +65,13 @@ def test_hip_light_inpaint(hiplib, g):
     assert y.shape == x.shape and y.dtype == x.dtype
     p = psnr(y.cpu(), g["infer"])
     assert p >= 50.0, p
+    _errloc(y, OL.random_state_dict(701), g["x"], g["mask"], mi.name)
     keep = ~OL.preprocess(g["x"], g["mask"])[1].expand_as(g["x"]).gt(0)                  # outside the soft mask: the input
     assert torch.equal(y.cpu()[keep], g["x"][keep])
     y2 = mi.infer(x, mask, closing=True, inner_dilation=1, outer_dilation=2, base_width=50)
     p = psnr(y2.cpu(), g["infer_close"])
     assert p >= 50.0, p
+    _errloc(y2, OL.random_state_dict(701), g["x"], g["mask"], mi.name, closing=True, inner_dilation=1, outer_dilation=2, base_width=50)
     assert torch.equal(mi.infer(x[:1], mask[:1]), y[:1])                                  # batch invariance
     with pytest.raises(NotImplementedError):
         mi(x, mask.float())
@@ -143,9 +157,12 @@ def test_hip_light_video_inpaint(hiplib, gv):
     y = mv.infer(x, mask)
     p = psnr(y.cpu(), gv["infer12"])
     assert y.shape == x.shape and p >= 50.0, p
+    _errloc(y, OL.video_random_state_dict(801), gv["x"], gv["mask"], mv.name)
     y7 = mv.infer(x[:7], mask[:7], closing=True, inner_dilation=1, outer_dilation=1, base_width=36)
     p = psnr(y7.cpu(), gv["infer7"])
     assert y7.shape[0] == 7 and p >= 50.0, p
+    _errloc(y7, OL.video_random_state_dict(801), gv["x"][:7], gv["mask"][:7], mv.name, closing=True, inner_dilation=1, outer_dilation=1,
+            base_width=36)
     with pytest.raises(AssertionError):
         mv.infer(torch.cat([x, x[:1]]), torch.cat([mask, mask[:1]]))
 
@@ -167,6 +184,9 @@ def test_large_frame_kernel_choices_at_small_size(hiplib, g, gv, monkeypatch):
     monkeypatch.setenv("NUNIF_GEMM_BIG_M", "1")
     b, bv = mi.infer(x, mask).clone(), mv.infer(xv, mkv).clone()
     assert psnr(b.cpu(), g["infer"]) >= 50.0 and psnr(bv.cpu(), gv["infer12"]) >= 50.0
+    for yi, yv in ((a, av), (b, bv)):
+        _errloc(yi, OL.random_state_dict(701), g["x"], g["mask"], mi.name)
+        _errloc(yv, OL.video_random_state_dict(801), gv["x"], gv["mask"], mv.name)
     assert psnr(a, b) >= 60.0 and psnr(av, bv) >= 60.0, (psnr(a, b), psnr(av, bv))
 
 
@@ -230,5 +250,6 @@ def test_hip_light_video_inpaint_medium_large(hiplib):
         y = mv.to("cuda:0").infer(x, mask, inner_dilation=1)
         p = psnr(y.cpu(), g["y_" + tag].float())
         assert y.shape == x.shape and p >= 50.0, (tag, p)
+        _errloc(y, OL.video_random_state_dict(seed, base_dim=dim, lv2_mlp_ratio=2), g["x"].float(), g["mask"], name, inner_dilation=1)
     with pytest.raises(ValueError):
         create_model("inpaint.light_video_inpaint_v1", base_dim=64)
