@@ -267,6 +267,16 @@ int nunif_hip_depth_anything_forward(nunif_depth_anything *handle, const float *
  * The network is not in the reference tree; oracle/video_depth_anything_net.py restates the published architecture, PARITY UNPINNED. */
 int nunif_hip_depth_anything_reset_state(nunif_depth_anything *handle);
 int nunif_hip_depth_anything_is_temporal(const nunif_depth_anything *handle);
+/* TESTS ONLY: temporal module `module` (0: layer_3, 1: layer_4, 2: path_4, 3: path_3) alone on B consecutive frames of its input
+ * map, with the launches of _forward.  x: [B][P][C] f32 device (rounded to fp16 on entry, C = the module's width), out: [B][P][C]
+ * f32 device.  taps: NULL, or 12 f32 device pointers (NULL = skip) in the order gn, proj_in, ln0, att0, res0, ln1, att1, res1, ff_ln,
+ * geglu, ff, out — the maps behind GroupNorm, proj_in, per attention block its LayerNorm, the attention kernel's output and the
+ * hidden state after to_out, then ff_norm, GEGLU, the hidden state after ff.net.2 and the module's output; [B][P][C] each, geglu
+ * [B][P][4 C].  The call advances the handle's window by B frames and touches only this module's K0 / V0 rings; any P > 0 is
+ * accepted, and another P or another module starts a new window.  A handle driven through this entry is for tests: call
+ * _reset_state before it is used for _forward again. */
+int nunif_hip_depth_anything_debug_temporal(nunif_depth_anything *handle, int32_t module, const float *x, float *out, int32_t B,
+                                            int32_t P, float *const *taps, int32_t n_taps, void *stream);
 
 /* The six activations the published DepthAnythingCore hooks for ZoeDepth (iw3/zoedepth_model.py:161-164 loads
  * "DepthAnythingMetricDepth" through torch.hub; the net is not in the reference tree): the 32-channel map behind the first conv +

@@ -153,6 +153,8 @@ SIGNATURES = {
     "nunif_hip_depth_anything_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "nunif_hip_depth_anything_reset_state": (c_int32, [c_void_p]),
     "nunif_hip_depth_anything_is_temporal": (c_int32, [c_void_p]),
+    "nunif_hip_depth_anything_debug_temporal": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32,
+                                                          ctypes.POINTER(c_void_p), c_int32, c_void_p]),
     "nunif_hip_depth_anything_forward_features": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                                             ctypes.POINTER(DaFeatures), c_void_p]),
     "nunif_hip_zoedepth_head_create": (c_int32, [ctypes.POINTER(TensorDesc), c_int32, c_float, c_float, c_float,

@@ -775,6 +775,88 @@ extern "C" void nunif_hip_depth_anything_destroy(nunif_depth_anything *h) {
     delete h;
 }
 
+// ---- Video-Depth-Anything: temporal module i on the B frames' maps x = [B][P][C], updated in place (depth_temporal.hip) --------------
+// Everything per token runs once over the B * P tokens; GroupNorm is per frame (blockIdx.y); the attention is the one sequential
+// step — frame f attends to the window as frames 0 .. f - 1 left it (t_idx[f]: its window position, t_st[f]: the ring's start).
+// The caller has sized the module's K0 / V0 rings and the scratch buffers ta .. tpart for B * P * C.
+// taps (nunif_hip_depth_anything_debug_temporal) = nullptr in the forward, else VT_COUNT fp32 device pointers, NULL = skip; a tap is
+// one conversion enqueued between the launches, so that without taps the launch sequence is what it was
+enum VdaTap { VT_GN = 0, VT_PROJ_IN, VT_LN0, VT_ATT0, VT_RES0, VT_LN1, VT_ATT1, VT_RES1, VT_FF_LN, VT_GEGLU, VT_FF, VT_OUT, VT_COUNT };
+
+namespace {
+__global__ void __launch_bounds__(256) vda_to_f32_kernel(const f16 *__restrict__ x, float *__restrict__ y, long n) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) y[i] = (float)x[i];
+}
+__global__ void __launch_bounds__(256) vda_to_f16_kernel(const float *__restrict__ x, f16 *__restrict__ y, long n) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) y[i] = (f16)x[i];
+}
+int vda_tap(float *const *taps, int i, const f16 *src, long n, hipStream_t s) {
+    if (!taps || !taps[i]) return NUNIF_HIP_OK;
+    vda_to_f32_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(src, taps[i], n);
+    NUNIF_LAUNCH_CHECK();
+    return NUNIF_HIP_OK;
+}
+}  // namespace
+
+static int run_tmod(nunif_depth_anything *h, int i, f16 *x, int B, int P, const int *t_idx, const int *t_st, hipStream_t st,
+                    float *const *taps = nullptr) {
+    TMod &tm = h->tm[i];
+    const int C = tm.C;
+    const long T = (long)B * P;
+    f16 *a = (f16 *)h->ta.p, *hs = (f16 *)h->th.p, *tq = (f16 *)h->tqkv.p, *ta = (f16 *)h->tatt.p, *hid = (f16 *)h->thid.p, *gg = (f16 *)h->tgg.p;
+    int rc;
+    if ((rc = launch_vda_groupnorm(x, tm.gn_g, tm.gn_b, a, (float2 *)h->tpart.p, B, P, C, 1e-6f, st))) return rc;
+    if ((rc = vda_tap(taps, VT_GN, a, T * C, st))) return rc;
+    if ((rc = run_tok(tm.proj_in, a, T, 0, nullptr, hs, st, "vda_proj_in"))) return rc;
+    if ((rc = vda_tap(taps, VT_PROJ_IN, hs, T * C, st))) return rc;
+    for (int k = 0; k < 2; ++k) {
+        TAtt &at = tm.at[k];
+        if ((rc = launch_vda_layernorm(hs, at.g, at.b, a, T, C, 1e-5f, st))) return rc;
+        if ((rc = vda_tap(taps, VT_LN0 + 3 * k, a, T * C, st))) return rc;
+        if ((rc = run_tok(at.qkv, a, T, 0, nullptr, tq, st, "vda_qkv"))) return rc;
+        for (int f = 0; f < B; ++f) {
+            VdaTattnArgs ga;
+            ga.qkv = tq + (size_t)f * P * 3 * C; ga.kc = (f16 *)at.kc.p; ga.vc = (f16 *)at.vc.p; ga.pq = at.pq; ga.pk = at.pk; ga.pv = at.pv;
+            ga.att = ta + (size_t)f * P * C; ga.P = P; ga.C = C; ga.hd = C / 8; ga.start = t_st[f]; ga.idx = t_idx[f];
+            if ((rc = launch_vda_tattn(ga, st))) return rc;
+        }
+        if ((rc = vda_tap(taps, VT_ATT0 + 3 * k, ta, T * C, st))) return rc;
+        if ((rc = run_tok(at.out, ta, T, 0, hs, hs, st, "vda_to_out"))) return rc;                 // hs += to_out(att)
+        if ((rc = vda_tap(taps, VT_RES0 + 3 * k, hs, T * C, st))) return rc;
+    }
+    if ((rc = launch_vda_layernorm(hs, tm.ff_g, tm.ff_b, a, T, C, 1e-5f, st))) return rc;
+    if ((rc = vda_tap(taps, VT_FF_LN, a, T * C, st))) return rc;
+    if ((rc = run_tok(tm.ff1, a, T, 0, nullptr, hid, st, "vda_ff1"))) return rc;
+    if ((rc = launch_vda_geglu(hid, gg, T, 4 * C, st))) return rc;
+    if ((rc = vda_tap(taps, VT_GEGLU, gg, T * 4 * C, st))) return rc;
+    if ((rc = run_tok(tm.ff2, gg, T, 0, hs, hs, st, "vda_ff2"))) return rc;                        // hs += ff2(geglu(ff1(norm(hs))))
+    if ((rc = vda_tap(taps, VT_FF, hs, T * C, st))) return rc;
+    if ((rc = run_tok(tm.proj_out, hs, T, 0, x, x, st, "vda_proj_out"))) return rc;                // x += proj_out(hs)
+    return vda_tap(taps, VT_OUT, x, T * C, st);
+}
+
+// frame f of B joins the window at position t_len; beyond 31 cached frames the oldest leaves (its slot is the next one written).
+// -> the window position / ring start of each frame, and in t_len / t_start the state behind the last one
+static void vda_window_plan(int B, int &t_len, int &t_start, std::vector<int> &t_idx, std::vector<int> &t_st) {
+    for (int f = 0; f < B; ++f) {
+        t_idx[f] = t_len; t_st[f] = t_start;
+        if (t_len + 1 > kTLen - 1) t_start = (t_start + 1) & (kTLen - 1);
+        else ++t_len;
+    }
+}
+// the scratch of run_tmod for maps of pc = B * P * C values
+static int vda_ensure_scratch(nunif_depth_anything *h, int B, size_t pc) {
+    const size_t e2 = sizeof(f16);
+    int rc;
+    if ((rc = h->ta.ensure(pc * e2)) || (rc = h->th.ensure(pc * e2)) || (rc = h->tatt.ensure(pc * e2)) || (rc = h->tqkv.ensure(3 * pc * e2)) ||
+        (rc = h->thid.ensure(8 * pc * e2)) || (rc = h->tgg.ensure(4 * pc * e2)) ||
+        (rc = h->tpart.ensure((size_t)B * (kVdaGnBlocks + 1) * 1024 * sizeof(float2))))
+        return rc;
+    return NUNIF_HIP_OK;
+}
+
 // x: [B,3,h,w] f32 (ImageNet-normalised), pos: [1 + gh*gw][D] f32 (interpolated position embedding, device),
 // depth: [B,h,w] f32
 // feat (optional): the maps ZoeDepth's head reads are left in the workspace and described there (nunif_da_features); the
@@ -873,50 +955,16 @@ static int da_forward(nunif_depth_anything *h, const float *x, const float *pos,
         for (int i = 0; i < 4; ++i) same = same && h->t_P[i] == tP[i];
         if (!same) { h->t_len = 0; h->t_start = 0; for (int i = 0; i < 4; ++i) h->t_P[i] = tP[i]; }     // another resolution: a new window
         t_len_end = h->t_len; t_start_end = h->t_start;
-        for (int f = 0; f < B; ++f) {
-            // frame f joins the window at position t_len; beyond 31 cached frames the oldest leaves (its slot is the next one written)
-            t_idx[f] = t_len_end; t_st[f] = t_start_end;
-            if (t_len_end + 1 > kTLen - 1) t_start_end = (t_start_end + 1) & (kTLen - 1);
-            else ++t_len_end;
-        }
+        vda_window_plan(B, t_len_end, t_start_end, t_idx, t_st);
         size_t pc = 0;
         for (int i = 0; i < 4; ++i) {
             pc = std::max(pc, (size_t)B * tP[i] * h->tm[i].C);
             for (TAtt &at : h->tm[i].at)
                 if ((rc = at.kc.ensure((size_t)kTLen * tP[i] * h->tm[i].C * e2)) || (rc = at.vc.ensure((size_t)kTLen * tP[i] * h->tm[i].C * e2))) return rc;
         }
-        if ((rc = h->ta.ensure(pc * e2)) || (rc = h->th.ensure(pc * e2)) || (rc = h->tatt.ensure(pc * e2)) || (rc = h->tqkv.ensure(3 * pc * e2)) ||
-            (rc = h->thid.ensure(8 * pc * e2)) || (rc = h->tgg.ensure(4 * pc * e2)) ||
-            (rc = h->tpart.ensure((size_t)B * (kVdaGnBlocks + 1) * 1024 * sizeof(float2))))
-            return rc;
+        if ((rc = vda_ensure_scratch(h, B, pc))) return rc;
     }
-    // x: the B frames' maps [B][tP[i]][C], updated in place.  Everything per token runs once over the B * P tokens; GroupNorm is per
-    // frame (blockIdx.y); the attention is the one sequential step — frame f attends to the window as frames 0 .. f - 1 left it
-    auto run_tmod = [&](int i, f16 *x, hipStream_t st) -> int {
-        TMod &tm = h->tm[i];
-        const int C = tm.C, P = tP[i];
-        const long T = (long)B * P;
-        f16 *a = (f16 *)h->ta.p, *hs = (f16 *)h->th.p, *tq = (f16 *)h->tqkv.p, *ta = (f16 *)h->tatt.p, *hid = (f16 *)h->thid.p, *gg = (f16 *)h->tgg.p;
-        int rc;
-        if ((rc = launch_vda_groupnorm(x, tm.gn_g, tm.gn_b, a, (float2 *)h->tpart.p, B, P, C, 1e-6f, st))) return rc;
-        if ((rc = run_tok(tm.proj_in, a, T, 0, nullptr, hs, st, "vda_proj_in"))) return rc;
-        for (TAtt &at : tm.at) {
-            if ((rc = launch_vda_layernorm(hs, at.g, at.b, a, T, C, 1e-5f, st))) return rc;
-            if ((rc = run_tok(at.qkv, a, T, 0, nullptr, tq, st, "vda_qkv"))) return rc;
-            for (int f = 0; f < B; ++f) {
-                VdaTattnArgs ga;
-                ga.qkv = tq + (size_t)f * P * 3 * C; ga.kc = (f16 *)at.kc.p; ga.vc = (f16 *)at.vc.p; ga.pq = at.pq; ga.pk = at.pk; ga.pv = at.pv;
-                ga.att = ta + (size_t)f * P * C; ga.P = P; ga.C = C; ga.hd = C / 8; ga.start = t_st[f]; ga.idx = t_idx[f];
-                if ((rc = launch_vda_tattn(ga, st))) return rc;
-            }
-            if ((rc = run_tok(at.out, ta, T, 0, hs, hs, st, "vda_to_out"))) return rc;                 // hs += to_out(att)
-        }
-        if ((rc = launch_vda_layernorm(hs, tm.ff_g, tm.ff_b, a, T, C, 1e-5f, st))) return rc;
-        if ((rc = run_tok(tm.ff1, a, T, 0, nullptr, hid, st, "vda_ff1"))) return rc;
-        if ((rc = launch_vda_geglu(hid, gg, T, 4 * C, st))) return rc;
-        if ((rc = run_tok(tm.ff2, gg, T, 0, hs, hs, st, "vda_ff2"))) return rc;                        // hs += ff2(geglu(ff1(norm(hs))))
-        return run_tok(tm.proj_out, hs, T, 0, x, x, st, "vda_proj_out");                               // x += proj_out(hs)
-    };
+    auto run_tmod = [&](int i, f16 *x, hipStream_t st) -> int { return ::run_tmod(h, i, x, B, tP[i], t_idx.data(), t_st.data(), st); };
 
     {   // patch embedding
         ProfScope ps("da_im2col_kernel", s, 0.0, (double)B * N * (kKp * 2.0 + 588 * 4.0));
@@ -1155,6 +1203,36 @@ extern "C" int nunif_hip_depth_anything_reset_state(nunif_depth_anything *h) {
     NUNIF_REQUIRE(h, "depth_anything_reset_state: NULL handle");
     h->t_len = 0;
     h->t_start = 0;
+    return NUNIF_HIP_OK;
+}
+
+// One temporal module alone, for the tests (include/nunif_hip.h).  The window key of a handle driven through here is t_P = P at
+// `module` and 0 elsewhere: another module or another P starts a new window, and so does the next forward (its four P are > 0).
+extern "C" int nunif_hip_depth_anything_debug_temporal(nunif_depth_anything *h, int32_t module, const float *x, float *out, int32_t B,
+                                                       int32_t P, float *const *taps, int32_t n_taps, void *stream) {
+    NUNIF_REQUIRE(h && h->temporal && x && out && module >= 0 && module < 4 && B > 0 && P > 0,
+                  "depth_anything_debug_temporal: a temporal engine, module 0..3, B > 0 and P > 0 expected");
+    NUNIF_REQUIRE(!taps || n_taps == VT_COUNT, "depth_anything_debug_temporal: %d tap slots expected", (int)VT_COUNT);
+    hipStream_t s = (hipStream_t)stream;
+    TMod &tm = h->tm[module];
+    const size_t pc = (size_t)B * P * tm.C, e2 = sizeof(f16);
+    bool same = true;
+    for (int i = 0; i < 4; ++i) same = same && h->t_P[i] == (i == module ? P : 0);
+    if (!same) { h->t_len = 0; h->t_start = 0; for (int i = 0; i < 4; ++i) h->t_P[i] = i == module ? P : 0; }
+    std::vector<int> t_idx(B, 0), t_st(B, 0);
+    int t_len_end = h->t_len, t_start_end = h->t_start;
+    vda_window_plan(B, t_len_end, t_start_end, t_idx, t_st);
+    int rc;
+    for (TAtt &at : tm.at)
+        if ((rc = at.kc.ensure((size_t)kTLen * P * tm.C * e2)) || (rc = at.vc.ensure((size_t)kTLen * P * tm.C * e2))) return rc;
+    if ((rc = vda_ensure_scratch(h, B, pc)) || (rc = h->m1.ensure(pc * e2))) return rc;
+    f16 *m = (f16 *)h->m1.p;
+    vda_to_f16_kernel<<<(unsigned)((pc + 255) / 256), 256, 0, s>>>(x, m, (long)pc);
+    NUNIF_LAUNCH_CHECK();
+    if ((rc = run_tmod(h, module, m, B, P, t_idx.data(), t_st.data(), s, taps))) return rc;
+    vda_to_f32_kernel<<<(unsigned)((pc + 255) / 256), 256, 0, s>>>(m, out, (long)pc);
+    NUNIF_LAUNCH_CHECK();
+    h->t_len = t_len_end; h->t_start = t_start_end;
     return NUNIF_HIP_OK;
 }
 

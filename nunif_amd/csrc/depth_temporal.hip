@@ -14,6 +14,12 @@
 // (fp16, [32 slots][P][C], a ring) ONCE per frame, and the position part is three [32][C] fp32 tables (Wq pe, Wk pe, Wv pe)
 // computed when the weights are loaded.  Per frame the attention then reads the two caches once — 2 x 32 x P x C x 2 bytes, the
 // algorithmic minimum for this step — and the Linears see P tokens, not 32 P.
+//
+// Pinned against float64 (tests/test_gpu_vda_errloc.py, cases in tests/vda_cases.py, figures in profiles/vda_temporal_errloc.txt): one
+// module alone through nunif_hip_depth_anything_debug_temporal — its output per pixel and frame, every launch's map per pixel and
+// head — for C = 64 .. 1024, both attention forms, P = 1 .. 2070 and streams of 66 frames (the ring's start once round and past it),
+// with the reference's own fp16 arithmetic as the yardstick.  That pins the kernels to the ORACLE; the oracle's parity with the
+// published network stays unpinned (above).
 #include <algorithm>
 #include <cstdlib>
 

@@ -10,6 +10,8 @@ the architecture and the checkpoint key layout (``pretrained.*``, ``head.*``, ``
 ones, restated in ``oracle/video_depth_anything_net.py`` — **parity unpinned** (INTEGRATION.md), the streaming cache policy in
 particular.  ``VideoDepthAnythingStreamingModel.load_model(backbone=HipVideoDepthAnythingStreaming(state_dict))`` plugs it in.
 """
+import ctypes
+
 import torch
 
 from .. import _hip
@@ -38,6 +40,26 @@ class HipVideoDepthAnythingStreaming(HipDepthAnythingV2):
     def reset_state(self):
         _hip.check(_hip.lib().nunif_hip_depth_anything_reset_state(self.handle))
         self.frame_id = 0
+
+    TEMPORAL_TAPS = ("gn", "proj_in", "ln0", "att0", "res0", "ln1", "att1", "res1", "ff_ln", "geglu", "ff", "out")
+
+    @torch.inference_mode()
+    def debug_temporal(self, module, maps, taps=False):
+        """TESTS ONLY (``nunif_hip_depth_anything_debug_temporal``): temporal module ``module`` (0..3) alone on ``maps`` [B, P, C] fp32,
+        B consecutive frames of its input map -> its output [B, P, C] fp32, or (output, {tap: [B, P, C] fp32; ``geglu`` [B, P, 4 C]})
+        with ``taps``.  Advances this handle's window by B frames; another P or module starts a new window.  ``reset_state()`` before
+        the handle serves ``infer_video_depth_*`` again."""
+        x = maps.to(device=self.device, dtype=torch.float32).contiguous()
+        if x.dim() != 3:
+            raise ValueError(f"debug_temporal takes [B, P, C] maps, got {tuple(x.shape)}")
+        B, P, C = x.shape
+        out = torch.empty_like(x)
+        bufs = {n: torch.empty(B, P, 4 * C if n == "geglu" else C, dtype=torch.float32, device=self.device)
+                for n in self.TEMPORAL_TAPS} if taps else {}
+        ptrs = (ctypes.c_void_p * len(self.TEMPORAL_TAPS))(*[bufs[n].data_ptr() for n in self.TEMPORAL_TAPS]) if taps else None
+        self.call(_hip.lib().nunif_hip_depth_anything_debug_temporal, self.handle, int(module), ctypes.c_void_p(x.data_ptr()),
+                  ctypes.c_void_p(out.data_ptr()), B, P, ptrs, len(self.TEMPORAL_TAPS) if taps else 0)
+        return (out, bufs) if taps else out
 
     @torch.inference_mode()
     def infer_video_depth_one(self, frame, use_amp=True):

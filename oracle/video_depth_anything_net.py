@@ -54,19 +54,28 @@ def new_state():
     return {"caches": [[None, None] for _ in range(4)], "frames": 0}
 
 
-def temporal_module(sd, p, x, cache=None):
+def temporal_module(sd, p, x, cache=None, taps=None):
     """x: [T, C, H, W], the T frames of ONE video at this stage.  cache None: offline, the T frames attend to each other.
-    cache = [c0, c1] (each None or [L, H*W, C]): streaming, T == 1.  -> (y [T, C, H, W], new cache)."""
+    cache = [c0, c1] (each None or [L, H*W, C]): streaming, T == 1.  -> (y [T, C, H, W], new cache).
+    ``taps``: a dict to fill with the maps of the forward as [T, H*W, C] (``geglu`` [T, H*W, 4 C]), under the names of the engine's
+    ``nunif_hip_depth_anything_debug_temporal``: gn, proj_in, ln{a}, att{a}, res{a} (a = 0, 1), ff_ln, geglu, ff, out."""
     T, C, H, W = x.shape
+
+    def tap(name, v):
+        if taps is not None:
+            taps[name] = v
     t = p + "temporal_transformer."
     h = F.group_norm(x, GN_GROUPS, sd[t + "norm.weight"], sd[t + "norm.bias"], eps=1e-6)
     h = h.permute(0, 2, 3, 1).reshape(T, H * W, C)
+    tap("gn", h)
     h = F.linear(h, sd[t + "proj_in.weight"], sd[t + "proj_in.bias"])
+    tap("proj_in", h)
     b = t + "transformer_blocks.0."
     hd = C // HEADS
     new_cache = []
     for a in range(2):
         n = F.layer_norm(h, (C,), sd[f"{b}norms.{a}.weight"], sd[f"{b}norms.{a}.bias"])          # eps 1e-5 (nn.LayerNorm default)
+        tap(f"ln{a}", n)
         seq = n if cache is None or cache[a] is None else torch.cat([cache[a], n], dim=0)
         assert seq.shape[0] <= MAX_LEN
         new_cache.append(seq[-(MAX_LEN - 1):])
@@ -80,13 +89,21 @@ def temporal_module(sd, p, x, cache=None):
         v = F.linear(kv_in, sd[ab + "to_v.weight"]).reshape(L, H * W, HEADS, hd).permute(1, 2, 0, 3)
         att = torch.softmax((q * hd ** -0.5) @ k.transpose(-2, -1), dim=-1) @ v
         att = att.permute(2, 0, 1, 3).reshape(T, H * W, C)
+        tap(f"att{a}", att)
         h = h + F.linear(att, sd[ab + "to_out.0.weight"], sd[ab + "to_out.0.bias"])
+        tap(f"res{a}", h)
     n = F.layer_norm(h, (C,), sd[b + "ff_norm.weight"], sd[b + "ff_norm.bias"])
+    tap("ff_ln", n)
     g = F.linear(n, sd[b + "ff.net.0.proj.weight"], sd[b + "ff.net.0.proj.bias"])
     val, gate = g.chunk(2, dim=-1)                                                                       # diffusers GEGLU
-    h = h + F.linear(val * F.gelu(gate), sd[b + "ff.net.2.weight"], sd[b + "ff.net.2.bias"])
+    gg = val * F.gelu(gate)
+    tap("geglu", gg)
+    h = h + F.linear(gg, sd[b + "ff.net.2.weight"], sd[b + "ff.net.2.bias"])
+    tap("ff", h)
     h = F.linear(h, sd[t + "proj_out.weight"], sd[t + "proj_out.bias"])
-    return h.reshape(T, H, W, C).permute(0, 3, 1, 2) + x, new_cache
+    y = h.reshape(T, H, W, C).permute(0, 3, 1, 2) + x
+    tap("out", y.permute(0, 2, 3, 1).reshape(T, H * W, C))
+    return y, new_cache
 
 
 def head(sd, feats, gh, gw, caches=None):

@@ -36,6 +36,14 @@ runs in fp32 outside the emulation, so the token decisions are the same on all t
 an MI355X over the 19 cases of tests/test_gpu_inpaint_errloc.py (profiles/light_inpaint_errloc.txt): outputs worst 1.28 global / 3.44 per
 region (the small video net at 12 x 72 x 136; the image net 1.20 / 1.36, 2.67 with the hot weights), taps worst 1.60 / 4.07 (``dec1``
 per 16-channel group).
+
+The Video-Depth-Anything temporal modules (``iw3.vda_temporal``: csrc/depth_temporal.hip and ``run_tmod`` of depth_anything.hip) go
+wrong per pixel (the attention's workgroup tails, GroupNorm's row lanes), per head (hd = C / 8 channels) and per frame (the window
+position, the ring slot): x = T consecutive frames of ONE module's input map [T, P, C], run as a stream from ``new_state()``; the
+region is one pixel — cell (1, 1) of the [T, C, 1, P] view — and for the engine's debug taps one pixel and one head.  The streaming
+whole net (``iw3.vda_stream``) takes T frames [T, 3, h, w] the same way, with the depth engine's cells.  ``vda_with_pe`` hands the
+fp32 sinusoidal table in through the ``pos_encoder.pe`` keys: evaluated inside the emulation mode, ``pos * div`` would be rounded to
+fp16 (up to 31 x 2^-11 rad) and the yardstick inflated (``tests/vda_cases.py``, ``tests/test_errloc_vda.py``).
 """
 import math
 
@@ -50,6 +58,7 @@ from oracle import mlbw as OM
 from oracle import row_flow_v3 as ORF
 from oracle import swin_unet as O
 from oracle import swin_unet_v2 as OV
+from oracle import video_depth_anything_net as VN
 from oracle.fp16_emulation import fp16_autocast_emulation, half_weights
 
 V2_SCALE = {"waifu2x.swin_unet_v2_1x": 1, "waifu2x.swin_unet_v2_2x": 2, "waifu2x.swin_unet_v2_4x": 4}
@@ -77,6 +86,19 @@ MLBW_CELL = (4, 32)
 DEPTH_ANYTHING, DEPTH_AA = "iw3.depth_anything", "iw3.depth_aa"
 DEPTH_ANYTHING_CELLS = ((14, 14), (56, 56), (8, 32))
 DEPTH_AA_CELL, DEPTH_AA_SHIFT = (16, 16), (8, 8)
+
+# Video-Depth-Anything: one temporal module on its own map (a region = one pixel, taps: one pixel and one head), and the streaming
+# net on frames (the depth engine's cells)
+VDA_TEMPORAL, VDA_STREAM = "iw3.vda_temporal", "iw3.vda_stream"
+VDA_TEMPORAL_CELL = (1, 1)
+VDA_TAPS = ("gn", "proj_in", "ln0", "att0", "res0", "ln1", "att1", "res1", "ff_ln", "geglu", "ff", "out")
+# The temporal modules' taps, per pixel and head: a region is hd = 8 .. 128 values, and the emulation's noise in 8 values is a
+# poor yardstick for one of them — measured on an MI355X over the 101 cases of tests/test_gpu_vda_errloc.py at the tap constants
+# (A_TAP 3.5, B_TAP 5.5): worst 3.14 global, 15.0 per region (``geglu`` at C = 64: one product of two rounded factors against a
+# region whose emulated noise happened to be 4e-4; ``att`` 7.3), and the engine's arrangement restated in torch (test_errloc_vda.py)
+# gives the same figures.  By the rule of the constants above — about twice the worst measured, for all cases at once (at B = 30 the
+# floor tau / B is smaller and the same runs read 3.14 / 20.9; profiles/vda_temporal_errloc.txt):
+A_VDA_TAP, B_VDA_TAP = 6.5, 30.0
 
 # the light inpaint nets (csrc/light_inpaint.hip): 4 x 4 pixels per level-1 token, pad bottom / right only (origin 0).  (64, 64) output
 # pixels = one 16 x 16 level-1 window = one 8 x 8 level-2 window, and the default half-cell shift is the shifted blocks' partition;
@@ -112,7 +134,52 @@ def warp_floor(c):
     return WARP_FLOOR_ULPS * 2.0 ** -23 * (0.5 * (w - 1) * sx + 0.5 * (h - 1) * sy)
 
 
-def _forward(sd, x, name, taps=None, no_clip=False, max_depth=0.0, infer=False, soft=None):
+def vda_pe_keys(sd):
+    """{``...attention_blocks.a.pos_encoder.pe``: C} of the 4 x 2 temporal attention blocks of a Video-Depth-Anything state dict."""
+    out = {}
+    for k, v in sd.items():
+        if k.startswith("head.motion_modules.") and k.endswith("to_q.weight"):
+            out[k[:-len("to_q.weight")] + "pos_encoder.pe"] = v.shape[0]
+    return out
+
+
+def vda_with_pe(sd, base=None):
+    """``sd`` with the fp32 position table of every temporal attention block under its ``pos_encoder.pe`` key ([1, 32, C], the
+    published buffer's shape), computed HERE — outside any emulation mode, as the reference's buffer is made at construction.  Keys
+    that ``base`` (the state dict the weights came from) already carries are taken from it as they are."""
+    out = dict(sd)
+    for k, c in vda_pe_keys(sd).items():
+        with torch._C.DisableTorchFunction():
+            out[k] = base[k].float().clone() if base is not None and k in base else VN.positional_encoding(c).unsqueeze(0)
+    return out
+
+
+def _vda_temporal(sd, x, module, hw, taps):
+    """T frames [T, P, C] of module ``module``'s input, one per streaming step from an empty cache -> [T, P, C]."""
+    (H, W), (T, P, C) = hw, x.shape
+    assert H * W == P, (hw, x.shape)
+    cache, outs, per = [None, None], [], []
+    for f in x:
+        tp = {} if taps is not None else None
+        y, cache = VN.temporal_module(sd, f"head.motion_modules.{module}.", f.reshape(1, H, W, C).permute(0, 3, 1, 2), cache, taps=tp)
+        outs.append(y.permute(0, 2, 3, 1).reshape(1, P, C))
+        per.append(tp)
+    if taps is not None:
+        taps.update({k: torch.cat([d[k] for d in per]) for k in per[0]})
+    return torch.cat(outs)
+
+
+def _vda_stream(sd, x):
+    st = VN.new_state()
+    return torch.stack([VN.infer_video_depth_one(sd, f, st) for f in x])
+
+
+def _forward(sd, x, name, taps=None, no_clip=False, max_depth=0.0, infer=False, soft=None, module=None, hw=None):
+    if name == VDA_TEMPORAL:
+        return _vda_temporal(sd, x, module, hw, taps)
+    if name == VDA_STREAM:
+        assert taps is None, "the streaming net has no taps here"
+        return _vda_stream(sd, x)
     if name in INPAINT:
         assert not no_clip and not infer and max_depth == 0.0 and soft is not None, "the inpaint nets take the soft mask only"
         # x: the pre-processed frames x (1 - hard mask), soft: the fp32 soft mask (``inpaint_preprocess``); taps: a dict to fill
@@ -152,6 +219,8 @@ def oracle64(sd, x, name, taps=None, no_clip=False, **kwargs):
     """The oracle forward with the state dict and the input cast to float64 (float64 output, clamped like the wrapper).
     ``kwargs``: ``max_depth`` (the depth engine's metric head), ``infer`` (DepthAA.infer instead of forward(clamp=False)); the inpaint
     nets: ``mask`` (bool holes) and ``pre`` (the options of ``preprocess``), x = the frames as given to ``infer``."""
+    if name in (VDA_TEMPORAL, VDA_STREAM):
+        sd = vda_with_pe(sd, sd)
     sd64 = {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
     if name in INPAINT:
         xp, soft = inpaint_preprocess(x.double(), kwargs["mask"], kwargs.get("pre"), taps)
@@ -167,6 +236,16 @@ def emulated(sd, x, name, taps=None, no_clip=False, **kwargs):
         xp, soft = inpaint_preprocess(x.float(), kwargs["mask"], kwargs.get("pre"), taps)
         with fp16_autocast_emulation():
             return _forward(half_weights(sd), xp, name, taps, soft=soft)
+    if name in (VDA_TEMPORAL, VDA_STREAM):
+        # ``pe_inside`` (tests only): leave the table to ``temporal_module``, i.e. evaluate it inside the mode — the trap
+        pe_inside = kwargs.pop("pe_inside", False)
+        hw16 = half_weights(sd)
+        if pe_inside:
+            hw16 = {k: v for k, v in hw16.items() if not k.endswith("pos_encoder.pe")}
+        else:
+            hw16 = vda_with_pe(hw16, sd)          # the fp32 buffer, not rounded with the parameters
+        with fp16_autocast_emulation():
+            return _forward(hw16, x.float(), name, taps, no_clip, **kwargs)
     with fp16_autocast_emulation():
         return _forward(half_weights(sd), x.float(), name, taps, no_clip, **kwargs)
 
@@ -193,6 +272,10 @@ def cells_for(name, origin=0, shape=None, level=None):
     The inpaint nets: (64, 64) and (32, 128) output pixels from pixel 0; ``level`` = 1 / 2: the cells of a tap at that token resolution."""
     if name in INPAINT:
         return [(c, (0, 0)) for c in (INPAINT_CELLS if level is None else INPAINT_TAP_CELLS[level])]
+    if name == VDA_TEMPORAL:                        # [T, C, 1, P] views: every pixel of every frame is a region
+        return [(VDA_TEMPORAL_CELL, (0, 0))]
+    if name == VDA_STREAM:
+        return [(c, (0, 0)) for c in DEPTH_ANYTHING_CELLS]
     assert level is None, "level is an option of the inpaint nets"
     if name == ROW_FLOW:
         return [(c, (0, 0)) for c in ROW_FLOW_CELLS]

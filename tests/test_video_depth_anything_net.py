@@ -12,6 +12,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import errloc as E
 from conftest import psnr
 from oracle import video_depth_anything_net as VN
 
@@ -155,6 +156,7 @@ def test_hip_streaming_network_vs_oracle_over_two_windows(vda_net):
         assert float(ref.std()) > 1e-3 and p >= 50.0 and rel < 1e-2, (i, p, rel)
         outs.append(y)
     print(f"\nVDA streaming, 36 frames: worst PSNR {worst_p:.2f} dB, worst rel. rms {worst_r:.2e}")
+    check_stream_localised(torch.stack(outs), sd, frames, "VDA_Stream_S 36 x 126x154")
     # reset_state starts the same stream again: the same bits
     net.reset_state()
     again = [net.infer_video_depth_one(f.to("cuda:0")).cpu() for f in frames[:3]]
@@ -163,6 +165,50 @@ def test_hip_streaming_network_vs_oracle_over_two_windows(vda_net):
     net.reset_state()
     alone = net.infer_video_depth_one(frames[2].to("cuda:0")).cpu()
     assert float((alone - outs[2]).abs().max()) > 0.05 * float(outs[2].std())
+
+
+def check_stream_localised(y, sd, frames, label):
+    """The stream's outputs [T, 1, h, w] region by region (the depth engine's cells: a token, a 4 x 4 token block, an 8 x 32 conv
+    patch) against the float64 stream, the reference's fp16 arithmetic over the same stream as the yardstick (tests/errloc.py)."""
+    E.set_threads()
+    with torch.inference_mode():
+        y64, ye = E.oracle64(sd, frames, E.VDA_STREAM), E.emulated(sd, frames, E.VDA_STREAM)
+    tau = E.TAP_TAU_REL * float(y64.pow(2).mean().sqrt())
+    st = E.localised_stats(y.reshape(y64.shape), y64, ye, E.cells_for(E.VDA_STREAM), E.B_SIDE, tau)
+    print(f"\nerrloc {label}: global {st['global']:.2f} worst {st['worst']:.2f} (err {st['_gmax']:.2e} noise {st['_nmax']:.2e})")
+    return E.assert_localised(st, E.A_SIDE, E.B_SIDE, tau, label=label)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("encoder", ["vitb", "vitl"])
+def test_hip_streaming_network_wide_encoders_vs_float64(hiplib, encoder):
+    """VDA_Stream_B / _L: a 3-frame stream at 70 x 98 (P = 35 / 12 / 35 / 140 pixels in the four temporal modules)."""
+    from nunif_amd.iw3.video_depth_anything_net import HipVideoDepthAnythingStreaming
+    sd = VN.random_state_dict(5, grid=8, encoder=encoder)
+    net = HipVideoDepthAnythingStreaming(sd)
+    frames = clip(14, 3, 70, 98)
+    y = torch.stack([net.infer_video_depth_one(f.to("cuda:0")).cpu() for f in frames])
+    check_stream_localised(y, sd, frames, f"VDA_Stream {encoder} 3 x 70x98")
+
+
+@pytest.mark.gpu
+def test_checkpoint_position_buffers_are_used(hiplib):
+    """A state dict that carries ``pos_encoder.pe`` buffers ([1, 32, C], the published layout): the engine and the oracle read them.
+    The tables are perturbed, so an engine that recomputed the sinusoidal code would miss the bound."""
+    from nunif_amd.iw3.video_depth_anything_net import HipVideoDepthAnythingStreaming
+    sd = dict(VN.random_state_dict(5))
+    g = torch.Generator().manual_seed(31)
+    for k, c in E.vda_pe_keys(sd).items():
+        sd[k] = (VN.positional_encoding(c) + 0.3 * torch.randn(32, c, generator=g)).unsqueeze(0)
+    net = HipVideoDepthAnythingStreaming(sd)
+    frames = clip(15, 4, 70, 98)
+    y = torch.stack([net.infer_video_depth_one(f.to("cuda:0")).cpu() for f in frames])
+    check_stream_localised(y, sd, frames, "VDA_Stream_S with pos_encoder.pe buffers")
+    # ... and the perturbation is visible at this bound: the same frames on the plain tables differ by far more than the bound allows
+    plain = HipVideoDepthAnythingStreaming(VN.random_state_dict(5))
+    y0 = torch.stack([plain.infer_video_depth_one(f.to("cuda:0")).cpu() for f in frames])
+    with pytest.raises(AssertionError):
+        check_stream_localised(y0, sd, frames, "plain tables against perturbed buffers")
 
 
 @pytest.mark.gpu
