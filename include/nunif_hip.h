@@ -976,6 +976,38 @@ int nunif_hip_find_transform(const float *xy1, const float *xy2, const uint8_t *
                              double sigma_min, double sigma_max, int32_t flags, float *shift_out, float *scale_out,
                              float *angle_out, void *workspace, int64_t workspace_bytes, float *trace_or_null, void *stream);
 
+/* stlizer pass 3 (stlizer/multipass_pipeline.py, reference): everything between pass 2's per-frame transforms and pass 4's
+ * per-frame fixes, on `stream`, without a host synchronisation.
+ * scene_weight: calc_scene_weight (:86-105) in fp32: (score - 0.5) / 0.25 clamped to [0, 1], squared below 0.65, first and last
+ *   frame 0; bit-equal to torch's.
+ * pass3_prepare: the angle clamped to +-90 (:359), the three per-frame values times the fp32 weight widened to float64 and their
+ *   inclusive prefix sums (:338-344) into paths [3, N]; two launches, the tile sums combined in index order.
+ * pass3_conv: conv1d_smoothing (:272-289) given its taps (gen_smoothing_kernel :64-75, built on the host): replicate pad (:78-83),
+ *   K-tap float64 correlation, minus the input, fix [3, N]; K odd, 1 <= K <= 4097.
+ * pass3_grad_opt: grad_opt (:292-334): the paths padded by three replicated elements and (x, y only) scaled by resolution_weight =
+ *   resolution / 320 (:297-302), `iteration` calls of torch.optim.LBFGS(history_size=10, max_iter=4, lr=1, tolerance_grad=1e-7,
+ *   tolerance_change=1e-9, line_search_fn=None).step on the loss of :311-322 with its gradient in closed form, and the fixes
+ *   (x - target) / resolution_weight (:330-332) into out [3, N].  LBFGS.step is restated decision for decision: the first step
+ *   min(1, 1 / |g|_1), the memory update only when y.s > 1e-10, H_diag = y.s / y.y, the two-loop recursion in the reference's
+ *   order over explicit s / y history vectors, prev_flat_grad and prev_loss carried across step calls, no re-evaluation after the
+ *   4th iteration, and the five exits.  x alone is held in two doubles (the closure's differences cancel most of it); the trace
+ *   is its high word.  1 + iteration * 4 * 22 + 1 launches whatever the data; nothing is read back; no float
+ *   atomics: bit-equal across calls, streams and workspaces.  1 <= N <= 1048576, 1 <= iteration <= 1024, else EINVAL.
+ *   trace_or_null: [iteration * 4, 3, N + 3], x after every LBFGS iteration slot (tests).
+ *   log_or_null: [iteration * 4, 32] doubles, the decision record of every slot as nunif_amd/csrc/stlizer_pass3_host.h lays it
+ *   out: which exit if any, the memory update taken or not, loss, g.d, max|g| and the optimizer's scalars (tests).
+ * workspace: caller-owned device bytes, 256-byte aligned, at least pass3_workspace_bytes(N, iteration) (prepare: (N, 1)); the
+ *   layout (records, history ring, per-launch partials) is in stlizer_pass3_host.h.  Calls that overlap on different streams need
+ *   their own. */
+int nunif_hip_stlizer_scene_weight(const float *scores, int32_t N, float *weight, void *stream);
+int64_t nunif_hip_stlizer_pass3_workspace_bytes(int32_t N, int32_t iteration);
+int nunif_hip_stlizer_pass3_prepare(const double *shift_x, const double *shift_y, const double *angle, const float *weight,
+                                    int32_t N, double *paths, void *workspace, int64_t workspace_bytes, void *stream);
+int nunif_hip_stlizer_pass3_conv(const double *paths, int32_t N, const double *taps, int32_t K, double *fix, void *stream);
+int nunif_hip_stlizer_pass3_grad_opt(const double *paths, const float *weight, int32_t N, double resolution_weight,
+                                     int32_t iteration, double penalty_weight, double *out, void *workspace,
+                                     int64_t workspace_bytes, double *trace_or_null, double *log_or_null, void *stream);
+
 /* Test hooks (tests/ only): snapshot every stage's NHWC fp16 output during the next forward calls, then read
  * them back one by one (returns 1 past the last tap).  Names match oracle.swin_unet.unet_forward(taps=...). */
 int nunif_hip_swin_unet_debug_taps(nunif_swin_unet *handle, int32_t enable);

@@ -265,6 +265,12 @@ SIGNATURES = {
     "nunif_hip_find_transform_workspace_bytes": (c_int64, [c_int32] * 3),
     "nunif_hip_find_transform": (c_int32, [c_void_p] * 4 + [c_int32] * 3 + [c_double] * 5 + [c_int32] + [c_void_p] * 4 + [c_int64,
                                                                                                                          c_void_p, c_void_p]),
+    "nunif_hip_stlizer_scene_weight": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p]),
+    "nunif_hip_stlizer_pass3_workspace_bytes": (c_int64, [c_int32, c_int32]),
+    "nunif_hip_stlizer_pass3_prepare": (c_int32, [c_void_p] * 4 + [c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
+    "nunif_hip_stlizer_pass3_conv": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
+    "nunif_hip_stlizer_pass3_grad_opt": (c_int32, [c_void_p, c_void_p, c_int32, c_double, c_int32, c_double, c_void_p, c_void_p,
+                                                  c_int64, c_void_p, c_void_p, c_void_p]),
     "nunif_hip_swin_unet_debug_taps":(c_int32, [c_void_p, c_int32]),
     "nunif_hip_swin_unet_get_tap": (c_int32, [c_void_p, c_int32, c_char_p, c_int32, c_void_p, c_int64,
                                               ctypes.POINTER(c_int64)]),
