@@ -197,6 +197,31 @@ void nunif_hip_swin_unet_v2_destroy(nunif_swin_unet_v2 *handle);
 int nunif_hip_swin_unet_v2_forward(nunif_swin_unet_v2 *handle, const float *x, float *z, int32_t batch, int32_t tile_size,
                                    int32_t clamp01, void *stream);
 
+/* waifu2x "waifu2x.wgmlp_4x" (waifu2x/models/wgmlp.py WGMLPBase :298-353, WGMLP4x :441-470): IR / Overscan stem :126-173, window-gMLP
+ * + GLU conv-MLP blocks :75-123 (nunif/modules/attention.py GMLP :621-651, WindowGMLP2d :654-693: 8 x 8 windows, zero-padded
+ * half-window shift in the order of get_shift_config :289-295), shortcut PatchDown / PatchUp :176-226, ToImage + SourceResidual
+ * :229-286.  State dict in the reference's key layout ("unet." prefix); only the registered geometry (base_dim 128, mlp ratios 2,
+ * 3 -> 3 channels) is carried.
+ * create / destroy replace WGMLP4x.__init__ :445-455; forward replaces WGMLP4x.forward :457-467 in eval mode: x [B,3,T,T] f32 device
+ * -> z [B,3,4T-72,4T-72] f32 device (offset 36), clamp01 != 0 = the eval clamp :467; T must satisfy tile_size_validator :406-409
+ * ((T - 16) % 48 == 0). */
+typedef struct nunif_wgmlp nunif_wgmlp;
+int nunif_hip_wgmlp_create(const nunif_tensor_desc *tensors, int32_t n_tensors, nunif_wgmlp **handle);
+void nunif_hip_wgmlp_destroy(nunif_wgmlp *handle);
+int nunif_hip_wgmlp_forward(nunif_wgmlp *handle, const float *x, float *z, int32_t batch, int32_t tile_size, int32_t clamp01,
+                            void *stream);
+/* tests: forward that also stores the output of every WGMLPBlock (wgmlp.py:92-101) as fp32 NHWC, concatenated in the order
+ * wgmlp1.blocks.*, wgmlp2.blocks.*, wgmlp3.blocks.*: [B,S,S,128] at level 1 and [B,S/2,S/2,256] at level 2, S = T - 16. */
+int nunif_hip_wgmlp_debug_taps(nunif_wgmlp *handle, const float *x, float *z, float *taps, int32_t batch, int32_t tile_size,
+                               int32_t clamp01, void *stream);
+/* tests: the WindowGMLP2d (attention.py:678-693 with GMLP.forward :634-651) of block `block` (0 .. 8 in the order above) alone on a
+ * caller-supplied map x [B,H,W,C] f32 (C = 128 at level 1, 256 at level 2; H, W multiples of 8; rounded to fp16 on entry), plain or
+ * shifted whatever the block's own place -> out [B,H,W,C] f32.  Optional (NULL: not stored) fp32 maps indexed like x: after
+ * LayerNorm 1 [C], GELU [2C], LayerNorm 2 [C], the token mixing [C] and the gate [C]. */
+int nunif_hip_wgmlp_debug_gmlp(nunif_wgmlp *handle, int32_t block, const float *x, float *out, int32_t batch, int32_t height,
+                               int32_t width, int32_t shift, float *tap_ln1, float *tap_gelu, float *tap_ln2, float *tap_mix,
+                               float *tap_gate, void *stream);
+
 typedef struct nunif_cunet nunif_cunet;
 int nunif_hip_cunet_create(const nunif_tensor_desc *tensors, int32_t n_tensors, int32_t no_clip, nunif_cunet **handle);
 void nunif_hip_cunet_destroy(nunif_cunet *handle);

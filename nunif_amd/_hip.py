@@ -108,6 +108,11 @@ SIGNATURES = {
     "nunif_hip_swin_unet_v2_create": (c_int32, [ctypes.POINTER(TensorDesc), c_int32, c_int32, ctypes.POINTER(c_void_p)]),
     "nunif_hip_swin_unet_v2_destroy": (None, [c_void_p]),
     "nunif_hip_swin_unet_v2_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "nunif_hip_wgmlp_create": (c_int32, [ctypes.POINTER(TensorDesc), c_int32, ctypes.POINTER(c_void_p)]),
+    "nunif_hip_wgmlp_destroy": (None, [c_void_p]),
+    "nunif_hip_wgmlp_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "nunif_hip_wgmlp_debug_taps": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "nunif_hip_wgmlp_debug_gmlp": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p] + [c_int32] * 4 + [c_void_p] * 6),
     "nunif_hip_cunet_create": (c_int32, [ctypes.POINTER(TensorDesc), c_int32, c_int32, ctypes.POINTER(c_void_p)]),
     "nunif_hip_cunet_destroy": (None, [c_void_p]),
     "nunif_hip_cunet_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),

@@ -28,7 +28,7 @@ EXTRA_FLAGS = {"stitch.hip": ["-ffp-contract=off"], "iw3_warp.hip": ["-ffp-contr
                "swin_kernels.hip": NO_SLP, "swin_patchup.hip": NO_SLP, "swin_patchdown.hip": NO_SLP, "cunet_up.hip": NO_SLP, "cunet_head.hip": NO_SLP,
                "cunet_kernels.hip": NO_SLP, "rowflow.hip": NO_SLP, "rowflow_v2.hip": NO_SLP, "depth_aa.hip": NO_SLP, "wa_block.hip": NO_SLP, "depth_anything.hip": NO_SLP + ["-fno-honor-nans"], "depth_temporal.hip": NO_SLP, "conv3_lds.hip": NO_SLP,
                "transnetv2.hip": NO_SLP, "sod_v1.hip": NO_SLP, "superpoint.hip": NO_SLP, "outpaint.hip": NO_SLP,
-               "jpeg.hip": NO_SLP, "cliqa.hip": NO_SLP, "png.hip": NO_SLP, "png_planes.hip": NO_SLP,
+               "jpeg.hip": NO_SLP, "cliqa.hip": NO_SLP, "png.hip": NO_SLP, "png_planes.hip": NO_SLP, "wgmlp.hip": NO_SLP,
                # hdr.hip: the reference's fp32 expressions operation by operation (its error is the tests' yardstick)
                "hdr.hip": ["-ffp-contract=off"] + NO_SLP,
                # pixfmt.hip: every multiply and add is one rounding, in the order tests/pixfmt_ref.py states them

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "packed_layers.h"
+#include "swin_unet_v2_kernels.h"
 #include "wa_block_host.h"
 
 namespace nunif {
@@ -261,6 +262,36 @@ __global__ void __launch_bounds__(256) v2_source_residual_kernel(const float *__
             }
     const float v = acc + r[i] * scale_bias[0];
     z[i] = clamp01 ? fminf(fmaxf(v, 0.f), 1.f) : v;
+}
+
+// ---- the shortcut / GLU / head kernels above for the other engine of this family of layers (wgmlp.hip; swin_unet_v2_kernels.h) ----
+int launch_v2_glu(const f16 *in, f16 *out, long M, int m, hipStream_t s) {
+    ProfScope ps("v2_glu_kernel", s, 0.0, (double)M * m * 6.0);
+    v2_glu_kernel<<<(unsigned)((M * (m / 8) + 255) / 256), 256, 0, s>>>(in, out, M, m);
+    NUNIF_LAUNCH_CHECK();
+    return NUNIF_HIP_OK;
+}
+int launch_v2_down_shortcut(const f16 *x, f16 *out, int B, int H, int W, int C, int C2, hipStream_t s) {
+    const long n = (long)B * (H / 2) * (W / 2) * C2;
+    ProfScope ps("v2_down_shortcut_kernel", s, 0.0, (double)n * 6.0);
+    v2_down_shortcut_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(x, out, B, H, W, C, C2);
+    NUNIF_LAUNCH_CHECK();
+    return NUNIF_HIP_OK;
+}
+int launch_v2_up_shortcut(const f16 *low, const f16 *skip, f16 *out, int B, int H, int W, int C, int C2, hipStream_t s) {
+    const long n = (long)B * H * W * C;
+    ProfScope ps("v2_up_shortcut_kernel", s, 0.0, (double)n * 6.0);
+    v2_up_shortcut_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(low, skip, out, B, H, W, C, C2);
+    NUNIF_LAUNCH_CHECK();
+    return NUNIF_HIP_OK;
+}
+int launch_v2_source_residual(const float *src, const float *r, const float *w, const float *scale_bias, float *z, int B, int T, int s_,
+                              int O, int clamp01, hipStream_t s) {
+    const long n = (long)B * 3 * O * O;
+    ProfScope ps("v2_source_residual_kernel", s, 54.0 * (double)n, (double)n * 8.0);
+    v2_source_residual_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(src, r, w, scale_bias, z, B, T, s_, O, clamp01);
+    NUNIF_LAUNCH_CHECK();
+    return NUNIF_HIP_OK;
 }
 
 }  // namespace nunif

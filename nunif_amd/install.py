@@ -111,7 +111,7 @@ _CONSUMER_ROOTS = ("nunif", "waifu2x", "iw3", "stlizer", "cliqa")
 # modules that register models (imported on both sides so that the registries are complete before they are merged)
 _MODEL_MODULES = [("waifu2x.models", ["nunif_amd.waifu2x.models.swin_unet", "nunif_amd.waifu2x.models.cunet",
                                       "nunif_amd.waifu2x.models.vgg_7", "nunif_amd.waifu2x.models.upconv_7",
-                                      "nunif_amd.waifu2x.models.swin_unet_v2"]),
+                                      "nunif_amd.waifu2x.models.swin_unet_v2", "nunif_amd.waifu2x.models.wgmlp"]),
                   ("iw3.models", ["nunif_amd.iw3.models"]),
                   # stlizer.light_outpaint_v1 (pass 4 of stlizer/multipass_pipeline.py:380 loads it through load_model); the
                   # reference package imports only torch and nunif.*: strict=True stays independent of PyAV

@@ -196,6 +196,80 @@ def swin_unet_v2_state_dict(seed, scale_factor=2, base_dim=None, lv1_mlp_ratio=2
     return sd
 
 
+def wgmlp_state_dict(seed, regime="benign"):
+    """Seeded random weights of ``waifu2x.wgmlp_4x`` in the reference's key layout and shapes (waifu2x/models/wgmlp.py WGMLPBase
+    :298-331, base_dim 128).
+
+    The reference's own initialisation would hide two kinds of mistake, so it is not kept: ``proj_spatial.weight`` is about
+    1e-3 / C there (the token mixing would be invisible: v' = bias) and ``scale_bias`` is 0 (the whole net would be invisible).  Here
+    the mixing matrix is N(0, 1 / 8) per entry with biases 1 + N(0, 0.3) (the 64-token sum and the bias are both O(1)), ``scale_bias``
+    is drawn from [0.5, 1] with the image head scaled so that source + scale_bias * residual stays a picture, norm weights are
+    1 + N(0, 0.1) and every bias N(0, 0.02).  Otherwise the conditioning of ``swin_unet_v2_state_dict``: xavier / kaiming magnitudes
+    with the residual-branch outputs (proj_out, conv_mlp.w2, the PatchDown / PatchUp convs beside their shortcuts) damped so that
+    the stream rms stays O(1) over the 9 blocks, and the resampling conv = nearest neighbour + N(0, 0.02).
+    ``regime="hot"``: branches not damped, a wider mixing matrix and HOT_OUTLIERS channels of ``patch`` scaled by HOT_OUTLIER_GAIN
+    (see HOT_TABLE_STD above); for the relative criterion only."""
+    assert regime in ("benign", "hot")
+    hot = regime == "hot"
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    C, C2 = 128, 256
+
+    def normal(shape, std):
+        return torch.randn(shape, generator=g) * std
+
+    def lin(key, cin, cout, gain=1.0):
+        bound = gain * math.sqrt(6.0 / (cin + cout))
+        sd[key + ".weight"] = (torch.rand((cout, cin), generator=g) * 2 - 1) * bound
+        sd[key + ".bias"] = normal((cout,), 0.02)
+
+    def conv(key, cin, cout, k, gain=1.0):
+        sd[key + ".weight"] = normal((cout, cin, k, k), gain * math.sqrt(2.0 / (cin * k * k)))
+        sd[key + ".bias"] = normal((cout,), 0.02)
+
+    def block(p, dim, conv_mlp=True):
+        lin(p + "gmlp.gmlp.proj_in", dim, dim * 2)
+        sd[p + "gmlp.gmlp.proj_spatial.weight"] = normal((64, 64, 1), 0.3 if hot else 0.125)
+        sd[p + "gmlp.gmlp.proj_spatial.bias"] = 1.0 + normal((64,), 0.3)
+        lin(p + "gmlp.gmlp.proj_out", dim, dim, 1.0 if hot else 0.5)
+        sd[p + "norm1.weight"] = 1.0 + normal((dim,), 0.1)
+        sd[p + "norm2.weight"] = 1.0 + normal((dim,), 0.1)
+        conv(p + "conv_mlp.w1", dim, dim * 2, 1)
+        if conv_mlp:
+            conv(p + "conv_mlp.w2", dim, dim, 3, 0.7 if hot else 0.25)
+        else:
+            conv(p + "conv_mlp.w2", dim * 2, dim, 1, 0.4 if hot else 0.2)
+
+    P = "unet."
+    conv(P + "ir.patch", 3, 16, 3)
+    conv(P + "ir.overscan.conv1", 16, 16, 3)
+    conv(P + "ir.overscan.conv2", 16, 8, 3)
+    conv(P + "ir.overscan.conv3", 8, 8, 3)
+    conv(P + "ir.overscan.fuse.0", 32, 16, 3)
+    conv(P + "ir.overscan.fuse.2", 16, 16, 1)
+    conv(P + "ir.fusion", 32, 16, 3)
+    conv(P + "patch", 16, C, 3)
+    if hot:
+        for ch in HOT_OUTLIERS:
+            sd[P + "patch.weight"][ch] *= HOT_OUTLIER_GAIN
+            sd[P + "patch.bias"][ch] *= HOT_OUTLIER_GAIN
+    for i in range(2):
+        block(f"{P}wgmlp1.blocks.{i}.", C)
+    conv(P + "down1.conv", C, C2, 2, 0.5)
+    for i in range(4):
+        block(f"{P}wgmlp2.blocks.{i}.", C2)
+    conv(P + "up1.proj", C2, C * 4, 1, 0.5)
+    for i in range(3):
+        block(f"{P}wgmlp3.blocks.{i}.", C, conv_mlp=i < 2)
+    conv(P + "to_residual_image.proj", C, 48, 1, 0.002 if hot else 0.02)
+    sd[P + "to_image.scale_bias"] = 0.5 + 0.5 * torch.rand((1,), generator=g)
+    w = normal((48, 3, 3, 3), 0.02)
+    for c in range(3):
+        w[c * 16:(c + 1) * 16, c, 1, 1] += 1.0
+    sd[P + "to_image.resampling.weight"] = w
+    return sd
+
+
 def cunet_state_dict(seed, up=False, in_channels=3, out_channels=3, regime="benign"):
     """Seeded weights in the reference's key layout; biases non-zero; the two image heads are scaled so that z1 and
     the final image sit inside [0,1] like a trained net's (same reasoning as oracle.swin_unet.random_state_dict).
