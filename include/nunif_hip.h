@@ -196,6 +196,30 @@ int nunif_hip_swin_unet_v2_create(const nunif_tensor_desc *tensors, int32_t n_te
 void nunif_hip_swin_unet_v2_destroy(nunif_swin_unet_v2 *handle);
 int nunif_hip_swin_unet_v2_forward(nunif_swin_unet_v2 *handle, const float *x, float *z, int32_t batch, int32_t tile_size,
                                    int32_t clamp01, void *stream);
+/* tests: forward that also stores its intermediate maps as fp32, concatenated in the order they are produced (each copied by a
+ * launch right after the one that produced it; z is what forward writes).  With S = T - 16, C = base_dim, C2 = the level-2 width,
+ * and per WAC block two maps of the block's own resolution and width, "att" (the window attention's output, before head_proj) and
+ * then the block's output:
+ *   ir.path2.2 att, out   [B,T/2,T/2,64]   x 2
+ *   ir.path2.3 att, out   [B,T/2,T/2,64]   x 2
+ *   ir                    [B,T,T,32]       (path1 | pixel_shuffle(path2))
+ *   patch                 [B,S,S,C]        (conv, crop 7, LeakyReLU)
+ *   wac1.blocks.i att, out [B,S,S,C]       x 2 per block
+ *   down1                 [B,S/2,S/2,C2]   (shortcut + conv)
+ *   wac2.blocks.i att, out [B,S/2,S/2,C2]  x 2 per block
+ *   up1                   [B,S,S,C]        (shortcut + proj + skip)
+ *   wac3.blocks.i att, out [B,S,S,C]       x 2 per block
+ *   residual              [B,3,O,O]        (planar like z, O = (S - 2) s: the fp32 residual image before the source residual)
+ * All but the last are channels-last. */
+int nunif_hip_swin_unet_v2_debug_taps(nunif_swin_unet_v2 *handle, const float *x, float *z, float *taps, int32_t batch,
+                                      int32_t tile_size, int32_t clamp01, void *stream);
+/* tests: the window attention of a WAC block alone (the kernel and the launch of the forward) on caller-supplied device maps.
+ * qkv [B,H,W,3C] fp16 in the kernel's own convention (q already multiplied by 32^-0.5 log2 e), btab [ws^2][ws^2] f32 (the score
+ * bias [query][key], multiplied by log2 e), bqkv [3C] f32 (q / k / v of a token in the zero padding of a shifted window, q scaled
+ * like the map's) -> att [B,H,W,C] fp16.  ws = 8 or 6, heads of 32 channels, H and W multiples of ws; shift != 0: windows
+ * offset by -ws/2 with zero-padded tokens. */
+int nunif_hip_swin_unet_v2_debug_wattn(const void *qkv, const float *btab, const float *bqkv, void *att, int32_t batch,
+                                       int32_t height, int32_t width, int32_t channels, int32_t window, int32_t shift, void *stream);
 
 /* waifu2x "waifu2x.wgmlp_4x" (waifu2x/models/wgmlp.py WGMLPBase :298-353, WGMLP4x :441-470): IR / Overscan stem :126-173, window-gMLP
  * + GLU conv-MLP blocks :75-123 (nunif/modules/attention.py GMLP :621-651, WindowGMLP2d :654-693: 8 x 8 windows, zero-padded

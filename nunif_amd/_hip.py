@@ -108,6 +108,8 @@ SIGNATURES = {
     "nunif_hip_swin_unet_v2_create": (c_int32, [ctypes.POINTER(TensorDesc), c_int32, c_int32, ctypes.POINTER(c_void_p)]),
     "nunif_hip_swin_unet_v2_destroy": (None, [c_void_p]),
     "nunif_hip_swin_unet_v2_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "nunif_hip_swin_unet_v2_debug_taps": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "nunif_hip_swin_unet_v2_debug_wattn": (c_int32, [c_void_p] * 4 + [c_int32] * 6 + [c_void_p]),
     "nunif_hip_wgmlp_create": (c_int32, [ctypes.POINTER(TensorDesc), c_int32, ctypes.POINTER(c_void_p)]),
     "nunif_hip_wgmlp_destroy": (None, [c_void_p]),
     "nunif_hip_wgmlp_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),

@@ -192,6 +192,12 @@ __global__ void __launch_bounds__(256) v2_wattn_kernel(V2AttnArgs a) {
     }
 }
 
+// ---- tests: an fp32 copy of an fp16 map (nunif_hip_swin_unet_v2_debug_taps) ---------------------------------------------------------
+__global__ void __launch_bounds__(256) v2_f16_to_f32_kernel(const f16 *__restrict__ in, float *__restrict__ out, long n) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = (float)in[i];
+}
+
 // ---- F.glu(dim = channels): out[c] = in[c] * sigmoid(in[m + c]) -----------------------------------------------------------------
 __global__ void __launch_bounds__(256) v2_glu_kernel(const f16 *__restrict__ in, f16 *__restrict__ out, long M, int m) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;           // (token, group of 8 channels)
@@ -387,27 +393,44 @@ int launch_wattn_t(const V2AttnArgs &a, hipStream_t s) {
     return NUNIF_HIP_OK;
 }
 
-// one WACBlock on the NHWC map *px ([B,S,S,C]); the result ends up in *px again (the buffers swap for the 3x3 form)
-int run_wac(nunif_swin_unet_v2 *h, const WacBlock &bk, f16 **px, f16 **pother, int B, int S, hipStream_t s) {
+// the window attention of a WAC block on the map qkv [B,H,W,3C] -> att [B,H,W,C]: what run_wac launches, and what the tests launch
+// on maps of their own (nunif_hip_swin_unet_v2_debug_wattn)
+int run_wattn(const f16 *qkv, f16 *att, const float *btab, const float *bqkv, int B, int H, int W, int C, int ws, int shift,
+              hipStream_t s) {
+    NUNIF_REQUIRE(C > 0 && C % 32 == 0, "swin_unet_v2: %d channels are not heads of 32", C);
+    NUNIF_REQUIRE(ws > 0 && H % ws == 0 && W % ws == 0 && (!shift || ws % 2 == 0), "swin_unet_v2: map %d x %d not a multiple of window %d",
+                  H, W, ws);
+    V2AttnArgs a;
+    a.qkv = qkv; a.att = att; a.btab = btab; a.bqkv = bqkv; a.B = B; a.H = H; a.W = W; a.C = C; a.heads = C / 32;
+    a.pad = shift ? ws / 2 : 0;
+    ProfScope ps("v2_wattn_kernel", s, 4.0 * (double)B * H * W * ws * ws * C, (double)B * H * W * C * 8.0);
+    const int rc = ws == 8 ? launch_wattn_t<8>(a, s) : ws == 6 ? launch_wattn_t<6>(a, s) : NUNIF_HIP_EUNSUPPORTED;
+    if (rc == NUNIF_HIP_EUNSUPPORTED) set_error("swin_unet_v2: window %d unsupported (8, 6)", ws);
+    return rc;
+}
+
+// tests: an fp32 copy of the fp16 map x [n] at *tap, which then moves on by n (no taps: nothing)
+int tap_out(const f16 *x, long n, float **tap, hipStream_t s) {
+    if (!tap || !*tap) return NUNIF_HIP_OK;
+    v2_f16_to_f32_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(x, *tap, n);
+    NUNIF_LAUNCH_CHECK();
+    *tap += n;
+    return NUNIF_HIP_OK;
+}
+
+// one WACBlock on the NHWC map *px ([B,S,S,C]); the result ends up in *px again (the buffers swap for the 3x3 form).
+// taps: the attention's output (it lives in tmpA until the GLU overwrites it), then the block's
+int run_wac(nunif_swin_unet_v2 *h, const WacBlock &bk, f16 **px, f16 **pother, int B, int S, float **taps, hipStream_t s) {
     f16 *x = *px, *other = *pother;
     const int C = bk.C;
     const long M = (long)B * S * S;
     f16 *tmpA = (f16 *)h->tmpA.p, *tmpB = (f16 *)h->tmpB.p, *qkv = (f16 *)h->qkv.p;
-    NUNIF_REQUIRE(S % bk.ws == 0 && (!bk.shift || bk.ws % 2 == 0), "swin_unet_v2: map %d not a multiple of window %d", S, bk.ws);
     int rc;
     // x = x + head_proj(window_mha(qkv_proj(layer_norm(x))))          (WACBlock.forward :95-96)
     if ((rc = launch_layernorm_nobias(x, tmpA, bk.norm, M, C, s))) return rc;
     if ((rc = run_lin(bk.qkv, tmpA, B, S, 0, 0.f, nullptr, qkv, s, "v2_qkv"))) return rc;
-    {
-        V2AttnArgs a;
-        a.qkv = qkv; a.att = tmpA; a.btab = bk.btab; a.bqkv = bk.bqkv; a.B = B; a.H = S; a.W = S; a.C = C; a.heads = bk.heads;
-        a.pad = bk.shift ? bk.ws / 2 : 0;
-        ProfScope ps("v2_wattn_kernel", s, 4.0 * (double)M * bk.ws * bk.ws * C, (double)M * C * 8.0);
-        if ((rc = bk.ws == 8 ? launch_wattn_t<8>(a, s) : bk.ws == 6 ? launch_wattn_t<6>(a, s) : NUNIF_HIP_EUNSUPPORTED)) {
-            if (rc == NUNIF_HIP_EUNSUPPORTED) set_error("swin_unet_v2: window %d unsupported (8, 6)", bk.ws);
-            return rc;
-        }
-    }
+    NUNIF_REQUIRE(bk.heads * 32 == C, "swin_unet_v2: %d heads for %d channels", bk.heads, C);
+    if ((rc = run_wattn(qkv, tmpA, bk.btab, bk.bqkv, B, S, S, C, bk.ws, bk.shift, s)) || (rc = tap_out(tmpA, M * C, taps, s))) return rc;
     if ((rc = run_lin(bk.proj, tmpA, B, S, 0, 0.f, x, x, s, "v2_proj"))) return rc;
     if (bk.glu) {
         // x = x + leaky_relu(conv3x3(replicate_pad(glu(w1 x))), 0.2)      (GLUConvMLP :27-35)
@@ -424,7 +447,7 @@ int run_wac(nunif_swin_unet_v2 *h, const WacBlock &bk, f16 **px, f16 **pother, i
         if ((rc = run_lin(bk.w1, x, B, S, 2, 0.1f, nullptr, tmpB, s, "v2_mlp_w1"))) return rc;
         if ((rc = run_lin(bk.w2lin, tmpB, B, S, 0, 0.f, x, x, s, "v2_mlp_w2"))) return rc;
     }
-    return NUNIF_HIP_OK;
+    return tap_out(*px, M * C, taps, s);
 }
 
 }  // namespace
@@ -519,14 +542,14 @@ extern "C" void nunif_hip_swin_unet_v2_destroy(nunif_swin_unet_v2 *h) {
     delete h;
 }
 
-// x: [B,3,T,T] f32 -> z: [B,3,O,O] f32 with O = T*s - 2*offset (offset = 9 s): SwinUNet{1,2,4}xV2.forward in eval mode
-extern "C" int nunif_hip_swin_unet_v2_forward(nunif_swin_unet_v2 *h, const float *x, float *z, int32_t B, int32_t T,
-                                              int32_t clamp01, void *stream) {
+// x: [B,3,T,T] f32 -> z: [B,3,O,O] f32 with O = T*s - 2*offset (offset = 9 s): SwinUNet{1,2,4}xV2.forward in eval mode.
+// taps: nullptr, or where the fp32 copies of the intermediate maps go, in the order nunif_hip.h lists
+static int v2_forward(nunif_swin_unet_v2 *h, const float *x, float *z, int B, int T, int clamp01, float *taps, hipStream_t s) {
     NUNIF_REQUIRE(h && x && z && B > 0, "swin_unet_v2_forward: bad argument");
     const int S = T - 16, C = h->C, C2 = h->C2, sc = h->scale;
     NUNIF_REQUIRE(T % 2 == 0 && (T / 2) % 8 == 0 && S > 0 && S % 24 == 0 && (S / 2) % 8 == 0,
                   "tile_size %d is not valid for swin_unet_v2 (T / 2 multiple of 8, T - 16 multiple of 48)", T);
-    hipStream_t s = (hipStream_t)stream;
+    float **tp = taps ? &taps : nullptr;
     const size_t e2 = sizeof(f16);
     const long M1 = (long)B * S * S, M2 = M1 / 4, Mt = (long)B * T * T, Mh = Mt / 4;
     const int midmax = std::max({C * 2, C2 * 2, 64});
@@ -546,20 +569,21 @@ extern "C" int nunif_hip_swin_unet_v2_forward(nunif_swin_unet_v2 *h, const float
     NUNIF_LAUNCH_CHECK();
     {
         f16 *cur = irf, *other = irf2;
-        if ((rc = run_wac(h, h->ir_blk[0], &cur, &other, B, T / 2, s)) || (rc = run_wac(h, h->ir_blk[1], &cur, &other, B, T / 2, s)))
+        if ((rc = run_wac(h, h->ir_blk[0], &cur, &other, B, T / 2, tp, s)) || (rc = run_wac(h, h->ir_blk[1], &cur, &other, B, T / 2, tp, s)))
             return rc;
         v2_ir_shuffle_kernel<<<(unsigned)((Mt + 255) / 256), 256, 0, s>>>(cur, ir, B, T);
         NUNIF_LAUNCH_CHECK();
+        if ((rc = tap_out(ir, Mt * 32, tp, s))) return rc;
     }
     // ---- patch: 3x3 VALID 32 -> C, crop 7, LeakyReLU(0.2) (:339-341): conv rows / cols [7, 7 + S) of the (T - 2)^2 result ------
     f16 *f1 = (f16 *)h->f1.p, *f1b = (f16 *)h->f1b.p;
     {
         ConvArgs c = conv_args(h->patch, ir + ((long)7 * T + 7) * 32, B, T, T, f1);
         c.Ho = S; c.Wo = S; c.act = 2; c.slope = 0.2f;
-        if ((rc = launch_conv(c, s))) return rc;
+        if ((rc = launch_conv(c, s)) || (rc = tap_out(f1, M1 * C, tp, s))) return rc;
     }
     for (auto &bk : h->wac1)
-        if ((rc = run_wac(h, bk, &f1, &f1b, B, S, s))) return rc;
+        if ((rc = run_wac(h, bk, &f1, &f1b, B, S, tp, s))) return rc;
     // the encoder's level-1 result is the U-Net skip: keep it where the decoder does not write
     f16 *skip = f1;
     f16 *dec = f1 == (f16 *)h->f1.p ? (f16 *)h->skip.p : (f16 *)h->f1.p;       // a level-1 buffer other than skip / f1b
@@ -570,22 +594,22 @@ extern "C" int nunif_hip_swin_unet_v2_forward(nunif_swin_unet_v2 *h, const float
     {
         GemmArgs g = gemm_map_args(h->down1, skip, B, S, S, C, S / 2, S / 2, f2, 2, 2);
         g.act = 2; g.slope = 0.2f; g.res = f2;
-        if ((rc = launch_gemm(g, s, "v2_down1"))) return rc;
+        if ((rc = launch_gemm(g, s, "v2_down1")) || (rc = tap_out(f2, M2 * C2, tp, s))) return rc;
     }
     for (auto &bk : h->wac2)
-        if ((rc = run_wac(h, bk, &f2, &f2b, B, S / 2, s))) return rc;
+        if ((rc = run_wac(h, bk, &f2, &f2b, B, S / 2, tp, s))) return rc;
     // ---- up1 (:186-192) + skip (:348): shortcut + skip first, then proj + LeakyReLU(0.2) + pixel shuffle accumulates onto it -------
     v2_up_shortcut_kernel<<<(unsigned)((M1 * C + 255) / 256), 256, 0, s>>>(f2, skip, dec, B, S, S, C, C2);
     NUNIF_LAUNCH_CHECK();
     {
         GemmArgs g = gemm_map_args(h->up1, f2, B, S / 2, S / 2, C2, S / 2, S / 2, dec);
         g.mode = 1; g.act = 2; g.slope = 0.2f; g.res = dec; g.ldo = C;
-        if ((rc = launch_gemm(g, s, "v2_up1"))) return rc;
+        if ((rc = launch_gemm(g, s, "v2_up1")) || (rc = tap_out(dec, M1 * C, tp, s))) return rc;
     }
     f16 *other = f1b;
     if (other == dec || other == skip) other = (f16 *)h->skip.p == dec || (f16 *)h->skip.p == skip ? (f16 *)h->f1.p : (f16 *)h->skip.p;
     for (auto &bk : h->wac3)
-        if ((rc = run_wac(h, bk, &dec, &other, B, S, s))) return rc;
+        if ((rc = run_wac(h, bk, &dec, &other, B, S, tp, s))) return rc;
     // ---- to_residual_image (:199-213): 1x1 conv, pixel shuffle, crop `scale`; then the source residual + clamp --------------------
     const int O = S * sc - 2 * sc;
     {
@@ -594,8 +618,26 @@ extern "C" int nunif_hip_swin_unet_v2_forward(nunif_swin_unet_v2 *h, const float
         if ((rc = launch_gemm(g, s, "v2_to_image"))) return rc;
     }
     const long n_out = (long)B * 3 * O * O;
+    if (taps) NUNIF_HIP_CHECK(hipMemcpyAsync(taps, h->rimg.p, (size_t)n_out * sizeof(float), hipMemcpyDeviceToDevice, s));
     v2_source_residual_kernel<<<(unsigned)((n_out + 255) / 256), 256, 0, s>>>(x, (const float *)h->rimg.p, h->res_w, h->scale_bias, z,
                                                                                B, T, sc, O, clamp01);
     NUNIF_LAUNCH_CHECK();
     return NUNIF_HIP_OK;
+}
+
+extern "C" int nunif_hip_swin_unet_v2_forward(nunif_swin_unet_v2 *h, const float *x, float *z, int32_t B, int32_t T,
+                                              int32_t clamp01, void *stream) {
+    return v2_forward(h, x, z, B, T, clamp01, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int nunif_hip_swin_unet_v2_debug_taps(nunif_swin_unet_v2 *h, const float *x, float *z, float *taps, int32_t B, int32_t T,
+                                                 int32_t clamp01, void *stream) {
+    NUNIF_REQUIRE(taps, "swin_unet_v2_debug_taps: NULL taps");
+    return v2_forward(h, x, z, B, T, clamp01, taps, (hipStream_t)stream);
+}
+
+extern "C" int nunif_hip_swin_unet_v2_debug_wattn(const void *qkv, const float *btab, const float *bqkv, void *att, int32_t B, int32_t H,
+                                                  int32_t W, int32_t C, int32_t ws, int32_t shift, void *stream) {
+    NUNIF_REQUIRE(qkv && btab && bqkv && att && B > 0 && H > 0 && W > 0, "swin_unet_v2_debug_wattn: bad argument");
+    return run_wattn((const f16 *)qkv, (f16 *)att, btab, bqkv, B, H, W, C, ws, shift ? 1 : 0, (hipStream_t)stream);
 }

@@ -87,6 +87,9 @@ class HipSwinUNetV2Engine(HipEngine):
         super().__init__(device, state_dict, "nunif_hip_swin_unet_v2_create", "nunif_hip_swin_unet_v2_destroy", scale_factor,
                          label="swin_unet_v2", skip=[k for k in state_dict if k.endswith("relative_bias.delta")])
         self.scale_factor = scale_factor
+        self.dims = (state_dict["unet.patch.weight"].shape[0], state_dict["unet.down1.conv.weight"].shape[0])
+        self.blocks = tuple(sum(1 for k in state_dict if k.startswith(f"unet.{g}.") and k.endswith("mha.mha.qkv_proj.weight"))
+                            for g in ("wac1", "wac2", "wac3"))
 
     def forward(self, x, clamp=True):
         B, C, T, T2 = x.shape
@@ -97,6 +100,59 @@ class HipSwinUNetV2Engine(HipEngine):
         self.call(_hip.lib().nunif_hip_swin_unet_v2_forward, self.handle, ctypes.c_void_p(x.data_ptr()),
                   ctypes.c_void_p(z.data_ptr()), B, T, 1 if clamp else 0)
         return z
+
+    def tap_layout(self, B, T):
+        """[(name, shape)] of the maps of ``nunif_hip_swin_unet_v2_debug_taps`` in its order (include/nunif_hip.h).  A WAC block gives
+        ``<block>.att`` (the attention before head_proj) and ``<block>``; all NHWC but ``residual`` [B,3,O,O]."""
+        (C, C2), (n1, n2, n3), S = self.dims, self.blocks, T - 16
+        out = []
+
+        def wac(name, shape):
+            out.extend([(name + ".att", shape), (name, shape)])
+        wac("ir.path2.2", (B, T // 2, T // 2, 64))
+        wac("ir.path2.3", (B, T // 2, T // 2, 64))
+        out.extend([("ir", (B, T, T, 32)), ("patch", (B, S, S, C))])
+        for i in range(n1):
+            wac(f"wac1.blocks.{i}", (B, S, S, C))
+        out.append(("down1", (B, S // 2, S // 2, C2)))
+        for i in range(n2):
+            wac(f"wac2.blocks.{i}", (B, S // 2, S // 2, C2))
+        out.append(("up1", (B, S, S, C)))
+        for i in range(n3):
+            wac(f"wac3.blocks.{i}", (B, S, S, C))
+        o = (T - 18) * self.scale_factor
+        out.append(("residual", (B, 3, o, o)))
+        return out
+
+    def debug_taps(self, x, clamp=True):
+        """``forward`` that also returns its intermediate maps as fp32 (tests only; ``nunif_hip_swin_unet_v2_debug_taps``):
+        (z, {name: map}) with the names and shapes of ``tap_layout``."""
+        B, C, T, T2 = x.shape
+        assert C == 3 and T == T2
+        o = (T - 18) * self.scale_factor
+        layout = self.tap_layout(B, T)
+        sizes = [s[0] * s[1] * s[2] * s[3] for _, s in layout]
+        z = torch.empty((B, 3, o, o), dtype=torch.float32, device=self.device)
+        flat = torch.empty(sum(sizes), dtype=torch.float32, device=self.device)
+        self.call(_hip.lib().nunif_hip_swin_unet_v2_debug_taps, self.handle, ctypes.c_void_p(x.data_ptr()),
+                  ctypes.c_void_p(z.data_ptr()), ctypes.c_void_p(flat.data_ptr()), B, T, 1 if clamp else 0)
+        return z, {n: t.reshape(s) for (n, s), t in zip(layout, flat.split(sizes))}
+
+
+def debug_wattn(qkv, btab, bqkv, ws, shift):
+    """The window attention kernel of a WAC block alone (tests only; ``nunif_hip_swin_unet_v2_debug_wattn``): qkv [B,H,W,3C] fp16 in
+    the kernel's convention (q scaled by 32^-0.5 log2 e), btab [ws^2, ws^2] fp32 (log2 e scaled), bqkv [3C] fp32 -> att [B,H,W,C]
+    fp16, on qkv's device and torch's current stream."""
+    B, H, W, C3 = qkv.shape
+    assert qkv.dtype == torch.float16 and qkv.is_contiguous() and qkv.is_cuda and C3 % 3 == 0
+    assert btab.dtype == bqkv.dtype == torch.float32 and btab.is_contiguous() and bqkv.is_contiguous()
+    assert btab.device == bqkv.device == qkv.device and btab.numel() == ws ** 4 and bqkv.numel() == C3
+    att = torch.empty((B, H, W, C3 // 3), dtype=torch.float16, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        _hip.check(_hip.lib().nunif_hip_swin_unet_v2_debug_wattn(
+            ctypes.c_void_p(qkv.data_ptr()), ctypes.c_void_p(btab.data_ptr()), ctypes.c_void_p(bqkv.data_ptr()),
+            ctypes.c_void_p(att.data_ptr()), B, H, W, C3 // 3, ws, 1 if shift else 0, _hip.current_stream_ptr(qkv.device)))
+    return att
 
 
 class _HipSwinUNetV2Model(_FlatWeightsModel):

@@ -17,7 +17,13 @@ import torch.nn.functional as F
 from . import row_flow_v3 as RF
 
 
-def window_mha(sd, p, x, ws, bias, num_heads, shift, norm_weight):
+def _tap(taps, name, t, nchw=True):
+    """taps[name] = the map as the engine's debug entry stores it: channels-last (``nchw``: permute), or as it is."""
+    if taps is not None:
+        taps[name] = (t.permute(0, 2, 3, 1) if nchw else t).contiguous()
+
+
+def window_mha(sd, p, x, ws, bias, num_heads, shift, norm_weight, taps=None, name=None):
     pad = ws // 2 if shift else 0
     if pad:
         x = F.pad(x, (pad, pad, pad, pad), mode="constant", value=0)
@@ -32,21 +38,28 @@ def window_mha(sd, p, x, ws, bias, num_heads, shift, norm_weight):
         return z.view(-1, n, num_heads, hd).permute(0, 2, 1, 3)
     s = (heads(q) @ heads(k).transpose(-1, -2)) * (1.0 / math.sqrt(hd)) + bias
     o = (torch.softmax(s, dim=-1) @ heads(v)).permute(0, 2, 1, 3).reshape(-1, n, C)
+    if taps is not None:                                           # the attention before head_proj, on the tokens inside the map
+        a = o.reshape(B, oh, ow, ws, ws, C).permute(0, 1, 3, 2, 4, 5).reshape(B, H, W, C)
+        _tap(taps, name + ".att", a[:, pad:H - pad, pad:W - pad] if pad else a, nchw=False)
     o = F.linear(o, sd[p + "mha.head_proj.weight"], sd[p + "mha.head_proj.bias"])
     o = o.reshape(B, oh, ow, ws, ws, C).permute(0, 5, 1, 3, 2, 4).reshape(B, C, H, W)                    # bnc_to_bchw
     return o[:, :, pad:H - pad, pad:W - pad] if pad else o
 
 
-def wac_block(sd, p, x, num_heads, ws, shift, conv_mlp=True):
+def wac_block(sd, p, x, num_heads, ws, shift, conv_mlp=True, taps=None):
+    """``taps``: a dict that gets ``<block>.att`` and ``<block>`` (the block's output), named without the ``unet.`` prefix."""
+    name = p[len("unet."):-1] if p.startswith("unet.") else p[:-1]
     bias = RF.window_score_bias(sd, p + "relative_bias.", (ws, ws))
-    x = x + window_mha(sd, p + "mha.", x, ws, bias, num_heads, shift, sd[p + "norm.weight"])
+    x = x + window_mha(sd, p + "mha.", x, ws, bias, num_heads, shift, sd[p + "norm.weight"], taps, name)
     z = F.conv2d(x, sd[p + "conv_mlp.w1.weight"], sd[p + "conv_mlp.w1.bias"])
     if conv_mlp:                                                   # GLUConvMLP
         z = F.glu(z, dim=1)
         z = F.conv2d(F.pad(z, (1, 1, 1, 1), mode="replicate"), sd[p + "conv_mlp.w2.weight"], sd[p + "conv_mlp.w2.bias"])
-        return x + F.leaky_relu(z, 0.2)
-    z = F.conv2d(F.leaky_relu(z, 0.1), sd[p + "conv_mlp.w2.weight"], sd[p + "conv_mlp.w2.bias"])          # MLP
-    return x + z
+        x = x + F.leaky_relu(z, 0.2)
+    else:
+        x = x + F.conv2d(F.leaky_relu(z, 0.1), sd[p + "conv_mlp.w2.weight"], sd[p + "conv_mlp.w2.bias"])  # MLP
+    _tap(taps, name, x)
+    return x
 
 
 def shift_config(n):
@@ -57,40 +70,48 @@ def n_blocks(sd, p):
     return sum(1 for k in sd if k.startswith(p) and k.endswith("mha.mha.qkv_proj.weight"))
 
 
-def model_forward(sd, x, scale, raw=False):
-    """SwinUNet{1,2,4}xV2.forward in eval mode: x [B,3,T,T] -> clamp([B,3,T*s - 2*offset, ...])."""
+def model_forward(sd, x, scale, raw=False, taps=None):
+    """SwinUNet{1,2,4}xV2.forward in eval mode: x [B,3,T,T] -> clamp([B,3,T*s - 2*offset, ...]).
+    ``taps``: a dict to fill with the maps of the engine's ``nunif_hip_swin_unet_v2_debug_taps`` under its names, channels-last:
+    ``ir.path2.2`` / ``ir.path2.3``, ``ir``, ``patch``, ``wac{1,2,3}.blocks.i`` (each block with its ``.att``), ``down1``, ``up1``
+    (with the skip), and ``residual`` [B,3,O,O], the cropped residual image before the source residual."""
     u = "unet."
     src = x
     x1 = F.leaky_relu(F.conv2d(F.pad(x, (1, 1, 1, 1), mode="replicate"), sd[u + "ir.path1.0.weight"], sd[u + "ir.path1.0.bias"]), 0.2)
     x2 = F.conv2d(F.pixel_unshuffle(x, 2), sd[u + "ir.path2.1.weight"], sd[u + "ir.path2.1.bias"])
-    x2 = wac_block(sd, u + "ir.path2.2.", x2, 2, 8, True)
-    x2 = wac_block(sd, u + "ir.path2.3.", x2, 2, 8, False)
+    x2 = wac_block(sd, u + "ir.path2.2.", x2, 2, 8, True, taps=taps)
+    x2 = wac_block(sd, u + "ir.path2.3.", x2, 2, 8, False, taps=taps)
     x = torch.cat([x1, F.pixel_shuffle(x2, 2)], dim=1)
+    _tap(taps, "ir", x)
     x = F.conv2d(x, sd[u + "patch.weight"], sd[u + "patch.bias"])
     x = F.leaky_relu(x[:, :, 7:-7, 7:-7], 0.2)
+    _tap(taps, "patch", x)
     C = x.shape[1]
     C2 = sd[u + "down1.conv.weight"].shape[0]
     heads, heads2 = max(C // 32, 2), max(C2 // 32, 2)
     n1, n3 = n_blocks(sd, u + "wac1."), n_blocks(sd, u + "wac3.")
     windows1 = [8, 6][:n1]
     for i, sh in enumerate(shift_config(n1)):
-        x = wac_block(sd, f"{u}wac1.blocks.{i}.", x, heads, windows1[i], sh)
+        x = wac_block(sd, f"{u}wac1.blocks.{i}.", x, heads, windows1[i], sh, taps=taps)
     skip = x
     sc = F.pixel_unshuffle(x, 2)
     B, C4, H, W = sc.shape
     sc = sc.view(B, C2, C4 // C2, H, W).mean(dim=2)
     x = sc + F.leaky_relu(F.conv2d(x, sd[u + "down1.conv.weight"], sd[u + "down1.conv.bias"], stride=2), 0.2)
+    _tap(taps, "down1", x)
     for i, sh in enumerate(shift_config(4)):
-        x = wac_block(sd, f"{u}wac2.blocks.{i}.", x, heads2, 8, sh)
+        x = wac_block(sd, f"{u}wac2.blocks.{i}.", x, heads2, 8, sh, taps=taps)
     sc = F.pixel_shuffle(x.repeat_interleave(C * 4 // C2, dim=1), 2)
     x = sc + F.pixel_shuffle(F.leaky_relu(F.conv2d(x, sd[u + "up1.proj.weight"], sd[u + "up1.proj.bias"]), 0.2), 2)
     x = x + skip
+    _tap(taps, "up1", x)
     for i, sh in enumerate(shift_config(n3)):
-        x = wac_block(sd, f"{u}wac3.blocks.{i}.", x, heads, 8, sh, conv_mlp=(i < n3 - 1))
+        x = wac_block(sd, f"{u}wac3.blocks.{i}.", x, heads, 8, sh, conv_mlp=(i < n3 - 1), taps=taps)
     x = F.conv2d(x, sd[u + "to_residual_image.proj.weight"], sd[u + "to_residual_image.proj.bias"])
     if scale > 1:
         x = F.pixel_shuffle(x, scale)
     x = x[:, :, scale:-scale, scale:-scale]
+    _tap(taps, "residual", x, nchw=False)
     s = F.conv2d(F.pad(src, (1, 1, 1, 1), mode="replicate"), sd[u + "to_image.resampling.weight"])
     if scale > 1:
         s = F.pixel_shuffle(s, scale)

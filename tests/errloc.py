@@ -44,6 +44,12 @@ region is one pixel — cell (1, 1) of the [T, C, 1, P] view — and for the eng
 whole net (``iw3.vda_stream``) takes T frames [T, 3, h, w] the same way, with the depth engine's cells.  ``vda_with_pe`` hands the
 fp32 sinusoidal table in through the ``pos_encoder.pe`` keys: evaluated inside the emulation mode, ``pos * div`` would be rounded to
 fp16 (up to 31 x 2^-11 rad) and the yardstick inflated (``tests/vda_cases.py``, ``tests/test_errloc_vda.py``).
+
+The swin_unet_v2 debug taps (``csrc/swin_unet_v2.hip``, ``nunif_hip_swin_unet_v2_debug_taps``) go wrong per window of their block (8 x 8
+or 6 x 6 tokens, starting at -ws / 2 in a shifted block, where the padded tokens are keys / values equal to the qkv bias), per head of
+32 channels (``att``) and per 16-channel n-tile of an epilogue: ``v2_tap_cells`` gives each tap the cells of its own block at its own
+resolution, with the tap constants (``tests/swin_v2_cases.py``, ``tests/test_errloc_swin_v2.py``).  Measured on an MI355X over the six
+cases of tests/test_gpu_swin_v2_errloc.py (profiles/swin_v2_errloc.txt): taps worst 1.33 global / 2.14 per region, output 0.55 / 0.76.
 """
 import math
 
@@ -202,8 +208,7 @@ def _forward(sd, x, name, taps=None, no_clip=False, max_depth=0.0, infer=False, 
         return OC.conv_stack_forward(sd, x, taps=taps)
     assert not no_clip, "no_clip is a cunet option"
     if name in V2_SCALE:
-        assert taps is None, "swin_unet_v2 has no taps"
-        return OV.model_forward(sd, x, V2_SCALE[name])
+        return OV.model_forward(sd, x, V2_SCALE[name], taps=taps)
     return torch.clamp(O.unet_forward(sd, x, O.GEOMETRY.get(name, (0, 0, 0, SCALE[name]))[3], taps=taps), 0.0, 1.0)
 
 
@@ -295,6 +300,31 @@ def cells_for(name, origin=0, shape=None, level=None):
         return [(ws * s, (-s - origin) % (ws * s)) for ws, _ in V2_WINDOWS]
     s = SCALE[name]
     return [(6 * s * 2 ** k, (-origin) % (6 * s * 2 ** k)) for k in range(3)]
+
+
+def v2_blocks(n1=2, n2=4, n3=3):
+    """{block name: (window, shifted)} of the WAC blocks of swin_unet_v2 in forward order (oracle/swin_unet_v2.py model_forward)."""
+    out = {"ir.path2.2": (8, True), "ir.path2.3": (8, False)}
+    for group, n, windows in (("wac1", n1, (8, 6)), ("wac2", n2, (8,) * n2), ("wac3", n3, (8,) * n3)):
+        for i, sh in enumerate(OV.shift_config(n)):
+            out[f"{group}.blocks.{i}"] = (windows[i], sh)
+    return out
+
+
+def v2_tap_cells(name, tap, blocks=None):
+    """(cells, group) of the swin_unet_v2 debug tap ``tap`` of net ``name``, at the tap's own resolution.  A block's maps (``<block>``,
+    ``<block>.att``): one cell per window of the block, starting at -ws / 2 where the block is shifted (``localised_stats`` adds the
+    partition half a window further, so both partitions are looked at for every block); group = 32 channels (one head) for ``att``,
+    16 (one MFMA n-tile of the GEMM / conv epilogues) for the outputs.  ``ir`` is the pixel-shuffled half-resolution map (windows of
+    16 pixels), ``patch`` / ``down1`` / ``up1`` take the 8 x 8 windows of their level, ``residual`` the cells of the output."""
+    blocks = blocks or v2_blocks()
+    if tap == "residual":
+        return cells_for(name), None
+    if tap in ("ir", "patch", "down1", "up1"):
+        return [(16 if tap == "ir" else 8, 0)], 16
+    block = tap[:-len(".att")] if tap.endswith(".att") else tap
+    ws, shifted = blocks[block]
+    return [(ws, (-(ws // 2)) % ws if shifted else 0)], (32 if tap.endswith(".att") else 16)
 
 
 def _pair(v):
